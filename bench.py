@@ -2,12 +2,15 @@
 """SemiVL training-step benchmark on MI355X (BASELINE.json metric: train images/sec, 512^2, ViT-B/16).
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W --full   (+ roofline profile, other arithmetic, CPU baseline, ...)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's outputs as DIR/*.npy)
 
 A "step" is one full iteration of semivl.py:223-345 on one synthetic batch per rank: CutMix, pseudo-label
 forward, MaskCLIP guidance on the frozen CLIP encoder, the two grad-carrying forwards (need_fp + strong), the fused
 per-pixel losses, backward through the VLG head and the ViT, gradient all-reduce (RCCL) and the fused AdamW step.
 images/s := (B_labeled + B_unlabeled) * world / t_step = 2*B*W / t_step, inputs resident in HBM.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line; everything else it
+can measure runs only with --full.
 """
 import argparse
 import json
@@ -82,10 +85,19 @@ def parse():
                          "16-bit-product mode for experiments and is never the default")
     ap.add_argument("--no-throughput-mode", "--no-second-mode", dest="no_throughput_mode", action="store_true",
                     help="skip the extra measurement of the other arithmetic (exact f32 next to a bf16x6 value and vice versa)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: per-kernel roofline profile, the other arithmetic, "
+                         "cross-mode losses, CPU baseline, committed numerics record, the --as-multi N = 1 anchor and (N > 1) "
+                         "the per-bucket all-reduce report; the --no-* options switch single legs off again")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): its "
+                         "losses and fixed, seeded samples of the updated parameters and of their gradients")
     a = ap.parse_args()
     if a.config is not None:
         a.nclass, a.crop, a.batch = {"voc": (21, 512, 16), "cityscapes": (19, 801, 8), "ade": (150, 512, 16),
                                      "coco": (81, 512, 16)}[a.config]
+    if not a.full:      # a plain run measures the headline figure and nothing else
+        a.no_profile = a.no_throughput_mode = a.no_cpu_baseline = a.no_multi_anchor = True
     return a
 
 
@@ -104,14 +116,23 @@ def respawn_ranks(a):
 
 
 def physical_cores():
+    """Physical cores of the host, capped by what this process may use (CPU affinity, OMP_NUM_THREADS): a thread pool
+    larger than that only slows itself down."""
+    n = None
     try:
         import psutil
         n = psutil.cpu_count(logical=False)
-        if n:
-            return int(n)
     except Exception:
         pass
-    return os.cpu_count() or 1
+    n = int(n or os.cpu_count() or 1)
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return n
 
 
 def cpu_model():
@@ -245,6 +266,22 @@ def inloop_dispatch_record():
     return None
 
 
+DUMP_SAMPLE = 1 << 22     # elements drawn from each flat parameter / gradient arena (<= 16 MB per file)
+
+
+def dump_outputs(out_dir, losses, opt):
+    """What the last timed step hands back to its caller, as float32 .npy files: the step's losses (LOSS_NAMES order)
+    and, from the optimizer's flat arenas, the parameters it updated and the gradients it applied, both at the same fixed,
+    seeded sample of positions (sorted, duplicates dropped) so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.unique(np.random.default_rng(20240611).integers(0, opt.total, DUMP_SAMPLE, dtype=np.int64))
+    idx_d = torch.from_numpy(idx).to(opt.p.device)
+    arrays = dict(losses=losses.float(), params_sample=opt.p[idx_d], grads_sample=opt.g[idx_d])
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -277,7 +314,7 @@ def main():
     model = build_model(cfg).to(dev)
     opt = FusedAdamW(model, cfg["optimizer"])
     red = GradAllReducer(opt)
-    red.profile = world > 1       # per-bucket all-reduce time + the un-overlapped remainder go into the JSON line
+    red.profile = world > 1 and a.full   # per-bucket all-reduce time + the un-overlapped remainder go into the JSON line
     red.broadcast_params()
     batch = synthetic_batch(a.batch, a.crop, a.nclass, seed=1234 + rank, device=dev)
     total_iters = 10000
@@ -310,6 +347,8 @@ def main():
     EMU = {"f32": 0, "bf16x6": 6, "bf16x3": 3}
     ops.set_gemm_emulation(EMU[a.gemm_arith])
     dt, losses = timed(a.warmup, a.steps, 0)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses, opt)
     loss_val = float(losses[0].item())
     ms = dt / a.steps * 1e3
     ips = 2.0 * a.batch * world / (dt / a.steps)
@@ -730,7 +769,7 @@ def main():
         except Exception as e:  # the baseline leg must never take the GPU number down with it
             out["cpu_baseline"] = dict(value=None, unit="images/s", cores=physical_cores(), kind="port",
                                        sample=f"failed: {type(e).__name__}: {e}")
-    if rank == 0:
+    if rank == 0 and a.full:
         # accuracy record of the arithmetic `value` runs in: worst distance from a FLOAT64 evaluation of the same step, per mode
         # and tensor family, written by tests/test_fullsize_gpu.py::test_fullsize_gradient_error_against_fp64 on the GPU box
         # and committed (profiles/numerics_fp64.json) -- bench.py itself has no oracle at B = 16
@@ -771,7 +810,7 @@ def main():
                 pass
         except Exception as e:
             out["n1_same_settings"] = dict(value=None, note=f"child run failed: {type(e).__name__}: {e}")
-    if world > 1:      # the communication side of the last timed step, so that a scaling curve explains itself
+    if world > 1 and a.full:   # the communication side of the last timed step, so that a scaling curve explains itself
         torch.cuda.synchronize()
         rep = red.timing_report()
         if rank == 0 and rep is not None:
@@ -792,7 +831,7 @@ def main():
                          "efficiency_vs_default_n1 divides by the default N = 1 line (weight-gradient stream on, 4 queues)" if same
                          else "anchor file is from another host / config: not used")
             except (OSError, ValueError, KeyError):
-                out["scaling_vs_n1_same_settings"] = dict(efficiency=None, note="no N = 1 anchor on this node yet (run `python bench.py` first)")
+                out["scaling_vs_n1_same_settings"] = dict(efficiency=None, note="no N = 1 anchor on this node yet (run `python bench.py --full` first)")
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

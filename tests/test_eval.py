@@ -109,12 +109,14 @@ def vlm_fixture():
 MODES = ("sliding_window", "zegclip_sliding_window", "original")
 
 
-def test_oracle_eval_through_vlm_matches_reference_fixture():
+def test_oracle_eval_through_vlm_matches_reference_fixture(request):
     """The oracle VLM under the oracle `predict` restatements == the reference's VLM under the reference's `predict` on a
     160x150 image (windows of 128x128, 128x65, 75x128, 75x65 pixels; whole-image mode)."""
     from golden_util import build_oracle, fixture_state
     from oracle import eval_oracle as E
     z, c, img, mask = vlm_fixture()
+    # (restored afterwards: later tests size their own thread pools from torch.get_num_threads())
+    request.addfinalizer(lambda n=torch.get_num_threads(): torch.set_num_threads(n))
     torch.set_num_threads(8)
     orc = build_oracle(c)
     orc.load_state_dict(fixture_state(z, c, orc), strict=True)

@@ -273,6 +273,8 @@ def test_collective_kernels_own_their_queue_and_run_under_backward(dev):
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not on PATH")
     env = dict(os.environ, TAG="test", GRAFT_REPO_ROOT=ROOT, SVL_COMM_B="4")
+    # eight hardware queues, the setting of every rank of a multi-GPU run, also where the caller's environment sets fewer
+    env["GPU_MAX_HW_QUEUES"] = "8"
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "comm_overlap_trace.sh")], env=env, capture_output=True, text=True,
                        timeout=900)
     print(r.stdout[-2000:])

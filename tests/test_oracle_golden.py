@@ -8,9 +8,11 @@ from golden_util import build_oracle, fixture_batch, fixture_fp_masks, fixture_s
 
 
 @pytest.mark.parametrize("name", ["tiny", "vlgdim", "offsize", "skr", "conf"])
-def test_oracle_reproduces_reference_step(name):
+def test_oracle_reproduces_reference_step(name, request):
     from oracle import semivl_oracle as O
     z, c = load_fixture(name)
+    # (restored afterwards: later tests size their own thread pools from torch.get_num_threads())
+    request.addfinalizer(lambda n=torch.get_num_threads(): torch.set_num_threads(n))
     torch.set_num_threads(8)
     orc = build_oracle(c)
     orc.load_state_dict(fixture_state(z, c, orc), strict=True)

@@ -1,4 +1,5 @@
-# End-of-round evidence run on the 1-GPU box:  gpurun -- 'TAG=r6_x bash tools/round_end_run.sh'   (everything lands in gpurun_out/)
+# End-of-round evidence run on a 1-GPU box:  TAG=r6_x bash tools/round_end_run.sh   (the bench lines, all with --full, are
+# written to profiles/${TAG}_bench_*; the other records to the output folder named below)
 cd $GRAFT_REPO_ROOT
 T=${TAG:-r6}
 python -m pytest tests -m gpu -q --durations=8 -s 2>&1 | grep -v "^$" | grep -E "passed|failed|FAILED|RATCHET|BF16X3|RESULT|s call|s setup" | cut -c1-400 | tail -40 > gpurun_out/${T}_pytest.log
@@ -26,18 +27,18 @@ for m in bf16x6 f32; do
 done
 # the records bench.py quotes must be in profiles/ BEFORE the default line is taken
 mkdir -p profiles && cp gpurun_out/pmc_x6p_traffic.json gpurun_out/pmc_gemm_traffic.json gpurun_out/dominant_dispatches.json gpurun_out/inloop_dispatches.json gpurun_out/numerics_fp64.json profiles/ 2>/dev/null
-python bench.py --steps 10 --warmup 3 > gpurun_out/${T}_bench_default.json 2> gpurun_out/${T}_bench_default.err
-for c in cityscapes ade coco; do python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-multi-anchor > gpurun_out/${T}_bench_$c.json 2>/dev/null; done
-python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-throughput-mode --no-multi-anchor --gemm-arith f32 > gpurun_out/${T}_bench_exact_f32.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 > profiles/${T}_bench_default.json 2> profiles/${T}_bench_default.err
+for c in cityscapes ade coco; do python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-multi-anchor > profiles/${T}_bench_$c.json 2>/dev/null; done
+python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-throughput-mode --no-multi-anchor --gemm-arith f32 > profiles/${T}_bench_exact_f32.json 2>/dev/null
 # BASELINE configs[4] names "fp16 mixed precision": a build-only mode, no reference counterpart -- recorded as such
-python bench.py --config coco --gemm-arith bf16x3 --steps 3 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-multi-anchor > gpurun_out/${T}_bench_coco_bf16x3_build_only_mode.json 2>/dev/null
+python bench.py --full --config coco --gemm-arith bf16x3 --steps 3 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-multi-anchor > profiles/${T}_bench_coco_bf16x3_build_only_mode.json 2>/dev/null
 # the N > 1 code path on this one-GPU box: two ranks over gloo (blocking all-reduce), and the stream-ordered branch traced
-SVL_DIST_BACKEND=gloo python bench.py --gpus 2 --batch 4 --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-profile > gpurun_out/${T}_bench_gloo2.json 2> gpurun_out/${T}_bench_gloo2.err
+SVL_DIST_BACKEND=gloo python bench.py --full --gpus 2 --batch 4 --steps 2 --warmup 1 --no-cpu-baseline --no-throughput-mode --no-profile > profiles/${T}_bench_gloo2.json 2> profiles/${T}_bench_gloo2.err
 TAG=$T SVL_COMM_B=16 bash tools/comm_overlap_trace.sh > /dev/null 2>&1
 python tools/shape_table.py voc > gpurun_out/${T}_shapes_voc.txt 2>/dev/null
 python tools/shape_table.py ade > gpurun_out/${T}_shapes_ade.txt 2>/dev/null
 for c in ade coco cityscapes; do TAG=${T}_$c bash tools/prof_step.sh --config $c > /dev/null 2>&1; done
 tail -4 gpurun_out/${T}_pytest.log
 for f in default cityscapes ade coco exact_f32 coco_bf16x3_build_only_mode; do python -c "
-import json; d=json.loads(open('gpurun_out/${T}_bench_$f.json').read().strip().splitlines()[-1]); r=d.get('roofline',{}); print('$f', d['value'], d['ms_per_step'], d['config']['peak_mem_gb'], r.get('frac'), r.get('avg_ms'), (d.get('exact_f32') or {}).get('value'))"; done
+import json; d=json.loads(open('profiles/${T}_bench_$f.json').read().strip().splitlines()[-1]); r=d.get('roofline',{}); print('$f', d['value'], d['ms_per_step'], d['config']['peak_mem_gb'], r.get('frac'), r.get('avg_ms'), (d.get('exact_f32') or {}).get('value'))"; done
 tail -3 gpurun_out/${T}_comm_overlap.txt
