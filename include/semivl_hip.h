@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -83,7 +83,15 @@ enum {
 enum {
   SVL_B_KCONTIG = 0, /* B(n,k) = B[n*ldb + k]   (torch Linear weight [out,in], K rows, packed conv w) */
   SVL_B_NCONTIG = 1, /* B(n,k) = B[k*ldb + n]   (dgrad: W as [K=out][N=in]; V in P·V; X in wgrad)     */
-  SVL_B_CONVW = 2    /* B(n,k): n = (tap, ci), k = NHWC pixel: im2col^T for conv wgrad                */
+  SVL_B_CONVW = 2,   /* B(n,k): n = (tap, ci), k = NHWC pixel: im2col^T for conv wgrad                */
+  /* B-operand producers of the weight gradients (A = SVL_A_MCONTIG only): the operand is computed while staging, never
+   * materialised in fp32.  Every arithmetic of svl_set_gemm_emulation serves them; the operand-maximum pass of the fp16 x 2
+   * form (emu_ws) sees the transformed values. */
+  SVL_B_NC_GELU = 3, /* B(n,k) = gelu_erf(B[k*ldb + n]) (the SVL_ACT_GELU function of a saved pre-activation)       */
+  SVL_B_NC_LN = 4,   /* B(n,k) = (B[k*ldb + n] - mean_k) * rstd_k * b_gamma[n] + b_beta[n], {mean, rstd} =
+                      * b_stats[2k], b_stats[2k+1] (the statistics svl_layernorm_fwd wrote)                           */
+  SVL_B_PATCHT = 5   /* B(n,k): n = (c, i, j), k = (img, py, px) of an NCHW image, patch P = conv.patch, grid
+                      * ceil(H/P) x ceil(W/P) with bottom / right zero fill: the transposed twin of SVL_A_PATCH     */
 };
 enum {
   SVL_ACT_NONE = 0,
@@ -158,6 +166,9 @@ typedef struct svl_gemm_desc {
                               * products instead of six -- with ONE power-of-two scale per operand tensor, found by a maximum
                               * pass over exactly the elements the launch reads (a per-row scale does not factor out of a
                               * convolution's taps).  Same error level vs fp64 (tests/test_ops_gpu.py); NULL: bf16 x 3 terms. */
+  const float* b_stats;      /* SVL_B_NC_LN: [K][2] row statistics {mean, rstd} of the B source rows                     */
+  const float* b_gamma;      /* SVL_B_NC_LN: [N] LayerNorm weight                                                         */
+  const float* b_beta;       /* SVL_B_NC_LN: [N] LayerNorm bias                                                           */
 } svl_gemm_desc;
 
 int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream);

@@ -57,6 +57,9 @@ struct GemmP {
   int accumulate;
   int tiles_n, tiles_m, band_n;
   const unsigned* amax;   // fp16 x 2 form of the split kernel: device {bits of max |A|, bits of max |B|} over the operands' elements
+  const float* b_stats;   // SVL_B_NC_LN: {mean, rstd} per k; b_gamma / b_beta per n
+  const float* b_gamma;
+  const float* b_beta;
 };
 
 int svl_gemm_part_mode_dense(int am, int bm, const GemmP& p, int batch, hipStream_t st);   // part 1
@@ -122,6 +125,29 @@ template <> struct ModeTraits<1, SVL_A_PATCH>   { static constexpr int shape = L
 template <> struct ModeTraits<0, SVL_B_KCONTIG> { static constexpr int shape = LS_KMAJOR; };
 template <> struct ModeTraits<0, SVL_B_NCONTIG> { static constexpr int shape = LS_RMAJOR; };
 template <> struct ModeTraits<0, SVL_B_CONVW>   { static constexpr int shape = LS_RMAJOR; };
+template <> struct ModeTraits<0, SVL_B_NC_GELU> { static constexpr int shape = LS_RMAJOR; };
+template <> struct ModeTraits<0, SVL_B_NC_LN>   { static constexpr int shape = LS_RMAJOR; };
+template <> struct ModeTraits<0, SVL_B_PATCHT>  { static constexpr int shape = LS_RMAJOR; };
+// B-operand producers: the raw value read at (n, k) is the NCONTIG element; the transform is applied after the load
+template <int IS_A, int MODE>
+constexpr bool raw_ncontig() { return MODE == 1 || (!IS_A && (MODE == SVL_B_NC_GELU || MODE == SVL_B_NC_LN)); }
+
+// SVL_B_PATCHT piece: 4 consecutive n = (c, i, j..j+3) (P % 4 == 0, so one patch row) of token k = (img, py, px).
+// Pixels past the image's bottom / right edge read 0 (the zero fill of SVL_A_PATCH).
+__device__ __forceinline__ float4 patcht_piece(const svl_conv_geom& cv, const float* base, int row, int k, bool vec) {
+  const int P = cv.patch;
+  const int npx = (cv.W + P - 1) / P, npy = (cv.H + P - 1) / P;
+  const int px = k % npx;
+  const int t = k / npx;
+  const int py = t % npy;
+  const int img = t / npy;
+  const int c = row / (P * P);
+  const int r2 = row - c * P * P;
+  const int i = r2 / P, j = r2 - i * P;
+  const int y = py * P + i, x = px * P + j;
+  if (y >= cv.H) return zero4();
+  return load4(base + (((long)img * cv.C1 + c) * cv.H + y) * cv.W + x, min(4, cv.W - x), vec);
+}
 
 // Address of logical conv input element (pixel given by (img, ih, iw) already bounds-checked, channel ci).
 __device__ __forceinline__ const float* conv_src(const OperandP& op, const svl_conv_geom& cv, int img, int ih, int iw,
@@ -193,8 +219,10 @@ __device__ __forceinline__ float4 load_piece(const OperandP& op, const svl_conv_
     const int k = k0 + kk;
     if (k >= kend || row >= rows_total) return zero4();
     const int nv = rows_total - row;
-    if constexpr (MODE == 1) {  // SVL_A_MCONTIG / SVL_B_NCONTIG share value 1
+    if constexpr (raw_ncontig<IS_A, MODE>()) {  // SVL_A_MCONTIG / SVL_B_NCONTIG share value 1; NC producers
       return load4(base + (long)k * op.ld + row, nv, op.vec);
+    } else if constexpr (!IS_A && MODE == SVL_B_PATCHT) {
+      return patcht_piece(cv, base, row, k, op.vec);
     } else {  // SVL_B_CONVW: row = (tap, ci), k = pixel
       const int Ct = cv.C1 + cv.C2;
       const int ow = (k % cv.Wo) * cv.stride;
@@ -312,8 +340,10 @@ __device__ __forceinline__ float4 load_piece_fast(const OperandP& op, const svl_
     const int kk = f / RP;
     const int row = row0 + ((f % RP) << 2);
     const int k = k0 + kk;
-    if constexpr (MODE == 1) {
+    if constexpr (raw_ncontig<IS_A, MODE>()) {
       return *reinterpret_cast<const float4*>(base + (long)k * op.ld + row);
+    } else if constexpr (!IS_A && MODE == SVL_B_PATCHT) {   // (vec: every patch inside the image)
+      return patcht_piece(cv, base, row, k, true);
     } else {
       const int Ct = cv.C1 + cv.C2;
       const int ow = (k % cv.Wo) * cv.stride;
@@ -345,6 +375,25 @@ __device__ __forceinline__ void store_piece(float* S, int f, float4 v) {
     const int row = (f % RP) << 2;
     *reinterpret_cast<float4*>(&S[kk * LD + row]) = v;
   }
+}
+
+// Producer transform of one staged B piece (4 consecutive n at one k, LS_RMAJOR) of the exact kernel.  GELU maps the zero
+// fill to 0; the LayerNorm form reads its statistics / affine parameters only for k < kend, n < N and leaves 0 elsewhere.
+template <int BMODE, int ROWS, int BK>
+__device__ __forceinline__ float4 b_xform(const GemmP& p, float4 v, int f, int row0, int k0, int kend) {
+  if constexpr (BMODE == SVL_B_NC_GELU) {
+    v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
+  } else if constexpr (BMODE == SVL_B_NC_LN) {
+    constexpr int RP = ROWS / 4;
+    const int k = k0 + f / RP, row = row0 + ((f % RP) << 2);
+    if (k >= kend || row >= p.N) return zero4();
+    const float mean = p.b_stats[2 * (long)k], rstd = p.b_stats[2 * (long)k + 1];
+    float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = row + j < p.N ? (e[j] - mean) * rstd * p.b_gamma[row + j] + p.b_beta[row + j] : 0.f;
+    v = make_float4(e[0], e[1], e[2], e[3]);
+  }
+  return v;
 }
 
 // Shared epilogue of the MFMA GEMM kernels.  C/D layout of the 32x32 MFMAs (dtype independent on gfx950):
@@ -595,7 +644,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM >= 64 ? 
             rb[ps] = conv_load_st(p.B, p.cv, stb[ps]);
             conv_advance_pixel<BK>(p.cv, stb[ps]);
           } else {
-            rb[ps] = load_piece_fast<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, k0);
+            rb[ps] = b_xform<BMODE, BN, BK>(p, load_piece_fast<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, k0), f, n0, k0, kend);
           }
         }
       }
@@ -604,7 +653,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM >= 64 ? 
       for (int ps = 0; ps < BPASS; ++ps) {
         const int f = tid + ps * 256;
         if (BPIECES % 256 == 0 || f < BPIECES)
-          rb[ps] = load_piece<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, p.N, k0, kend);
+          rb[ps] = b_xform<BMODE, BN, BK>(p, load_piece<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, p.N, k0, kend), f, n0, k0,
+                                          kend);
       }
     }
   };
@@ -681,7 +731,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BM >= 64 ? 
               rb[ps] = conv_load_st(p.B, p.cv, stb[ps]);
               conv_advance_pixel<BK>(p.cv, stb[ps]);
             } else {
-              rb[ps] = load_piece_fast<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, k0);
+              rb[ps] = b_xform<BMODE, BN, BK>(p, load_piece_fast<0, BMODE, BN, BK>(p.B, p.cv, Bbase, f, n0, k0), f, n0, k0,
+                                              kend);
             }
           }
         }
@@ -1058,6 +1109,24 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
   m = block_max_256(m, red);
   if (threadIdx.x == 0 && m > 0.f) atomicMax(out, __float_as_uint(m));
 }
+// the same over the TRANSFORMED elements of a producer operand (SVL_B_NC_GELU / SVL_B_NC_LN) B(n, k), k < K, n < N: the
+// scale of the fp16 x 2 form must come from the values the kernel splits, not from the raw source (a LayerNorm's gamma / beta
+// and row statistics can take the operand far above or below its input)
+__global__ __launch_bounds__(256) void absmax_bx_kernel(const float* __restrict__ x, long K, int N, long ld, int mode,
+                                                        const float* __restrict__ st, const float* __restrict__ gm,
+                                                        const float* __restrict__ bt, unsigned* out) {
+  __shared__ float red[4];
+  float m = 0.f;
+  const long n_all = K * N;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_all; i += (long)gridDim.x * 256) {
+    const long k = i / N;
+    const int n = (int)(i - k * N);
+    const float v = x[k * ld + n];
+    m = fmaxf(m, fabsf(mode == SVL_B_NC_GELU ? gelu_erf(v) : (v - st[2 * k]) * st[2 * k + 1] * gm[n] + bt[n]));
+  }
+  m = block_max_256(m, red);
+  if (threadIdx.x == 0 && m > 0.f) atomicMax(out, __float_as_uint(m));
+}
 
 // B operand = im2col(x)^T (SVL_B_CONVW, the weight gradient of an implicit-GEMM convolution): row n = (tap, ci) is FIXED
 // per thread for the whole K loop, k = output pixel advances.  A thread's 8 consecutive k are 8 consecutive pixels of one
@@ -1102,6 +1171,53 @@ __device__ __forceinline__ void convbt_load(const GemmP& p, ConvBT& s, EmuRaw& r
   while (s.ow >= cv.Wo) {
     s.ow -= cv.Wo;
     if (++s.oh == cv.Ho) { s.oh = 0; ++s.img; }
+  }
+}
+
+// B-operand producers of the split kernel (B_RM 3 / 4 / 5 = SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT; row-contiguous
+// store shape): a thread owns row n and 8 consecutive k = kb .. kb + 7, of which the first `nvalid` are in range.  The
+// transform runs on the loaded fp32 values, before the split.
+template <int B_RM>
+__device__ __forceinline__ void emu_bxform(const GemmP& p, EmuRaw& r, long n, int kb, int nvalid) {
+  if constexpr (B_RM == 3) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.v[j] = gelu_erf(r.v[j]);   // (gelu(0) = 0: the zero fill stays)
+  } else if constexpr (B_RM == 4) {
+    const float g = p.b_gamma[n], b = p.b_beta[n];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (j < nvalid) {
+        const long k = kb + j;
+        r.v[j] = (r.v[j] - p.b_stats[2 * k]) * p.b_stats[2 * k + 1] * g + b;
+      } else {
+        r.v[j] = 0.f;
+      }
+    }
+  }
+}
+// SVL_B_PATCHT: n = (c, i, j) fixed per thread, the 8 k are consecutive tokens (img, py, px): decomposed once, then walked
+// with carries.  Pixels past the image's bottom / right edge (and k past the slab) read 0.
+__device__ __forceinline__ void emu_patcht_load(const GemmP& p, const float* img0, long n, int kb, int nvalid, EmuRaw& r) {
+  const svl_conv_geom& cv = p.cv;
+  const int P = cv.patch;
+  const int npx = (cv.W + P - 1) / P, npy = (cv.H + P - 1) / P;
+  const int c = (int)n / (P * P);
+  const int r2 = (int)n - c * P * P;
+  const int i = r2 / P, jj = r2 - i * P;
+  int px = kb % npx;
+  int t = kb / npx;
+  int py = t % npy;
+  int img = t / npy;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int y = py * P + i, x = px * P + jj;
+    float v = 0.f;
+    if (j < nvalid && y < cv.H && x < cv.W) v = img0[(((long)img * cv.C1 + c) * cv.H + y) * cv.W + x];
+    r.v[j] = v;
+    if (++px == npx) {
+      px = 0;
+      if (++py == npy) { py = 0; ++img; }
+    }
   }
 }
 
@@ -1170,7 +1286,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     cs1.ti = cs0.ti; cs1.tj = cs0.tj; cs1.ci = cs0.ci;
   };
   constexpr bool B_CV = B_RM == 2;   // B operand = im2col^T of an NHWC tensor (row-contiguous store shape, conv addressing)
-  const float* pb = B_CV ? B : B + (B_RM ? b_r : b_r * p.B.ld) + (long)(kbeg + b_ko) * b_ks;
+  constexpr bool B_PT = B_RM == 5;   // B operand = transposed patch matrix of an NCHW image (own addressing)
+  const float* pb = (B_CV || B_PT) ? B : B + (B_RM ? b_r : b_r * p.B.ld) + (long)(kbeg + b_ko) * b_ks;
   ConvBT cbt;
   if constexpr (B_CV) convbt_init(p, (int)b_r, kbeg + b_ko, cbt);   // (like the conv A operand: loads are requested in step order)
   const long a_d2 = A_RM ? 0 : (a_r2 - a_r) * p.A.ld, b_d2 = B_RM ? 0 : (b_r2 - b_r) * p.B.ld;  // second-row offsets
@@ -1204,13 +1321,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (A_CV) aload_conv(xa);            // (K % 16 == 0 for this mode: every step is a full one)
       else emu_gload<A_RM>(xa, qa, qa + a_d2, a_ks, a_vec);
       if constexpr (B_CV) convbt_load<BKE>(p, cbt, xb);   // (16-aligned K slabs for this mode: every step is a full one)
+      else if constexpr (B_PT) emu_patcht_load(p, B, b_r, kbeg + b_ko + t * BKE, 8, xb);
       else emu_gload<B_RM>(xb, qb, qb + b_d2, b_ks, b_vec);
+      emu_bxform<B_RM>(p, xb, b_r, kbeg + b_ko + t * BKE, 8);
     } else if (t < nk) {
       const int rem = klen - t * BKE;
       const float* qa = pa + (long)t * BKE * a_ks;
       const float* qb = pb + (long)t * BKE * b_ks;
       emu_gload_tail<A_ST>(xa, qa, qa + a_d2, a_ks, rem - a_ko);
-      if constexpr (!B_CV) emu_gload_tail<B_RM>(xb, qb, qb + b_d2, b_ks, rem - b_ko);
+      if constexpr (B_PT) emu_patcht_load(p, B, b_r, kbeg + b_ko + t * BKE, rem - b_ko, xb);
+      else if constexpr (!B_CV) emu_gload_tail<B_RM>(xb, qb, qb + b_d2, b_ks, rem - b_ko);
+      emu_bxform<B_RM>(p, xb, b_r, kbeg + b_ko + t * BKE, rem - b_ko);
     }
   };
   auto sstore = [&](const EmuRaw& xa, const EmuRaw& xb, int buf) {
@@ -1267,6 +1388,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const long a_step = (long)BKE * a_ks, b_step = (long)BKE * b_ks;
     const float* qa = pa + 3 * a_step;
     const float* qb = pb + 3 * b_step;
+    int tq = 3;   // the K step the loads of the next fast_step fetch (producer modes)
     // One K step with an explicit schedule: MFMA m of the step is followed by its share of the next step's split
     // (one cvt_pk + residual update per pair of values and plane), fenced so that the matrix pipe and the VALU overlap
     // inside the wave; the LDS stores of an operand follow the slice that completes it.
@@ -1275,7 +1397,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (A_CV) aload_conv(la);
       else emu_gload<A_RM>(la, qa, qa + a_d2, a_ks, true);
       if constexpr (B_CV) convbt_load<BKE>(p, cbt, lb);
+      else if constexpr (B_PT) emu_patcht_load(p, B, b_r, kbeg + b_ko + tq * BKE, 8, lb);
       else emu_gload<B_RM>(lb, qb, qb + b_d2, b_ks, true);
+      emu_bxform<B_RM>(p, lb, b_r, kbeg + b_ko + tq * BKE, 8);
+      ++tq;
       qa += a_step;
       qb += b_step;
       // opaque re-definition: keeps this step's split after the previous barrier (it is pure register arithmetic on
@@ -1422,6 +1547,9 @@ int launch_emu(const GemmP& p, int a_rm, int b_rm, int batch, hipStream_t st) {
   const long tiles = (long)((p.M + 127) / 128) * q.tiles_n;
   dim3 grid((unsigned)tiles, 1, (unsigned)batch);
   if (b_rm == 2) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 1, 2, H2>), grid, dim3(256), 0, st, q);
+  else if (b_rm == 3) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 1, 3, H2>), grid, dim3(256), 0, st, q);
+  else if (b_rm == 4) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 1, 4, H2>), grid, dim3(256), 0, st, q);
+  else if (b_rm == 5) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 1, 5, H2>), grid, dim3(256), 0, st, q);
   else if (a_rm == 2) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 2, 0, H2>), grid, dim3(256), 0, st, q);
   else if (a_rm == 0 && b_rm == 0) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 0, 0, H2>), grid, dim3(256), 0, st, q);
   else if (a_rm == 0 && b_rm == 1) hipLaunchKernelGGL((gemm_bf16x_kernel<NS, 0, 1, H2>), grid, dim3(256), 0, st, q);
@@ -1544,6 +1672,16 @@ int absmax_launch(const float* x, long rows, long cols, long ld, unsigned* out, 
   return SVL_OK;
 }
 
+int absmax_bx_launch(const GemmP& q, int mode, unsigned* out, hipStream_t st) {
+  const long work = (long)q.K * q.N;
+  long blocks = (work + 256 * 8 - 1) / (256 * 8);
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  hipLaunchKernelGGL(absmax_bx_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q.B.p, (long)q.K, q.N, q.B.ld, mode,
+                     q.b_stats, q.b_gamma, q.b_beta, out);
+  SVL_LAUNCH_CHECK("svl_gemm_f32 (producer operand maximum)");
+  return SVL_OK;
+}
+
 #endif
 }  // namespace
 
@@ -1552,11 +1690,15 @@ int svl_gemm_part_mode_dense(int am, int bm, const GemmP& p, int batch, hipStrea
   if (am == SVL_A_KCONTIG && bm == SVL_B_KCONTIG) return launch_mode<SVL_A_KCONTIG, SVL_B_KCONTIG>(p, batch, st);
   if (am == SVL_A_KCONTIG && bm == SVL_B_NCONTIG) return launch_mode<SVL_A_KCONTIG, SVL_B_NCONTIG>(p, batch, st);
   if (am == SVL_A_MCONTIG && bm == SVL_B_NCONTIG) return launch_mode<SVL_A_MCONTIG, SVL_B_NCONTIG>(p, batch, st);
+  // producers (weight gradients: large M and N): one tile shape
+  if (bm == SVL_B_NC_GELU) return launch_cfg<128, 128, 2, 2, SVL_A_MCONTIG, SVL_B_NC_GELU>(p, batch, st);
+  if (bm == SVL_B_NC_LN) return launch_cfg<128, 128, 2, 2, SVL_A_MCONTIG, SVL_B_NC_LN>(p, batch, st);
   return launch_mode<SVL_A_MCONTIG, SVL_B_KCONTIG>(p, batch, st);
 }
 #elif SVL_GEMM_PART == 2
 int svl_gemm_part_mode_conv(int am, int bm, const GemmP& p, int batch, hipStream_t st) {
   if (am == SVL_A_CONV) return launch_mode<SVL_A_CONV, SVL_B_KCONTIG>(p, batch, st);
+  if (bm == SVL_B_PATCHT) return launch_cfg<128, 128, 2, 2, SVL_A_MCONTIG, SVL_B_PATCHT>(p, batch, st);
   if (am == SVL_A_MCONTIG) return launch_mode<SVL_A_MCONTIG, SVL_B_CONVW>(p, batch, st);
   (void)bm;
   return launch_mode<SVL_A_PATCH, SVL_B_KCONTIG>(p, batch, st);
@@ -1631,6 +1773,23 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     p.A.vec = dense_vec(d->A);
   }
   p.B.vec = b_conv ? conv_vec(d->B) : dense_vec(d->B);
+  const bool b_prod = d->b_mode == SVL_B_NC_GELU || d->b_mode == SVL_B_NC_LN || d->b_mode == SVL_B_PATCHT;
+  if (b_prod) {
+    SVL_CHECK_ARG(d->a_mode == SVL_A_MCONTIG && d->out_mode == SVL_OUT_STRIDED && (d->batch == 1 || d->ksplit > 0),
+                  "svl_gemm_f32: B producers need A = SVL_A_MCONTIG, a strided output and no operand batch");
+    p.b_stats = d->b_stats; p.b_gamma = d->b_gamma; p.b_beta = d->b_beta;
+  }
+  if (d->b_mode == SVL_B_NC_LN)
+    SVL_CHECK_ARG(d->b_stats && d->b_gamma && d->b_beta, "svl_gemm_f32: SVL_B_NC_LN needs b_stats / b_gamma / b_beta");
+  if (d->b_mode == SVL_B_PATCHT) {
+    const int P = cv.patch;
+    SVL_CHECK_ARG(P > 0 && P % 4 == 0 && cv.H > 0 && cv.W > 0 && cv.C1 > 0 && d->N == cv.C1 * P * P,
+                  "svl_gemm_f32: bad transposed-patch geometry");
+    const long npimg = (long)((cv.H + P - 1) / P) * ((cv.W + P - 1) / P);
+    SVL_CHECK_ARG(d->K % npimg == 0, "svl_gemm_f32: transposed-patch K is not whole images");
+    // vector / unguarded loads only when every patch lies inside the image
+    p.B.vec = aligned16(d->B.ptr) && (cv.W % 4 == 0) && (cv.H % P == 0) && (cv.W % P == 0);
+  }
   if (d->out_mode == SVL_OUT_CONVT2X)
     SVL_CHECK_ARG(d->ct_H > 0 && d->ct_W > 0 && d->ct_Cout > 0 && d->N == 4 * d->ct_Cout,
                   "svl_gemm_f32: bad convT geometry");
@@ -1661,6 +1820,35 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     return SVL_OK;
   };
   auto launch = [&](const GemmP& q) -> int {
+    // B-operand producers of the ViT weight gradients (dY^T @ f(X)): the dense thresholds of the split emulation
+    if (b_prod) {
+      if ((emu_mode == 3 || emu_mode == 6) && q.M >= 256 && q.N >= 96 && q.K >= 64) {
+        g_last_path = SVL_PATH_BF16X;
+        const double b_elems = bm == SVL_B_PATCHT ? (double)q.K * q.cv.patch * q.cv.patch * q.cv.C1 : (double)q.N * q.K;
+        const double elems = (double)q.M * q.K + b_elems;
+        if (h2_ok(q, elems) && 2.0 * q.M * q.N * q.K * 1.7e-15 > elems * 4.0 / 4.0e12 * 1.5) {
+          int rc = h2_begin();
+          if (!rc) rc = absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st);
+          if (!rc) {
+            if (bm == SVL_B_PATCHT) {   // the zero fill adds only zeros: the image's own maximum is the operand's
+              const int P = q.cv.patch;
+              const long imgs = q.K / ((long)((q.cv.H + P - 1) / P) * ((q.cv.W + P - 1) / P));
+              rc = absmax_launch(q.B.p, imgs * q.cv.C1 * q.cv.H, q.cv.W, q.cv.W, h2_ws + 1, st);
+            } else {
+              rc = absmax_bx_launch(q, bm, h2_ws + 1, st);
+            }
+          }
+          if (rc) return rc;
+          GemmP q2 = q;
+          q2.amax = h2_ws;
+          g_last_path = SVL_PATH_H2X;
+          return svl_gemm_part_emu2(1, q2, 1, bm, d->batch, st);
+        }
+        return emu_mode == 6 ? svl_gemm_part_emu3(q, 1, bm, d->batch, st) : svl_gemm_part_emu2(0, q, 1, bm, d->batch, st);
+      }
+      return bm == SVL_B_PATCHT ? svl_gemm_part_mode_conv(am, bm, q, d->batch, st)
+                                : svl_gemm_part_mode_dense(am, bm, q, d->batch, st);
+    }
     // implicit-GEMM convolutions (NHWC im2col on the fly, forward and mirrored-tap input gradient) join the split
     // emulation when every 4-k piece stays inside one tap (channels % 4) and K is a whole number of 16-deep steps
     if ((emu_mode == 3 || emu_mode == 6) && am == SVL_A_CONV && bm == SVL_B_KCONTIG && d->out_mode == SVL_OUT_STRIDED &&

@@ -141,9 +141,13 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
     return xo, v
 
 
-def block_backward(dxo, dv, p, s, heads, Bn, T, train_ffn_ln=False, dxo_p=None):
-    """Returns (dx_in, dx_in planes or None, grads dict).  Attention projections are the trainable part of the backbone
-    (vlm.py:66-67); `train_ffn_ln` additionally produces FFN / LN weight grads (decoder's SemanticTransformer).
+FFN_LN_KEYS = ("ln1w", "ln1b", "ln2w", "ln2b", "w1", "b1", "w2", "b2")
+
+
+def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
+    """Returns (dx_in, dx_in planes or None, grads dict).  The attention projections' pieces are always collected (the
+    `ftap` recipes train them, vlm.py:66-67); `want` names the FFN / LayerNorm tensors (plist keys, FFN_LN_KEYS) that
+    train too (freeze_backbone=False or a wider exclude_keys): only their weight-gradient pieces are produced.
     `dxo_p`: dxo as packed planes when the block above already produced them (its LN1 backward)."""
     x, y1 = s["x"], s["y1"]
     E = x.shape[1]
@@ -153,31 +157,35 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, train_ffn_ln=False, dxo_p=None):
     dx_res = None
     dqkv = dqkv_p = None
     wout_parts = []  # (dy, input) pairs contributing to out_proj wgrad
+    need_h = "w1" in want or "b1" in want
 
-    def ffn_ln_bwd(dout, dout_p, pre_ln_in, st2, h_pre, tag):
+    def ffn_ln_bwd(dout, dout_p, pre_ln_in, st2, h_pre):
         """-> (d pre_ln_in, the same as planes or None)"""
-        # (dout W2) * GELU'(h_pre), one pass; with frozen FFN weights its only consumer is the next GEMM (bf16 planes)
+        # (dout W2) * GELU'(h_pre), one pass; with frozen FFN-1 weights its only consumer is the next GEMM (bf16 planes)
         a_ = dout_p if dout_p is not None else dout
-        dhp = ops.matmul_nn(a_, p["w2"], dact=ops.ACT_MUL_DGELU, z=h_pre, planes_only=not train_ffn_ln)
+        dhp = ops.matmul_nn(a_, p["w2"], dact=ops.ACT_MUL_DGELU, z=h_pre, planes_only=not need_h)
         dy2 = ops.matmul_nn(dhp, p["w1"])
-        if train_ffn_ln:
-            # recompute h = gelu(h_pre) and y2 = LN(pre_ln_in) for the weight grads (cheap vs. saving them)
-            y2, _ = ops.layernorm_fwd(pre_ln_in, p["ln2w"], p["ln2b"], s["eps"])
-            hh = ops.gelu(h_pre)
-            g.setdefault("w2", []).append((dout, hh))
-            g.setdefault("b2", []).append(dout)
-            g.setdefault("w1", []).append((dhp, y2))
-            g.setdefault("b1", []).append(dhp)
+        # weight-gradient pieces: gelu(h_pre) and LN2(pre_ln_in) are B-operand producers of the weight-gradient GEMMs
+        # (recomputed while staging from the saved pre-activation / LayerNorm statistics, never materialised)
+        if "w2" in want:
+            g.setdefault("w2", []).append(("gelu", dout, h_pre))
+        if "b2" in want:
+            g.setdefault("b2", []).append(("sum", dout))
+        if "w1" in want:
+            g.setdefault("w1", []).append(("ln", dhp, pre_ln_in, st2))
+        if "b1" in want:
+            g.setdefault("b1", []).append(("sum", dhp))
+        if "ln2w" in want or "ln2b" in want:
             r_ = ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout, want_wgrad=True, planes=pp)
-            g.setdefault("ln2w", []).append(r_[1])
-            g.setdefault("ln2b", []).append(r_[2])
+            g.setdefault("ln2w", []).append(("add", r_[1]))
+            g.setdefault("ln2b", []).append(("add", r_[2]))
             return r_[0], (r_[3] if pp else None)
         if pp:
             return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout, planes=True)
         return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout), None
 
     if not s["skip_x"] and dxo is not None:
-        dx2, dx2p = ffn_ln_bwd(dxo, dxo_p, s["x2"], s["st2"], s["h_pre"], "x")
+        dx2, dx2p = ffn_ln_bwd(dxo, dxo_p, s["x2"], s["st2"], s["h_pre"])
         do = ops.matmul_nn(dx2p if dx2p is not None else dx2, p["wout"])
         wout_parts.append((dx2, s["o"]))
         if D == 64 and pp and ops.attention_planes_ok() and not (s["want_v"] and dv is not None):
@@ -190,7 +198,7 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, train_ffn_ln=False, dxo_p=None):
         dx_res = dx2
     dvproj = None
     if s["want_v"] and dv is not None:
-        dvo, dvop = ffn_ln_bwd(dv, None, s["vo"], s["st2v"], s["hv_pre"], "v")
+        dvo, dvop = ffn_ln_bwd(dv, None, s["vo"], s["st2v"], s["hv_pre"])
         dvproj = ops.matmul_nn(dvop if dvop is not None else dvo, p["wout"])
         wout_parts.append((dvo, s["vproj"]))
         dx_res = dvo if dx_res is None else ops.add(dx_res, dvo)
@@ -207,14 +215,39 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, train_ffn_ln=False, dxo_p=None):
         dy1 = ops.matmul_nn(dvproj, p["win"][2 * E:])
     else:
         return dx_res, None, g
-    if train_ffn_ln:
-        dx_in, dg_, db_ = ops.layernorm_bwd(dy1, x, s["st1"], p["ln1w"], dx_add=dx_res, want_wgrad=True)
-        g["ln1w"], g["ln1b"] = dg_, db_
-        return dx_in, None, g
+    if "ln1w" in want or "ln1b" in want:
+        r_ = ops.layernorm_bwd(dy1, x, s["st1"], p["ln1w"], dx_add=dx_res, want_wgrad=True, planes=pp)
+        g["ln1w"], g["ln1b"] = [("add", r_[1])], [("add", r_[2])]
+        return r_[0], (r_[3] if pp else None), g
     if pp:   # the block below consumes dx_in as the A operand of its d FFN-2 GEMM
         dx_in, dx_in_p = ops.layernorm_bwd(dy1, x, s["st1"], p["ln1w"], dx_add=dx_res, planes=True)
         return dx_in, dx_in_p, g
     return ops.layernorm_bwd(dy1, x, s["st1"], p["ln1w"], dx_add=dx_res), None, g
+
+
+def ffn_ln_wgrads(p, g):
+    """Write the FFN / LayerNorm weight grads of one block from the pieces block_backward collected (x path and v path
+    summed).  Returns a dict plist key -> tensor|None (None when written into main_grad)."""
+    out = {}
+    for key, parts in g.items():
+        if key not in FFN_LN_KEYS:
+            continue
+
+        def fn(dst, acc, parts=parts):
+            for j, part in enumerate(parts):
+                a_ = acc or j > 0
+                if part[0] == "gelu":
+                    ops.matmul_tn_gelu(part[1], part[2], out=dst, accumulate=a_)
+                elif part[0] == "ln":
+                    ops.matmul_tn_ln(part[1], part[2], part[3], p["ln2w"], p["ln2b"], out=dst, accumulate=a_)
+                elif part[0] == "sum":
+                    ops.colsum(part[1], out=dst, accumulate=a_)
+                elif a_:
+                    ops.add(dst, part[1], out=dst)
+                else:
+                    ops.eltwise(4, part[1], None, out=dst)
+        out[key] = sink_grad(p[key], fn)
+    return out
 
 
 def attn_wgrads(p_mod, g, E):
@@ -380,6 +413,20 @@ class MaskClipVisionTransformer(nn.Module):
     def _trainable(self):
         return [p for p in self.parameters() if p.requires_grad]
 
+    def _check_grad_rules(self, params):
+        """Every trainable tensor handed to the encoder's backward must have a gradient rule there: a tensor without one
+        would silently never receive a gradient (AdamW skips it)."""
+        ruled = self.__dict__.get("_ruled")
+        if ruled is None:
+            ruled = {id(t) for l_ in self.layers for t in l_.plist().values()}
+            ruled |= {id(t) for t in (self.ln0.weight, self.ln0.bias, self.ln1.weight, self.ln1.bias, self.cls_token,
+                                      self.pos_embed, self.patch_embed.projection.weight, self.proj.weight)}
+            self.__dict__["_ruled"] = ruled
+        bad = [n for n, t in self.named_parameters() if t.requires_grad and id(t) not in ruled and
+               any(t is q for q in params)]
+        if bad:
+            raise NotImplementedError(f"MaskClipVisionTransformer (HIP): no gradient rule for trainable {bad}")
+
     def _pos_resize_matrix(self, hw):
         """R [hw0*hw1, ph*pw] with resize_pos_embed(pos)[patches] == R @ pos[patches] (cached per target grid/device)."""
         Pz = self.patch_size
@@ -446,6 +493,8 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
     x0, st0 = ops.layernorm_fwd(x, m.ln0.weight, m.ln0.bias, m.eps)
     if saved is not None:
         saved["x_pre"], saved["st0"] = x, st0
+        if m.patch_embed.projection.weight.requires_grad:
+            saved["img"] = img     # B operand of the patch-embedding weight gradient
         saved["layers"] = []
         saved["dims"] = (B, T, NP, hp, wp)
     x = x0
@@ -475,6 +524,8 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
     emb, inv = ops.l2norm_fwd(pe, 0.0)
     if saved is not None:
         saved.update(v_last=v_last, stv=stv, emb=emb, inv=inv)
+        if m.proj.weight.requires_grad:
+            saved["vtok"] = vtok   # B operand of the proj weight gradient
     if L in m.out_indices:
         feats.append(emb.view(B, NP, -1))
     glob = None
@@ -485,6 +536,14 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         gp = ops.linear(c, wproj)
         glob, _ = ops.l2norm_fwd(gp, 0.0)
     return tuple(feats) + (glob,)
+
+
+def _sink_vectors(grads, pairs):
+    """LayerNorm weight / bias gradients computed by layernorm_bwd(want_wgrad=True) into their sinks."""
+    for prm, t in pairs:
+        if prm.requires_grad:
+            grads[id(prm)] = sink_grad(prm, lambda dst, acc, t=t: ops.add(dst, t, out=dst) if acc
+                                       else ops.eltwise(4, t, None, out=dst))
 
 
 class _PosResizeFn(torch.autograd.Function):
@@ -520,6 +579,7 @@ class _EncoderFn(torch.autograd.Function):
         ctx.pos_is_input = pos_in is not None
         ctx.n_feats = len(outs) - 1
         ctx.params = params
+        m._check_grad_rules(params)
         gradsync.expect(params)
         if outs[-1] is not None:
             ctx.mark_non_differentiable(outs[-1])  # the global embedding is a side output (unused by VLGHead)
@@ -543,14 +603,23 @@ class _EncoderFn(torch.autograd.Function):
         demb = dfeats[len(feat_layers)] if has_emb else None
         # ---- tail
         dv_last = None
+        grads = {}
         if demb is not None:
             demb = demb.contiguous().view(B * NP, -1)
             dpe = ops.l2norm_bwd(demb, s["emb"], s["inv"])
             wproj = m.proj.weight.view(m.proj.weight.shape[0], E)
             dvtok = ops.matmul_nn(dpe, wproj)
+            if m.proj.weight.requires_grad:
+                vtok = s["vtok"]
+                grads[id(m.proj.weight)] = sink_grad(m.proj.weight, lambda dst, acc: ops.matmul_tn(
+                    dpe, vtok, out=dst.view(wproj.shape), accumulate=acc))
             dvn = ops.zeros(B * T, E, device=dev)
             ops.copy2d(dvtok, 0, NP, NP * E, E, dvn, E, NP, T * E, E, B * NP, E)
-            dv_last = ops.layernorm_bwd(dvn, s["v_last"], s["stv"], m.ln1.weight)
+            if m.ln1.weight.requires_grad or m.ln1.bias.requires_grad:
+                dv_last, dg_, db_ = ops.layernorm_bwd(dvn, s["v_last"], s["stv"], m.ln1.weight, want_wgrad=True)
+                _sink_vectors(grads, ((m.ln1.weight, dg_), (m.ln1.bias, db_)))
+            else:
+                dv_last = ops.layernorm_bwd(dvn, s["v_last"], s["stv"], m.ln1.weight)
         dvs = {L - 1: dv_last}
         for j, li in enumerate(feat_layers):
             d = dfeats[j]
@@ -562,28 +631,32 @@ class _EncoderFn(torch.autograd.Function):
             dvs[li] = full if dvs.get(li) is None else ops.add(dvs[li], full)
         # ---- blocks, last to first
         dx = dxp = pend = None
-        grads = {}
         for i in range(L - 1, -1, -1):
             layer = m.layers[i]
             sv = s["layers"][i]
-            dx, dxp, g = block_backward(dx, dvs.get(i), layer.plist(), sv, m.num_heads, B, T, dxo_p=dxp)
-            # this block's weight gradients (two split-K GEMMs, their slab reductions, two column sums) are off the
-            # dependency chain: they go to the weight-gradient stream and run next to the chain's LayerNorm-backward /
-            # pack passes of the blocks below (ops.wgrad_side)
+            pl = layer.plist()
+            want = frozenset(k_ for k_ in FFN_LN_KEYS if pl[k_].requires_grad)
+            dx, dxp, g = block_backward(dx, dvs.get(i), pl, sv, m.num_heads, B, T, want=want, dxo_p=dxp)
+            # this block's weight gradients (two split-K GEMMs, their slab reductions, two column sums; with a trained FFN
+            # two more GEMM families on B-operand producers) are off the dependency chain: they go to the weight-gradient
+            # stream and run next to the chain's LayerNorm-backward / pack passes of the blocks below (ops.wgrad_side)
             used = [t_ for pair in g["wout_parts"] for t_ in pair] + [t_ for k_ in ("in_full", "in_v") for t_ in g.get(k_, ())]
+            used += [t_ for k_ in want for part in g.get(k_, ()) for t_ in part[1:]]
             with ops.wgrad_side(*used):
                 wg = attn_wgrads(layer, g, E)
+                fg = ffn_ln_wgrads(pl, g) if want else {}
             a = layer.attn.attn
             grads[id(a.in_proj_weight)], grads[id(a.in_proj_bias)] = wg["win"], wg["bin"]
             grads[id(a.out_proj.weight)], grads[id(a.out_proj.bias)] = wg["wout"], wg["bout"]
+            for k_, v_ in fg.items():
+                grads[id(pl[k_])] = v_
             s["layers"][i] = None  # free this block's activations
             # this block's attention gradients are complete for this graph ONE BLOCK LATER (when its side-stream work has
             # had a block's time to finish): then their all-reduce bucket may go (train.py)
             if pend is not None:
                 ops.wgrad_join(pend[0])
                 gradsync.ready(pend[1])
-            pend = (ops.wgrad_event(), [q for q in (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias)
-                                        if any(q is r_ for r_ in ctx.params)])
+            pend = (ops.wgrad_event(), [q for q in layer.parameters() if any(q is r_ for r_ in ctx.params)])
         ops.wgrad_join(produced=grads.values())     # every weight gradient of this graph is complete from here on
         if pend is not None:
             gradsync.ready(pend[1])
@@ -591,9 +664,23 @@ class _EncoderFn(torch.autograd.Function):
         if dx is None:
             gradsync.ready(rest)
             ctx.saved = None
-            return (None, None, None, None) + tuple(None for _ in ctx.params)
-        # ---- ln0 + pos_embed
-        dxpre = ops.layernorm_bwd(dx, s["x_pre"], s["st0"], m.ln0.weight)
+            return (None, None, None, None) + tuple(grads.get(id(p)) for p in ctx.params)
+        # ---- ln0, pos_embed, cls_token, patch embedding
+        if m.ln0.weight.requires_grad or m.ln0.bias.requires_grad:
+            dxpre, dg_, db_ = ops.layernorm_bwd(dx, s["x_pre"], s["st0"], m.ln0.weight, want_wgrad=True)
+            _sink_vectors(grads, ((m.ln0.weight, dg_), (m.ln0.bias, db_)))
+        else:
+            dxpre = ops.layernorm_bwd(dx, s["x_pre"], s["st0"], m.ln0.weight)
+        if m.cls_token.requires_grad:   # x[b*T] = cls + pos[0]: the batch sum of the class-token rows
+            grads[id(m.cls_token)] = sink_grad(m.cls_token, lambda dst, acc: ops.colsum(
+                dxpre.view(B, T * E), out=dst.view(-1), accumulate=acc, C_=E, ld=T * E))
+        wpe = m.patch_embed.projection.weight
+        if wpe.requires_grad:           # patch tokens (rows b*T + 1 + p) against the image's patches
+            dtok = ops.empty(B * NP, E, device=dev)
+            ops.copy2d(dxpre, E, NP, T * E, E, dtok, 0, NP, NP * E, E, B * NP, E)
+            img = s["img"]
+            grads[id(wpe)] = sink_grad(wpe, lambda dst, acc: ops.matmul_tn_patch(
+                dtok, img, m.patch_size, out=dst.view(E, -1), accumulate=acc))
         def pos_fn(dst, acc):
             # sum over the batch: rows b*T + t -> t
             ops.copy2d(dxpre, 0, B * T, 0, E, dst.view(-1), 0, T, 0, E, T, E, accumulate=acc)

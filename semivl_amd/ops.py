@@ -15,6 +15,7 @@ from . import lib as L
 
 A_KC, A_MC, A_CONV, A_PATCH = 0, 1, 2, 3
 B_KC, B_NC, B_CONVW = 0, 1, 2
+B_NC_GELU, B_NC_LN, B_PATCHT = 3, 4, 5   # B-operand producers of the weight gradients (A = A_MC)
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_MUL_DGELU, ACT_MUL_DRELU = 0, 1, 2, 3, 4
 OUT_STRIDED, OUT_CONVT2X, OUT_PATCH = 0, 1, 2
 
@@ -119,8 +120,10 @@ EMU_H2_CONVFWD = True
 def gemm(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batch=1, batch_inner=1, ksplit=0,
          c_bso=0, c_bsi=0, alpha=1.0, bias=None, bias_mod=0, act=ACT_NONE, resid=None, r_off=0, ldr_m=None, ldr_n=1,
          r_bso=0, r_bsi=0, accumulate=False, out_mode=OUT_STRIDED, conv=None, ct=(0, 0, 0), preact=None, w_planes=None,
-         emu_h2=True):
+         emu_h2=True, b_aux=None):
     d = L.GemmDesc()
+    if b_aux is not None:   # B_NC_LN: (row statistics, gamma, beta)
+        d.b_stats, d.b_gamma, d.b_beta = (_p(t) for t in b_aux)
     d.conv_w_planes = _p(w_planes)
     d.a_mode, d.b_mode, d.M, d.N, d.K = a_mode, b_mode, M, N, K
     d.batch, d.batch_inner, d.ksplit = batch, batch_inner, ksplit
@@ -630,6 +633,47 @@ def matmul_tn(a, b, out=None, accumulate=False):
     gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), slabs, batch=s, ksplit=ks, c_bso=M * N)
     reduce_slabs(out, slabs, accumulate)
     return out
+
+
+def _matmul_tn_prod(a, N, b_op, b_mode, out, accumulate, conv=None, b_aux=None):
+    """out[M,N] = a[K,M]^T @ f(B)[K,N] with a B-operand producer (the split-K plan of matmul_tn)."""
+    K, M = a.shape
+    assert a.stride(1) == 1
+    if out is None:
+        out = empty(M, N, device=a.device)
+        accumulate = False
+    assert out.is_contiguous() and out.numel() == M * N
+    s, ks = _ksplit_plan(M, N, K, dense=True)
+    if s == 1:
+        gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, out, accumulate=accumulate, conv=conv, b_aux=b_aux)
+        return out
+    slabs = empty(s, M, N, device=a.device)
+    gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, slabs, batch=s, ksplit=ks, c_bso=M * N, conv=conv, b_aux=b_aux)
+    reduce_slabs(out, slabs, accumulate)
+    return out
+
+
+def matmul_tn_gelu(a, h_pre, out=None, accumulate=False):
+    """out = a^T @ gelu(h_pre): the FFN-2 weight gradient from the saved pre-activation (gelu recomputed while staging)."""
+    assert h_pre.shape[0] == a.shape[0] and h_pre.stride(1) == 1
+    return _matmul_tn_prod(a, h_pre.shape[1], Op(h_pre, h_pre.stride(0)), B_NC_GELU, out, accumulate)
+
+
+def matmul_tn_ln(a, x, stats, gamma, beta, out=None, accumulate=False):
+    """out = a^T @ LN(x): the FFN-1 weight gradient from the LayerNorm input and its saved statistics."""
+    assert x.shape[0] == a.shape[0] and x.stride(1) == 1 and stats.is_contiguous()
+    return _matmul_tn_prod(a, x.shape[1], Op(x, x.stride(0)), B_NC_LN, out, accumulate,
+                           b_aux=(stats, gamma.contiguous(), beta.contiguous()))
+
+
+def matmul_tn_patch(a, img, patch, out=None, accumulate=False):
+    """out[M, C*P*P] = a[imgs*np, M]^T @ patches(img): the patch-embedding weight gradient (token rows of `a` in
+    (image, patch row, patch col) order; bottom / right zero fill of a ragged grid)."""
+    img = img.contiguous()
+    Bn, Cin, H, W = img.shape
+    g = conv_geom(H, W, Cin, patch, patch, patch=patch)
+    assert a.shape[0] == Bn * ((H + patch - 1) // patch) * ((W + patch - 1) // patch)
+    return _matmul_tn_prod(a, Cin * patch * patch, Op(img, 0), B_PATCHT, out, accumulate, conv=g)
 
 
 def reduce_slabs(out, slabs, accumulate=False):
