@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -385,6 +385,32 @@ int svl_semivl_loss(const double* sums, double numel_u, float lam, const double*
 /* out[b, c, p] = softmax over classes c of NCHW logits (probability accumulation of the sliding-window eval modes,
  * supervised.py:61,113). */
 int svl_softmax_planes_f32(const float* logits, int B, int N, int64_t HW, float* out, svl_stream_t stream);
+
+/* OHEM supervised criterion (third_party/unimatch/util/ohem.py: ProbOhemCrossEntropy2d, selected by cfg['criterion'] =
+ * 'OHEM', semivl.py:142-149,267), one rank's batch, no host synchronisation.  The criterion relabels the target and then
+ * runs the plain cross entropy (svl_ce_fused_f32 / svl_ce_up_fused_f32 on the relabelled map, its count as normaliser):
+ *   svl_target_prob_f32     prob [B, HW] = softmax over classes of logits [B, N, HW] at the target class (svl_ce_fused_f32's
+ *                           max-subtracted arithmetic); 1.0 where target == 255.  Targets are in [0, N) or 255;
+ *   svl_target_prob_up_f32  the same on bilinear(logits [B, N, h, w] -> [H, W]) evaluated in the kernel (svl_ce_up_fused_f32's
+ *                           index math, tiling and base-2 arithmetic; geometry: svl_ce_up_num_blocks > 0); prob [B, H, W];
+ *   svl_ohem_threshold_f32  threshold[0] (device float) = the effective threshold of ohem.py:39-52 over prob [n]
+ *                           (n <= 2^31 - 1, 16-byte aligned, values in [0, 1]): with v = the k-th smallest prob (exact radix
+ *                           select over the fp32 bit patterns, bit-identical to torch.kthvalue; k = min(n, min_kept) from the
+ *                           host) it is max(v, thresh) when num_valid > 0 and 0 < min_kept <= num_valid, else +inf (keep every
+ *                           valid pixel: min_kept > num_valid, min_kept == 0, or nothing valid).  num_valid: device int64, the
+ *                           count svl_count_valid_i64 produces for the target.  ws: svl_ohem_ws_bytes(n) bytes of device
+ *                           memory (no initialisation needed); deterministic;
+ *   svl_ohem_relabel_i64    out[i] = target[i] where target[i] != 255 and prob[i] <= threshold[0], else 255;
+ *                           count (device int64, may be NULL) += the number of kept pixels. */
+int svl_target_prob_f32(const float* logits, int B, int N, int64_t HW, const int64_t* target, float* prob,
+                        svl_stream_t stream);
+int svl_target_prob_up_f32(const float* logits, int B, int N, int h, int w, int H, int W, int align_corners,
+                           const int64_t* target, float* prob, svl_stream_t stream);
+int64_t svl_ohem_ws_bytes(int64_t n);
+int svl_ohem_threshold_f32(const float* prob, int64_t n, int64_t k, const int64_t* num_valid, int64_t min_kept,
+                           float thresh, void* ws, float* threshold, svl_stream_t stream);
+int svl_ohem_relabel_i64(const int64_t* target, const float* prob, int64_t n, const float* threshold, int64_t* out,
+                         int64_t* count, svl_stream_t stream);
 
 /* counts-only pre-pass so the normalisers of semivl.py:38/57 exist before the fused pass:
  * counts[0] += #(map != 255) over [n] */

@@ -168,6 +168,60 @@ __global__ __launch_bounds__(256) void softmax_max_up_kernel(const UpP p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// OHEM's target-class probability of the resized logits (ohem.py:36-45): p = softmax(x)[target], 1.0 where target == 255.
+// Staged in base 2 and reduced with up_online in class order exactly like ce_up_kernel: p = exp2(x_t - lse) is the number
+// ce_up_kernel's gradient sees for the target class (the same interpolated value -- the same cell read through the same
+// up_interp -- and the same lse).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void target_prob_up_kernel(const UpP p, float* __restrict__ prob) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];   // [N][CSTR]
+  __shared__ int ry0[RMAX], ry1[RMAX], cx0[RMAX], cx1[RMAX];
+  __shared__ float rl0[RMAX], rl1[RMAX], cl0[RMAX], cl1[RMAX];
+  const int tid = threadIdx.x;
+  const int per = p.ncy * p.ncx;
+  const int b = blockIdx.x / per, rem = blockIdx.x - b * per;
+  const int ty = rem / p.ncx, tx = rem - ty * p.ncx;
+  const float sh = up_scale(p.h, p.H, p.align), sw = up_scale(p.w, p.W, p.align);
+  int c0y, c1y, s0y, nsy, r0y, nry, c0x, c1x, s0x, nsx, r0x, nrx;
+  up_axis<false>(ty, p.h, p.H, sh, p.align, c0y, c1y, s0y, nsy, r0y, nry);
+  up_axis<false>(tx, p.w, p.W, sw, p.align, c0x, c1x, s0x, nsx, r0x, nrx);
+  if (tid < nry) up_src(r0y + tid, sh, p.h, p.align, ry0[tid], ry1[tid], rl0[tid], rl1[tid]);
+  else if (tid >= 64 && tid < 64 + nrx) up_src(r0x + tid - 64, sw, p.w, p.align, cx0[tid - 64], cx1[tid - 64], cl0[tid - 64], cl1[tid - 64]);
+  {
+    const int cell = tid & 127, cl = tid >> 7;
+    if (cell < (nsy + 1) * (nsx + 1)) {
+      const int cr = cell / (nsx + 1), cc = cell - cr * (nsx + 1);
+      const float* g = p.logits + (long)b * p.N * p.h * p.w + (long)imin_(s0y + cr, p.h - 1) * p.w + imin_(s0x + cc, p.w - 1);
+      float* d = tile + cr * LR + cc;
+      const long hw = (long)p.h * p.w;
+      for (int c = cl; c < p.N; c += 2) d[c * CSTR] = g[c * hw] * LOG2E;
+    }
+  }
+  __syncthreads();
+  const int npx = nry * nrx;
+  for (int px = tid; px < npx; px += 256) {
+    const int r = px / nrx, q = px - r * nrx;
+    const int y0 = ry0[r], x0 = cx0[q];
+    if (y0 < c0y || y0 >= c1y || x0 < c0x || x0 >= c1x) continue;   // (owned by a neighbour)
+    const long o = (long)b * p.H * p.W + (long)(r0y + r) * p.W + (r0x + q);
+    const long t = p.target[o];
+    float pr = 1.f;
+    if (t != 255) {
+      Taps k;
+      k.o00 = (y0 - s0y) * LR + (x0 - s0x);
+      k.o10 = (ry1[r] - s0y) * LR + (x0 - s0x);
+      k.ly0 = rl0[r]; k.ly1 = rl1[r]; k.lx0 = cl0[q]; k.lx1 = cl1[q];
+      float m = -INFINITY, s = 0.f;
+      for (int c = 0; c < p.N; ++c) up_online(up_interp(tile + c * CSTR, k), m, s);
+      const float lse = m + log2f(s);
+      // (a label outside [0, N) reads no logit and is never a hard pixel; the reference's indexing would fail there)
+      pr = (t >= 0 && t < p.N) ? __builtin_amdgcn_exp2f(up_interp(tile + (int)t * CSTR, k) - lse) : 1.f;
+    }
+    prob[o] = pr;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Cross entropy (+ confidence weighting + guidance term) forward and backward on the resized logits; the gradient
 // arrives at the LOW resolution.  partials[block] = { sum w_t*ce_t, sum ce_m, sum conf*valid, #valid } like ce_fused_kernel.
 // ------------------------------------------------------------------------------------------------
@@ -465,5 +519,26 @@ extern "C" int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t stream)
   hipLaunchKernelGGL(ce_up_kernel, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
                      (hipStream_t)stream, p);
   SVL_LAUNCH_CHECK("svl_ce_up_fused_f32");
+  return SVL_OK;
+}
+
+extern "C" int svl_target_prob_up_f32(const float* logits, int B, int N, int h, int w, int H, int W, int align_corners,
+                                      const int64_t* target, float* prob, svl_stream_t stream) {
+  SVL_CHECK_ARG(logits && target && prob && B > 0, "svl_target_prob_up_f32: bad args");
+  SVL_CHECK_ARG(up_ok(N, h, w, H, W, align_corners),
+                "svl_target_prob_up_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_num_blocks < 0)", N, h, w, H, W);
+  UpP p = {};
+  p.logits = logits; p.B = B; p.N = N; p.h = h; p.w = w; p.H = H; p.W = W; p.align = align_corners != 0;
+  p.target = target;
+  p.ncy = (h + TC - 1) / TC; p.ncx = (w + TC - 1) / TC;
+  const size_t lds = (size_t)N * CSTR * sizeof(float);
+  static std::atomic<uint64_t> mask{0};
+  {
+    const int rc = lds_attr_once(mask, target_prob_up_kernel, 96 * 1024);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(target_prob_up_kernel, dim3((unsigned)((long)B * p.ncy * p.ncx)), dim3(256), lds, (hipStream_t)stream,
+                     p, prob);
+  SVL_LAUNCH_CHECK("svl_target_prob_up_f32");
   return SVL_OK;
 }

@@ -116,6 +116,11 @@ SIGNATURES = {
     "svl_bernoulli_f32": (_I, [_P, _L, _F, C.c_uint64, C.c_uint64, _P]),
     "svl_softmax_planes_f32": (_I, [_P, _I, _I, _L, _P, _P]),
     "svl_count_valid_i64": (_I, [_P, _L, _P, _P]),
+    "svl_target_prob_f32": (_I, [_P, _I, _I, _L, _P, _P, _P]),
+    "svl_target_prob_up_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "svl_ohem_ws_bytes": (_L, [_L]),
+    "svl_ohem_threshold_f32": (_I, [_P, _L, _L, _P, _L, _F, _P, _P, _P]),
+    "svl_ohem_relabel_i64": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "svl_maskclip_labels": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "svl_concept_max_f32": (_I, [_P, _I, _I, _L, _P, _I, _P, _P]),
     "svl_iou_hist_i64": (_I, [_P, _P, _L, _I, _I, _P, _P]),

@@ -1426,6 +1426,65 @@ def ce_up_fused(logits, H, W, align, target, use_ignore_t, conf=None, ign=None, 
     return sums_out
 
 
+def target_prob(logits, target, up=None):
+    """OHEM's p [B, H, W]: softmax over classes at the target class, 1.0 where target == 255.  `up` = (H, W, align_corners):
+    `logits` [B, N, h, w] are resized inside the kernel (svl_target_prob_up_f32); else they are the full-resolution
+    [B, N, H, W] map (svl_target_prob_f32)."""
+    Bn, N = logits.shape[:2]
+    prob = empty(*target.shape, device=logits.device)
+    lib = L.load()
+    if up is not None:
+        H, W, align = up
+        h, w = logits.shape[2:]
+        assert tuple(target.shape) == (Bn, H, W), (tuple(target.shape), (Bn, H, W))
+        L.check(lib.svl_target_prob_up_f32(_p(logits), Bn, N, h, w, H, W, 1 if align else 0, _p(target), _p(prob), _st()),
+                "svl_target_prob_up_f32")
+    else:
+        HW = logits[0, 0].numel()
+        assert target.numel() == Bn * HW, (tuple(target.shape), tuple(logits.shape))
+        L.check(lib.svl_target_prob_f32(_p(logits), Bn, N, HW, _p(target), _p(prob), _st()), "svl_target_prob_f32")
+    return prob
+
+
+def ohem_threshold(prob, k, num_valid, min_kept, thresh):
+    """Device float[1]: ohem.py's effective threshold over `prob` (fp32, contiguous, values in [0, 1]) -- max(k-th smallest,
+    thresh) when 0 < min_kept <= num_valid (device int64[1]), else +inf.  k = min(prob.numel(), min_kept)."""
+    n = prob.numel()
+    lib = L.load()
+    ws = empty(lib.svl_ohem_ws_bytes(n), dtype=torch.uint8, device=prob.device)
+    out = empty(1, device=prob.device)
+    L.check(lib.svl_ohem_threshold_f32(_p(prob), n, int(k), _p(num_valid), int(min_kept), float(thresh), _p(ws), _p(out),
+                                       _st()), "svl_ohem_threshold_f32")
+    return out
+
+
+def kth_smallest(x, k):
+    """torch.kthvalue(x.flatten(), k).values for fp32 values in [0, 1], as a device float[1] (the radix select of
+    svl_ohem_threshold_f32 with thresh -inf)."""
+    nv = torch.full((1,), x.numel(), dtype=torch.int64, device=x.device)
+    return ohem_threshold(x.contiguous(), k, nv, k, -math.inf)
+
+
+def ohem_target(logits, target, thresh=0.7, min_kept=256, up=None, counts_out=None):
+    """ProbOhemCrossEntropy2d's relabelling (third_party/unimatch/util/ohem.py:30-55): an int64 map equal to `target` where
+    the pixel is labelled and its target-class probability is <= the effective threshold, 255 elsewhere.  `logits`: the
+    full-resolution [B, N, H, W] map, or with `up` = (H, W, align_corners) the head-resolution [B, N, h, w] one (resized
+    inside the kernel).  `counts_out` (int64[1] view, pre-zeroed): += the number of kept pixels.  No host sync."""
+    target = target.contiguous()
+    n = target.numel()
+    lib = L.load()
+    e0 = _prof_begin()
+    num_valid = zeros(1, dtype=torch.int64, device=target.device)
+    L.check(lib.svl_count_valid_i64(_p(target), n, _p(num_valid), _st()), "svl_count_valid_i64")
+    prob = target_prob(logits.contiguous(), target, up)
+    thr = ohem_threshold(prob, min(n, int(min_kept)), num_valid, int(min_kept), thresh)
+    out = empty(*target.shape, dtype=torch.int64, device=target.device)
+    L.check(lib.svl_ohem_relabel_i64(_p(target), _p(prob), n, _p(thr), _p(out), _p(counts_out), _st()),
+            "svl_ohem_relabel_i64")
+    _prof_end("ohem_target", e0, float(n) * 48.0, (n,))
+    return out
+
+
 def maskclip_labels(dense, H, W, scale, thresh, ign=None):
     Bn, N, h, w = dense.shape
     out = empty(Bn, H, W, dtype=torch.int64, device=dense.device)

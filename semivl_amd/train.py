@@ -68,6 +68,46 @@ def compute_mc_loss(pred, mask, ign, mcc_loss_reduce="mean_all", criterion_mc=No
     return l_mc
 
 
+class ProbOhemCrossEntropy2d(torch.nn.Module):
+    """third_party/unimatch/util/ohem.py's criterion (the reference's cfg['criterion'] = 'OHEM', semivl.py:142-149) with
+    its constructor signature.  API-compatibility helper for reference-style scripts: the hard pixels are selected on the
+    device by the OHEM kernels (ops.ohem_target, no host sync), then the mean cross entropy over the kept pixels is taken
+    like the reference's inner nn.CrossEntropyLoss(ignore_index).  `semivl_train_step` reads the same configuration and
+    relabels through the same kernels before its fused cross entropy.
+    Supported: ignore_index 255 (the CE kernels fix it), reduction 'mean', use_weight False; `down_ratio` is accepted and
+    unused, as in the reference."""
+
+    def __init__(self, ignore_index, reduction="mean", thresh=0.7, min_kept=256, down_ratio=1, use_weight=False):
+        super().__init__()
+        if ignore_index != 255:
+            raise ValueError(f"ProbOhemCrossEntropy2d: ignore_index={ignore_index!r}; the cross-entropy kernels fix it at 255")
+        if reduction != "mean":
+            raise NotImplementedError(f"ProbOhemCrossEntropy2d: reduction={reduction!r}; only 'mean' is supported")
+        if use_weight:
+            raise NotImplementedError("ProbOhemCrossEntropy2d: use_weight=True (the 19 fixed class weights) is not supported")
+        self.ignore_index = ignore_index
+        self.thresh = float(thresh)
+        self.min_kept = int(min_kept)
+        self.down_ratio = down_ratio
+
+    def relabel(self, pred, target, up=None, counts_out=None):
+        """The relabelled int64 target (255 outside the kept pixels); `up` as in ops.ohem_target."""
+        return ops.ohem_target(pred.detach(), target, self.thresh, self.min_kept, up=up, counts_out=counts_out)
+
+    def forward(self, pred, target):
+        return torch.nn.functional.cross_entropy(pred, self.relabel(pred, target), ignore_index=self.ignore_index)
+
+
+def supervised_criterion(cfg):
+    """cfg['criterion'] (semivl.py:142-149) -> None for the plain cross entropy (missing, 'CELoss', and -- unchanged --
+    every other name) or a ProbOhemCrossEntropy2d for 'OHEM', built from cfg['criterion']['kwargs'] as given (ohem.py's
+    defaults fill the rest, like the reference)."""
+    crit = cfg.get("criterion")
+    if not isinstance(crit, dict) or crit.get("name") != "OHEM":
+        return None
+    return ProbOhemCrossEntropy2d(**(crit.get("kwargs") or {}))
+
+
 def _cat2(a, b):
     """torch.cat((a, b)) along dim 0 with the library's copy kernel."""
     out = ops.empty(a.shape[0] + b.shape[0], *a.shape[1:], device=a.device)
@@ -145,7 +185,7 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
 
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
                        return_aux=False):
-    """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) / CELoss; conf_mode 'pixelwise' /
+    """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
     returned `losses` is a device float[8] (LOSS_NAMES order).
     """
@@ -155,6 +195,7 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         raise ValueError(conf_mode)                      # train_utils.py:47-48
     if mcc_reduce not in ("mean_all", "mean_valid", "mean"):
         raise ValueError(mcc_reduce)                     # semivl.py:161-162
+    ohem = supervised_criterion(cfg)                     # semivl.py:142-149 (raises on what the kernels cannot do)
     pixelavg = conf_mode == "pixelavg"
     whole_map = conf_mode in ("pixelavg", "pixelratio")  # both weight the WHOLE CE map, not the confident valid pixels
     lam_cfg = cfg.get("maskclip_consistency_lambda", [0.1, 0])
@@ -272,8 +313,12 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     mc1, mc2 = cutmix_mask(mclip, mclip_other, mix1), cutmix_mask(mclip, mclip_other, mix2)
     # normalisers -> per-branch gradient scales, on the device
     counts = ops.zeros(4, dtype=torch.int64, device=dev)
+    mask_x_ohem = None
+    if ohem is not None:   # semivl.py:267 with criterion_l = OHEM: the plain CE on the relabelled map, its count as normaliser
+        mask_x = mask_x_ohem = ohem.relabel(pred_x, mask_x, up=up, counts_out=counts[0:1])
     for i, m_ in enumerate((mask_x, ig1, ig2, ign)):
-        ops.count_valid(m_, counts[i:i + 1])
+        if i > 0 or ohem is None:
+            ops.count_valid(m_, counts[i:i + 1])
     numel_u = float(ign.numel())
     gscale = ops.empty(4, 2, device=dev)
     factors = None
@@ -334,7 +379,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     if return_aux:
         aux = dict(mask_w=mask_w, mask_w_other=mask_w_other, mclip=mclip, mclip_other=mclip_other, conf_w=conf_w,
                    pred_x=full_res(pred_x.detach()), pred_s1=full_res(pred_s1.detach()), pred_w=full_res(pred_w.detach()),
-                   pred_w_other=full_res(pred_w_other), dl4=dl4, dls=dls, upsample_in_loss=up is not None)
+                   pred_w_other=full_res(pred_w_other), dl4=dl4, dls=dls, upsample_in_loss=up is not None,
+                   mask_x_ohem=mask_x_ohem)
         return losses, aux
     return losses
 
