@@ -105,6 +105,9 @@ enum {
   SVL_OUT_STRIDED = 0, /* C + zo*bs_outer + zi*bs_inner + m*ld_m + n*ld_n                              */
   SVL_OUT_CONVT2X = 1, /* ConvTranspose2d k2 s2: m=(img,h,w), n=(a,b,co) -> pixel (img,2h+a,2w+b), co  */
   SVL_OUT_PATCH = 2    /* patch tokens: row m=(img,p) -> img*(P+1)+1+p ; resid row = 1+p (pos_embed)   */
+  /* SVL_OUT_CONVT2X / SVL_OUT_PATCH: batch == 1 (SVL_ERR_INVALID_ARG otherwise: the batch strides address the strided
+   * output only); `resid` with SVL_OUT_CONVT2X is refused (SVL_ERR_UNSUPPORTED: no residual addressing is defined for it).
+   * K == 0 is valid for the dense modes: the result is the epilogue of a zero sum (so is an empty split-K range). */
 };
 
 typedef struct svl_operand {

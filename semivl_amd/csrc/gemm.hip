@@ -1794,6 +1794,12 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     SVL_CHECK_ARG(d->ct_H > 0 && d->ct_W > 0 && d->ct_Cout > 0 && d->N == 4 * d->ct_Cout,
                   "svl_gemm_f32: bad convT geometry");
   if (d->out_mode == SVL_OUT_PATCH) SVL_CHECK_ARG(d->ct_H > 0, "svl_gemm_f32: bad patch-token geometry");
+  // the scatter stores have one destination per (m, n) and no residual addressing of their own
+  SVL_CHECK_ARG(d->out_mode == SVL_OUT_STRIDED || d->batch == 1, "svl_gemm_f32: batched output needs SVL_OUT_STRIDED");
+  if (d->out_mode == SVL_OUT_CONVT2X && d->resid != nullptr) {
+    svl_set_error("svl_gemm_f32: resid is not supported with SVL_OUT_CONVT2X");
+    return SVL_ERR_UNSUPPORTED;
+  }
 
   const int am = d->a_mode, bm = d->b_mode;
   int emu_mode = g_emu_mode.load(std::memory_order_relaxed);
