@@ -494,7 +494,10 @@ int svl_bernoulli_f32(float* p, int64_t n, float keep_prob, uint64_t seed, uint6
 int svl_affine_planes_f32(const float* x, int64_t planes, int C, int64_t HW, const float* k4, float* y, svl_stream_t stream);
 /* Strided row copy / gather / scatter / broadcast of `rows` rows of C floats:
  *   dst[(i / dgrp)*dst_go + (i % dgrp)*dst_ld + c] (=|+=) src[(i / sgrp)*src_go + (i % sgrp)*src_ld + c]
- * (token slicing x[:, 1:], cls-row scatter, torch.cat into channel slices, batch broadcast, strided grad adds). */
+ * (token slicing x[:, 1:], cls-row scatter, torch.cat into channel slices, batch broadcast, strided grad adds).
+ * Destination rows of one call must be distinct: each element is one plain load / store (no atomics), so two rows that
+ * land on the same destination leave one of them (plain copy) or lose addends (accumulate).  A sum over rows takes one
+ * call per addend (the pos_embed gradient: one call per image). */
 int svl_copy2d_f32(const float* src, int64_t sgrp, int64_t src_go, int64_t src_ld, float* dst, int64_t dgrp,
                    int64_t dst_go, int64_t dst_ld, int64_t rows, int C, int accumulate, svl_stream_t stream);
 /* dst (contiguous [n0, n1, n2, n3]) = src read through the element strides (s0 .. s3): the weight-sized permutes between the

@@ -85,11 +85,14 @@ def zeros(*shape, dtype=torch.float32, device=None):
     return t
 
 
-def permute4(src, shape, strides):
+def permute4(src, shape, strides, out=None):
     """A contiguous fp32 tensor of `shape` (4 dims) read from `src` through the element `strides` (svl_permute4_f32): the
-    weight-sized permutes between parameter layouts and kernel packs without an ATen copy kernel."""
+    weight-sized permutes between parameter layouts and kernel packs without an ATen copy kernel.  `out`: a contiguous
+    fp32 tensor of `shape` to write instead of a fresh one."""
     assert src.dtype == torch.float32 and len(shape) == 4 and len(strides) == 4
-    out = torch.empty(*shape, dtype=torch.float32, device=src.device)
+    if out is None:
+        out = torch.empty(*shape, dtype=torch.float32, device=src.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == tuple(shape) and out.is_contiguous()
     if not src.is_cuda:
         return out.copy_(torch.as_strided(src, shape, strides, src.storage_offset()))
     L.check(L.load().svl_permute4_f32(_p(src), _p(out), *[int(v) for v in shape], *[int(v) for v in strides], _st()),
@@ -563,7 +566,11 @@ def linear(x, W, bias=None, act=ACT_NONE, resid=None, out=None, accumulate=False
 
 
 def copy2d(src, s_off, sgrp, src_go, src_ld, dst, d_off, dgrp, dst_go, dst_ld, rows, Cc, accumulate=False):
-    """Strided row copy; offsets in elements."""
+    """Strided row copy; offsets in elements.  The destination rows of one call must be distinct (the kernel's += is not
+    atomic): checked from the descriptor for accumulating calls, where an overlap would lose addends."""
+    if accumulate:
+        assert dst_go != 0 or rows <= dgrp, "copy2d: accumulating rows of different groups land on one destination (dst_go 0)"
+        assert dst_ld != 0 or dgrp == 1, "copy2d: accumulating rows of one group land on one destination (dst_ld 0)"
     L.check(L.load().svl_copy2d_f32(C.c_void_p(src.data_ptr() + 4 * s_off), sgrp, src_go, src_ld,
                                     C.c_void_p(dst.data_ptr() + 4 * d_off), dgrp, dst_go, dst_ld, rows, Cc,
                                     1 if accumulate else 0, _st()), "svl_copy2d_f32")
@@ -721,11 +728,12 @@ def fill(t, v):
     return t
 
 
-def affine_planes(x, k4):
+def affine_planes(x, k4, out=None):
     """((x * k4[0][c] + k4[1][c]) - k4[2][c]) / k4[3][c] on an NCHW tensor (k4 [4, C] on the device)."""
     x = x.contiguous()
     Bn, Cc = x.shape[:2]
-    y = torch.empty_like(x)
+    y = torch.empty_like(x) if out is None else out
+    assert y.shape == x.shape and y.dtype == torch.float32 and y.is_contiguous()
     L.check(L.load().svl_affine_planes_f32(_p(x), Bn * Cc, Cc, x[0, 0].numel(), _p(k4), _p(y), _st()),
             "svl_affine_planes_f32")
     return y
@@ -1529,10 +1537,12 @@ def bernoulli(shape, keep_prob, device):
     return out
 
 
-def conf_ratio(conf, ign, thresh):
+def conf_ratio(conf, ign, thresh, out=None):
     """ratio[b] = #(conf_b >= thresh & valid) / #valid   (conf_mode 'pixelratio', train_utils.py:39-40) -> float[B]."""
     lib = L.load()
-    out = empty(conf.shape[0], device=conf.device)
+    if out is None:
+        out = empty(conf.shape[0], device=conf.device)
+    assert out.dtype == torch.float32 and out.numel() == conf.shape[0] and out.is_contiguous()
     ws = torch.empty(int(lib.svl_conf_avg_ws_doubles(conf.shape[0])), dtype=torch.float64, device=conf.device)
     L.check(lib.svl_conf_ratio_f32(_p(conf), _p(ign), conf.shape[0], conf[0].numel(), float(thresh), _p(out), _p(ws), _st()),
             "svl_conf_ratio_f32")
@@ -1547,9 +1557,11 @@ def conf_avg_factor(conf, ign, out_f64):
             "svl_conf_avg_factor")
 
 
-def softmax_planes(logits):
+def softmax_planes(logits, out=None):
     Bn, N = logits.shape[:2]
-    out = torch.empty_like(logits)
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.shape == logits.shape and out.dtype == torch.float32 and out.is_contiguous()
     L.check(L.load().svl_softmax_planes_f32(_p(logits), Bn, N, logits[0, 0].numel(), _p(out), _st()),
             "svl_softmax_planes_f32")
     return out

@@ -1,5 +1,6 @@
 """Golden vectors for the evaluation path, captured from the reference's OWN `predict` / `intersectionAndUnion`
-(build container only; needs /root/reference).  Writes tests/golden/eval_zegclip.npz."""
+(build container only; needs /root/reference).  Writes tests/golden/eval_zegclip.npz; `gen_golden_eval.py edges` writes
+tests/golden/eval_edges.npz instead: `predict` on images smaller than the crop, a fractional stride and center_crop."""
 import os
 import sys
 
@@ -13,12 +14,46 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
 
+def edges(ref_predict):
+    """The reference's `predict` with ToyModel on the geometries of tests/small_kernel_ref.py::edge_cases: per case the
+    prediction map, min(top-2 gap of `final`, EDGE_GAP_CLIP) and `final` subsampled by 4 -- or, if the reference itself
+    raises there, the exception's type name under '<key>/raises'."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import small_kernel_ref as R
+    from oracle import eval_oracle as E
+    torch.Tensor.cuda = lambda self, *a, **k: self      # the probability-averaging modes call .cuda() on fresh tensors
+    model = E.ToyModel(R.EDGE_CFG["nclass"])
+    out = {}
+    for key, mode, cfg, (h, w), mask_hw in R.edge_cases():
+        img = R.edge_image(h, w)
+        out[f"{key}/img_checksum"] = np.array([img.double().sum().item(), img.double().abs().sum().item()])
+        mask = torch.zeros(2, *mask_hw, dtype=torch.long)
+        try:
+            with torch.no_grad():
+                pred, final = ref_predict(model, img, mask, mode, cfg, return_logits=True)
+        except Exception as e:  # noqa: BLE001 -- recorded: the product must raise there too
+            out[f"{key}/raises"] = np.array(type(e).__name__)
+            print(f"{key}: the reference raises {type(e).__name__}: {e}")
+            continue
+        t2 = final.topk(2, dim=1).values if final.shape[1] > 1 else None
+        gap = (t2[:, 0] - t2[:, 1]).clamp(max=R.EDGE_GAP_CLIP)
+        out[f"{key}/pred"] = pred.numpy().astype(np.uint8)
+        out[f"{key}/gap"] = gap.numpy().astype(np.float32)
+        out[f"{key}/final_s4"] = final[:, :, ::4, ::4].numpy()
+        print(f"{key}: final {tuple(final.shape)}, near-ties {(gap < 1e-5).sum().item()}")
+    path = os.path.join(HERE, "eval_edges.npz")
+    np.savez_compressed(path, **out)
+    print("wrote eval_edges.npz", os.path.getsize(path) / 1e6, "MB")
+
+
 def main():
     os.chdir(REF)
     sys.path.insert(0, REF)
     import _ref_shim
     _ref_shim.install()
     from third_party.unimatch.supervised import predict as ref_predict
+    if sys.argv[1:] == ["edges"]:
+        return edges(ref_predict)
     from third_party.unimatch.util.utils import intersectionAndUnion as ref_iau
     from oracle import eval_oracle as E
     K, crop, stride = 21, 512, 426
