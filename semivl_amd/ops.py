@@ -1221,15 +1221,28 @@ def conv_cout1_fwd(x, ldx, imgs, H, W, Cc, wf, KH, KW, dil, pad, bias=None, out=
     return y
 
 
-def conv_cout1_wgrad(dy, x, ldx, imgs, H, W, Cc, dil, pad, gn_in=None):
-    """Weight gradient of Conv2d(C -> 1, 3x3): returns the forward-pack layout [1, 9*C] (`gn_in` as in conv_cout1_fwd)."""
+def conv_cout1_wgrad(dy, x, ldx, imgs, H, W, Cc, dil, pad, gn_in=None, out=None):
+    """Weight gradient of Conv2d(C -> 1, 3x3): returns the forward-pack layout [1, 9*C] (`gn_in` as in conv_cout1_fwd).
+    `out`: a contiguous fp32 tensor of 9*C elements to write instead of a fresh one."""
     lib = L.load()
     nb = lib.svl_conv_cout1_wgrad_blocks(imgs, H, W)
     slabs = empty(nb, 9 * Cc, device=x.device)
     L.check(lib.svl_conv_cout1_wgrad(_p(dy), _p(x), ldx, imgs, H, W, Cc, dil, pad, _p(gn_in), _p(slabs), _st()),
             "svl_conv_cout1_wgrad")
-    out = empty(1, 9 * Cc, device=x.device)
+    if out is None:
+        out = empty(1, 9 * Cc, device=x.device)
+    assert out.is_contiguous() and out.numel() == 9 * Cc
     reduce_slabs(out, slabs)
+    return out
+
+
+def tap_gather(T, imgs, H, W, KH, KW, dil, pad, sign, out=None):
+    """out[p] = sum_tap T[p - sign * off(tap)][tap] (svl_tap_gather); T [imgs*H*W, KH*KW]; returns [imgs*H*W, 1]."""
+    assert T.is_contiguous() and T.numel() == imgs * H * W * KH * KW
+    if out is None:
+        out = empty(imgs * H * W, 1, device=T.device)
+    assert out.is_contiguous() and out.numel() == imgs * H * W
+    L.check(L.load().svl_tap_gather(_p(T), imgs, H, W, KH, KW, dil, pad, sign, _p(out), _st()), "svl_tap_gather")
     return out
 
 
@@ -1239,9 +1252,7 @@ def conv_cin1_dgrad(dy, lddy, imgs, H, W, Co, wtap, KH, KW, dil, pad):
     M = imgs * H * W
     T = empty(M, KH * KW, device=dy.device)
     gemm(A_KC, B_KC, M, KH * KW, Co, Op(dy, lddy), Op(wtap, Co), T)
-    out = empty(M, 1, device=dy.device)
-    L.check(L.load().svl_tap_gather(_p(T), imgs, H, W, KH, KW, dil, pad, 1, _p(out), _st()), "svl_tap_gather")
-    return out
+    return tap_gather(T, imgs, H, W, KH, KW, dil, pad, 1)
 
 
 def convT2x_fwd(x, ldx, imgs, H, W, Ci, wp, Co, bias, out, ldo):
@@ -1284,12 +1295,22 @@ def bilinear_nhwc_fwd(x, ldx, imgs, h, w, Cc, align, rep, H, W, y, ldy, accumula
                                            1 if accumulate else 0, _st()), "svl_bilinear_nhwc_fwd")
 
 
-def bilinear_nhwc_bwd(dy, lddy, imgs, h, w, Cc, align, rep, H, W, dx, lddx, accumulate=False):
-    if rep > 1 and Cc % 4 == 0 and lddy % 4 == 0:
+def sum_rep(src, ld, groups, rep, rows, Cc, out=None):
+    """out [groups * rows, Cc] = sum over r < rep of src[(g * rep + r) * rows + row] (rows `ld` apart; svl_sum_rep_f32).
+    `out`: a contiguous, 16-byte aligned fp32 tensor of groups * rows * Cc elements to write instead of a fresh one."""
+    if out is None:
+        out = empty(groups * rows, Cc, device=src.device)
+    assert out.is_contiguous() and out.numel() == groups * rows * Cc
+    L.check(L.load().svl_sum_rep_f32(_p(src), ld, groups, rep, rows, Cc, _p(out), _st()), "svl_sum_rep_f32")
+    return out
+
+
+def bilinear_nhwc_bwd(dy, lddy, imgs, h, w, Cc, align, rep, H, W, dx, lddx, accumulate=False, sum_first=True):
+    """`sum_first` = False keeps the class repeats inside svl_bilinear_nhwc_bwd (its own rep loop) instead of summing them first:
+    no model code passes it, it exists so that tests/test_spatial_kernels_gpu.py reaches that loop through this wrapper."""
+    if sum_first and rep > 1 and Cc % 4 == 0 and lddy % 4 == 0:
         # sum the class repeats first (one coalesced pass), then a rep = 1 backward on the per-image map
-        summed = empty(imgs * H * W, Cc, device=dy.device)
-        L.check(L.load().svl_sum_rep_f32(_p(dy), lddy, imgs, rep, H * W, Cc, _p(summed), _st()), "svl_sum_rep_f32")
-        dy, lddy, rep = summed, Cc, 1
+        dy, lddy, rep = sum_rep(dy, lddy, imgs, rep, H * W, Cc), Cc, 1
     L.check(L.load().svl_bilinear_nhwc_bwd(_p(dy), lddy, imgs, h, w, Cc, 1 if align else 0, rep, H, W, _p(dx), lddx,
                                            1 if accumulate else 0, _st()), "svl_bilinear_nhwc_bwd")
 
@@ -1303,34 +1324,41 @@ def bilinear_planes_fwd(x, h, w, align, H, W, out=None):
     return y
 
 
-def bilinear_planes_bwd(dy, h, w, align, H, W):
+def bilinear_planes_bwd(dy, h, w, align, H, W, out=None):
     planes = dy.numel() // (H * W)
-    dx = empty(*dy.shape[:-2], h, w, device=dy.device)
+    dx = empty(*dy.shape[:-2], h, w, device=dy.device) if out is None else out
+    assert dx.is_contiguous() and dx.numel() == planes * h * w
     L.check(L.load().svl_bilinear_planes_bwd(_p(dy), planes, h, w, 1 if align else 0, H, W, _p(dx), _st()),
             "svl_bilinear_planes_bwd")
     return dx
 
 
-def avgpool_cat_fwd(x, imgs, H, W, Cc, P, text, nclass):
-    """P: int (square window) or (PH, PW)."""
+def avgpool_cat_fwd(x, imgs, H, W, Cc, P, text, nclass, out=None):
+    """P: int (square window) or (PH, PW).  `out`: a contiguous fp32 tensor of the result's size to write instead."""
     PH, PW = (P, P) if isinstance(P, int) else P
     Ct = text.shape[1] if text is not None else 0
-    y = empty(imgs * (H // PH) * (W // PW), Cc + Ct, device=x.device)
+    y = empty(imgs * (H // PH) * (W // PW), Cc + Ct, device=x.device) if out is None else out
+    assert y.is_contiguous() and y.numel() == imgs * (H // PH) * (W // PW) * (Cc + Ct)
     L.check(L.load().svl_avgpool_cat_fwd(_p(x), imgs, H, W, Cc, PH, PW, _p(text), Ct, nclass, _p(y), _st()),
             "svl_avgpool_cat_fwd")
     return y
 
 
-def avgpool_cat_bwd(dy, imgs, H, W, Cc, P, Ct, nclass, add_to=None):
-    """`add_to`: an existing [imgs*H*W, Cc] gradient the pooled gradient is added to in place (returned as dx)."""
+def avgpool_cat_bwd(dy, imgs, H, W, Cc, P, Ct, nclass, add_to=None, out=None, text_out=None):
+    """`add_to`: an existing [imgs*H*W, Cc] gradient the pooled gradient is added to in place (returned as dx).  `out` (without
+    add_to) / `text_out`: contiguous fp32 tensors of imgs*H*W*Cc / nclass*Ct elements to write instead of fresh ones."""
     PH, PW = (P, P) if isinstance(P, int) else P
-    dx = empty(imgs * H * W, Cc, device=dy.device) if add_to is None else add_to
+    assert add_to is None or out is None
+    dx = (empty(imgs * H * W, Cc, device=dy.device) if out is None else out) if add_to is None else add_to
+    assert dx.is_contiguous() and dx.numel() == imgs * H * W * Cc
     lib = L.load()
     L.check(lib.svl_avgpool_cat_bwd(_p(dy), imgs, H, W, Cc, PH, PW, Ct, _p(dx), 0 if add_to is None else 1, _st()),
             "svl_avgpool_cat_bwd")
     dtext = None
     if Ct > 0:
-        dtext, part = empty(nclass, Ct, device=dy.device), empty(imgs, Ct, device=dy.device)
+        dtext = empty(nclass, Ct, device=dy.device) if text_out is None else text_out
+        assert dtext.is_contiguous() and dtext.numel() == nclass * Ct
+        part = empty(imgs, Ct, device=dy.device)
         L.check(lib.svl_avgpool_cat_bwd_text(_p(dy), imgs, (H // PH) * (W // PW), Cc, Ct, nclass, _p(part), _p(dtext), _st()),
                 "svl_avgpool_cat_bwd_text")
     return dx, dtext
@@ -1646,15 +1674,19 @@ def bn_bwd_apply(dy, x, y, C, mean, invstd, gamma, sums, count, want_dres=False,
     return (dx, dres) if want_dres else dx
 
 
-def maxpool3x3s2_fwd(x, imgs, H, W, C):
+def maxpool3x3s2_fwd(x, imgs, H, W, C, out=None, idx_out=None):
+    """`out` / `idx_out`: contiguous fp32 / uint8 tensors of imgs*Ho*Wo*C elements to write instead of fresh ones."""
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    y = empty(imgs * Ho * Wo, C, device=x.device)
-    idx = torch.empty(imgs * Ho * Wo, C, dtype=torch.uint8, device=x.device)
+    y = empty(imgs * Ho * Wo, C, device=x.device) if out is None else out
+    idx = torch.empty(imgs * Ho * Wo, C, dtype=torch.uint8, device=x.device) if idx_out is None else idx_out
+    assert y.is_contiguous() and idx.is_contiguous() and idx.dtype == torch.uint8
+    assert y.numel() == imgs * Ho * Wo * C and idx.numel() == imgs * Ho * Wo * C
     L.check(L.load().svl_maxpool3x3s2_fwd(_p(x), imgs, H, W, C, _p(y), _p(idx), _st()), "svl_maxpool3x3s2_fwd")
     return y, idx, Ho, Wo
 
 
-def maxpool3x3s2_bwd(dy, idx, imgs, H, W, C):
-    dx = empty(imgs * H * W, C, device=dy.device)
+def maxpool3x3s2_bwd(dy, idx, imgs, H, W, C, out=None):
+    dx = empty(imgs * H * W, C, device=dy.device) if out is None else out
+    assert dx.is_contiguous() and dx.numel() == imgs * H * W * C
     L.check(L.load().svl_maxpool3x3s2_bwd(_p(dy), _p(idx), imgs, H, W, C, _p(dx), _st()), "svl_maxpool3x3s2_bwd")
     return dx
