@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -172,6 +172,11 @@ typedef struct svl_gemm_desc {
   const float* b_stats;      /* SVL_B_NC_LN: [K][2] row statistics {mean, rstd} of the B source rows                     */
   const float* b_gamma;      /* SVL_B_NC_LN: [N] LayerNorm weight                                                         */
   const float* b_beta;       /* SVL_B_NC_LN: [N] LayerNorm bias                                                           */
+  const unsigned* a_amax;    /* optional, with emu_ws: one device word each, the bit pattern of the largest |x| of the WHOLE A / B */
+  const unsigned* b_amax;    /* operand this call reads (what svl_split_planes_f16x2's tensor_amax leaves for the same matrix,
+                              * unwritten since).  The dense launches and the A side (SVL_B_PATCHT: both sides) of the
+                              * producer launches then take the word instead of running their maximum pass over that operand;
+                              * every other launch ignores them.  NULL: the pass runs. */
 } svl_gemm_desc;
 
 int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream);
@@ -197,6 +202,8 @@ int svl_set_conv_tiled(int on);
  * tiled 3x3), 2 the short-K row stream (fp32 MFMA, HBM-bound), 3 an elementwise kernel (no MFMA), 4 the in-register split
  * kernel on fp16 x 2 terms (three products; svl_gemm_desc::emu_ws). */
 int svl_last_gemm_path(void);
+/* Introspection for tests: operand-maximum passes (the fp16 x 2 form's absmax kernels) this process has launched so far. */
+int64_t svl_absmax_launches(void);
 
 /* ------------------------------------------------------------------------------------------------
  * fp32-accurate GEMM with PRE-SPLIT, fragment-packed operands (the fast form of emulation mode 6; csrc/gemm_planes.hip).
@@ -256,10 +263,13 @@ int svl_split_planes_bf16x3(const float* x, int64_t ld, int64_t k_stride, int64_
  * plain fp32 MFMA chain's for K >= 48 (tests/test_ops_gpu.py::test_gemm_planes_path).  The GEMM multiplies its
  * accumulators by 2^(e_A(m) + e_B(n)) (exact).  svl_split_planes_f16x2 is the generic pack pass (arguments as
  * svl_split_planes_bf16x3); it also writes sexp[row_off + r] and, if rnorm != NULL, an upper bound of each row's L2 norm --
- * what a GEMM needs to scale a planes OUTPUT in this format (svl_pgemm_desc::a_rnorm / b_bound). */
+ * what a GEMM needs to scale a planes OUTPUT in this format (svl_pgemm_desc::a_rnorm / b_bound).  tensor_amax (optional,
+ * one device word, zeroed by the call): receives the bit pattern of the matrix's largest |x| -- the pass holds every row's
+ * maximum anyway -- in the convention of svl_gemm_desc::a_amax / b_amax (non-negative float bits, NaNs take no part). */
 int64_t svl_planes_bytes_fmt(int64_t rows, int K, int fmt);
 int svl_split_planes_f16x2(const float* x, int64_t ld, int64_t k_stride, int64_t rows, int K, void* planes,
-                           int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm, svl_stream_t stream);
+                           int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm, unsigned* tensor_amax,
+                           svl_stream_t stream);
 int svl_gemm_planes_f32(const svl_pgemm_desc* d, svl_stream_t stream);
 /* Weight gradient of a narrow (Co = 32 / 64) 3x3 / stride 1 / pad 1 convolution over NHWC activations with an optional
  * second concat source (read at image img / rep): slabs[g][co][tap * (C1 + C2) + ci] for g < groups (forward-pack
@@ -454,6 +464,18 @@ int svl_layernorm_fwd_planes(const float* x, const float* gamma, const float* be
 int svl_layernorm_fwd_planes_f16x2(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C,
                                    float* y, float* stats, void* planes, int64_t planes_rows, int32_t* sexp, float* rnorm,
                                    svl_stream_t stream);
+/* LayerNorm forward / backward (no weight-gradient partials) with the fp16 x 2 planes of the result as a by-product of ONE
+ * pass, C = 768 (other widths: SVL_ERR_UNSUPPORTED; run the row kernel, then svl_split_planes_f16x2).  The finished rows are
+ * packed from an LDS copy instead of a second read: y (optional) / dx / stats carry the bits of svl_layernorm_fwd / _bwd,
+ * planes / sexp / rnorm / tensor_amax those of svl_split_planes_f16x2(result, rows, C, planes, planes_rows, row_off, ...),
+ * padding rows of the last 32-row block included.  row_rnorm != 0 (forward): sexp / rnorm as svl_layernorm_fwd_planes_f16x2
+ * leaves them instead (the norm bound from the row pass's fp32 sum of squares; padding rows untouched). */
+int svl_layernorm_fwd_pack_f16x2(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C,
+                                 float* y, float* stats, void* planes, int64_t planes_rows, int64_t row_off, int32_t* sexp,
+                                 float* rnorm, int row_rnorm, unsigned* tensor_amax, svl_stream_t stream);
+int svl_layernorm_bwd_pack_f16x2(const float* dy, const float* x, const float* stats, const float* gamma, int64_t rows, int C,
+                                 const float* dx_add, float* dx, void* planes, int64_t planes_rows, int64_t row_off,
+                                 int32_t* sexp, float* rnorm, unsigned* tensor_amax, svl_stream_t stream);
 /* dx = LN backward (+ dx_add if non-NULL, fused residual-grad add). If dgamma_part != NULL also writes
  * per-block partial sums dgamma_part/dbeta_part [nparts, C] (nparts = svl_layernorm_bwd_parts(rows)). */
 int svl_layernorm_bwd_parts(int64_t rows);

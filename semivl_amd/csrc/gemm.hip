@@ -1661,7 +1661,19 @@ int launch_shortk(const GemmP& p, bool fast, hipStream_t st) {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // largest |x| of a strided block into *out (atomicMax: the caller zeroes it)
+std::atomic<long> g_absmax_launches{0};   // operand-maximum passes launched so far (svl_absmax_launches: introspection for tests)
+// operand maxima the caller already holds (svl_gemm_desc::a_amax / b_amax) -> the two words the split kernel reads
+__global__ void amax_take_kernel(const unsigned* __restrict__ a, const unsigned* __restrict__ b, unsigned* __restrict__ out) {
+  if (threadIdx.x == 0 && a) out[0] = *a;
+  if (threadIdx.x == 1 && b) out[1] = *b;
+}
+int amax_take(const unsigned* a, const unsigned* b, unsigned* out, hipStream_t st) {
+  hipLaunchKernelGGL(amax_take_kernel, dim3(1), dim3(64), 0, st, a, b, out);
+  SVL_LAUNCH_CHECK("svl_gemm_f32/amax");
+  return SVL_OK;
+}
 int absmax_launch(const float* x, long rows, long cols, long ld, unsigned* out, hipStream_t st) {
+  g_absmax_launches.fetch_add(1, std::memory_order_relaxed);
   if (rows <= 0 || cols <= 0) return SVL_OK;
   const int vec = aligned16(x) && (ld % 4 == 0) && (cols % 4 == 0);
   const long work = rows * cols / (vec ? 4 : 1);
@@ -1813,6 +1825,8 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
   // this call; without it, or for launches too small to pay for the two extra passes, the bf16 x 3 form serves the launch).
   static const int h2_on = getenv("SVL_GEMM_EMU_NO_H2") ? 0 : 1;
   unsigned* h2_ws = static_cast<unsigned*>(d->emu_ws);
+  const unsigned* a_amax = d->a_amax;
+  const unsigned* b_amax = d->b_amax;
   // Worth it when the halved matrix work outweighs the two maximum passes: measured, the fp16 x 2 form runs at ~240 TF where
   // the bf16 x 3 form runs at ~170 (1.7e-15 s saved per FLOP) and a maximum pass reads at ~4 TB/s (x 1.2 for its launch) --
   // the K = 128 pixel-wise layers and the 1 x 1 weight gradients lose, the dilated 3 x 3 layers and the ViT's split-K weight
@@ -1833,9 +1847,13 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
         const double b_elems = bm == SVL_B_PATCHT ? (double)q.K * q.cv.patch * q.cv.patch * q.cv.C1 : (double)q.N * q.K;
         const double elems = (double)q.M * q.K + b_elems;
         if (h2_ok(q, elems) && 2.0 * q.M * q.N * q.K * 1.7e-15 > elems * 4.0 / 4.0e12 * 1.5) {
+          // (a_amax / b_amax: a maximum the caller already holds replaces its pass; the producers' transformed operands
+          //  -- absmax_bx_launch -- always take theirs)
+          const unsigned* b_have = bm == SVL_B_PATCHT ? b_amax : nullptr;
           int rc = h2_begin();
-          if (!rc) rc = absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st);
-          if (!rc) {
+          if (!rc && !a_amax) rc = absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st);
+          if (!rc && (a_amax || b_have)) rc = amax_take(a_amax, b_have, h2_ws, st);
+          if (!rc && !b_have) {
             if (bm == SVL_B_PATCHT) {   // the zero fill adds only zeros: the image's own maximum is the operand's
               const int P = q.cv.patch;
               const long imgs = q.K / ((long)((q.cv.H + P - 1) / P) * ((q.cv.W + P - 1) / P));
@@ -1913,11 +1931,14 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
       if ((d->batch == 1 || d->ksplit > 0) && h2_ok(q, dense_elems) &&
           2.0 * q.M * q.N * q.K * 1.7e-15 > dense_elems * 4.0 / 4.0e12 * 1.5) {
         // dense operands: [M, K] or [K, M], [N, K] or [K, N]
-        int rc = h2_begin();
-        if (!rc) rc = am == SVL_A_MCONTIG ? absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st)
-                                          : absmax_launch(q.A.p, q.M, q.K, q.A.ld, h2_ws, st);
-        if (!rc) rc = bm == SVL_B_NCONTIG ? absmax_launch(q.B.p, q.K, q.N, q.B.ld, h2_ws + 1, st)
-                                          : absmax_launch(q.B.p, q.N, q.K, q.B.ld, h2_ws + 1, st);
+        // (a_amax / b_amax: a maximum the caller already holds -- the pack pass that split the same matrix a moment ago
+        //  left it, svl_split_planes_f16x2 -- replaces that operand's pass over 4 B per element)
+        int rc = (a_amax && b_amax) ? SVL_OK : h2_begin();
+        if (!rc && !a_amax) rc = am == SVL_A_MCONTIG ? absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st)
+                                                      : absmax_launch(q.A.p, q.M, q.K, q.A.ld, h2_ws, st);
+        if (!rc && !b_amax) rc = bm == SVL_B_NCONTIG ? absmax_launch(q.B.p, q.K, q.N, q.B.ld, h2_ws + 1, st)
+                                                      : absmax_launch(q.B.p, q.N, q.K, q.B.ld, h2_ws + 1, st);
+        if (!rc && (a_amax || b_amax)) rc = amax_take(a_amax, b_amax, h2_ws, st);
         if (rc) return rc;
         GemmP q2 = q;
         q2.amax = h2_ws;
@@ -2072,6 +2093,7 @@ extern "C" int svl_set_gemm_emulation(int mode) {
   return SVL_OK;
 }
 extern "C" int svl_last_gemm_path(void) { return g_last_path; }
+extern "C" int64_t svl_absmax_launches(void) { return (int64_t)g_absmax_launches.load(std::memory_order_relaxed); }
 extern "C" int svl_set_conv_tiled(int on) {
   g_conv_tiled.store(on ? 1 : 0, std::memory_order_relaxed);
   return SVL_OK;

@@ -25,7 +25,8 @@ namespace {
 // hits) and writes its share of the k-groups -- the planes are bit-identical to the one-slice launch.
 __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __restrict__ x, long ld, long ks, long rows, int K,
                                                              char* __restrict__ planes, long p_ks, long row_off,
-                                                             int* __restrict__ sexp, float* __restrict__ rnorm) {
+                                                             int* __restrict__ sexp, float* __restrict__ rnorm,
+                                                             unsigned* __restrict__ tensor_amax) {
   __shared__ float s_max[8][32];
   __shared__ double s_sq[8][32];
   __shared__ int s_e[32];
@@ -86,6 +87,12 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
     const long rr = row_off + rb * 32 + tid;
     sexp[rr] = e;
     if (rnorm) rnorm[rr] = r < rows ? (float)(sqrt(sq) * (1.0 + 1e-6)) : 0.f;     // (rounded up: it is used as a bound)
+    if (tensor_amax && blockIdx.y == 0) {     // the matrix's largest |x| as a by-product (absmax_kernel's convention, gemm.hip:
+      float m = r < rows ? amax : 0.f;         // bit pattern of a non-negative float, NaNs take no part, the word zeroed beforehand)
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+      if (tid == 0 && m > 0.f) atomicMax(tensor_amax, __float_as_uint(m));
+    }
   }
   __syncthreads();
   const int nkg = K >> 4;
@@ -119,7 +126,8 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
 }  // namespace
 
 extern "C" int svl_split_planes_f16x2(const float* x, int64_t ld, int64_t k_stride, int64_t rows, int K, void* planes,
-                                      int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm, svl_stream_t stream) {
+                                      int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm, unsigned* tensor_amax,
+                                      svl_stream_t stream) {
   SVL_CHECK_ARG(x && planes && sexp && rows > 0 && K > 0 && (K & 15) == 0 && k_stride >= 1 && planes_rows >= row_off + rows &&
                     row_off >= 0 && (planes_rows & 255) == 0 && (row_off & 31) == 0,
                 "svl_split_planes_f16x2: bad args (K %% 16, planes_rows %% 256, row_off %% 32 must be 0; sexp required)");
@@ -131,8 +139,9 @@ extern "C" int svl_split_planes_f16x2(const float* x, int64_t ld, int64_t k_stri
     if (ysplit > (K >> 6)) ysplit = K >> 6;      // at least four k-groups per slice
     if (ysplit < 1) ysplit = 1;
   }
+  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
   hipLaunchKernelGGL(pack_planes_h2_kernel, dim3((unsigned)blocks, (unsigned)ysplit), dim3(256), 0, (hipStream_t)stream, x, (long)ld,
-                     (long)k_stride, (long)rows, K, (char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm);
+                     (long)k_stride, (long)rows, K, (char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax);
   SVL_LAUNCH_CHECK("svl_split_planes_f16x2");
   return SVL_OK;
 }

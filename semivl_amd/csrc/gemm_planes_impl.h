@@ -50,6 +50,7 @@
 // for (vmcnt) before B_{2kg-1} / B_{2kg}, i.e. at least one barrier before the first read (RAW safe).
 #pragma once
 #include "svl_common.h"
+#include "planes_split_h2.h"
 #include <atomic>
 #include <type_traits>
 
@@ -101,7 +102,6 @@ struct PlanesP {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 is a class: not promoted to registers)
 
@@ -169,20 +169,7 @@ __device__ __forceinline__ void split3x8(const float (&x)[8], bf16x8& h0, bf16x8
   }
 }
 
-// x 2^-e = h0 + h1: the two fp16 planes of 8 values (e = the row's scale exponent)
-__device__ __forceinline__ void split2x8(const float (&x)[8], int e, f16x8& h0, f16x8& h1) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = __builtin_amdgcn_ldexpf(x[j], -e);
-    h0[j] = (_Float16)v;
-    h1[j] = (_Float16)(v - (float)h0[j]);
-  }
-}
-// scale exponent of a row whose entries are bounded by `bound`: bound 2^-e < 2^15 (fp16 overflows at 65504)
-__device__ __forceinline__ int scale_exp_of(float bound) {
-  const int e = __builtin_amdgcn_frexp_expf(bound) - 15;      // bound = f 2^E, f in [0.5, 1)
-  return e < -100 ? -100 : (e > 100 ? 100 : e);
-}
+// (split2x8, scale_exp_of: planes_split_h2.h)
 
 // Block -> tile.  Blocks go to XCD (id % 8) and, inside an XCD, to CUs in id order as CUs free up.  Every XCD first takes
 // its share of the RAGGED row band's tiles (M % 256 rows), then a contiguous chunk of the full tiles in n-fastest order:

@@ -3,6 +3,7 @@
 // row softmax (inside nn.MultiheadAttention), L2 normalise (maskclip_vit.py:555, vlg_head.py:215-216),
 // GroupNorm+ReLU (vlg_head.py:74-137), bias-gradient column sums, F.dropout2d channel masks (builder.py:79-85).
 #include "svl_common.h"
+#include "planes_split_h2.h"
 
 namespace {
 
@@ -101,8 +102,8 @@ __device__ __forceinline__ void ln_emit_planes_h2(const float* __restrict__ src,
       h1[q] = (_Float16)(u - (float)h0[q]);
     }
     char* q_ = planes + (long)kg * p_ks + (r >> 5) * 2048 + (h * 32 + (int)(r & 31)) * 16;
-    *reinterpret_cast<f16x8_*>(q_) = h0;
-    *reinterpret_cast<f16x8_*>(q_ + 1024) = h1;
+    *reinterpret_cast<f16x8*>(q_) = h0;
+    *reinterpret_cast<f16x8*>(q_ + 1024) = h1;
   }
 }
 
@@ -750,6 +751,225 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_apply_kernel(const float* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// LayerNorm forward / backward with the fp16 x 2 planes of the result as a by-product, C = 768: the row pass of the plain
+// row kernels, then the generic pack pass (pack_planes_h2_kernel, gemm_planes_h2.hip) run on an LDS copy of the finished
+// rows instead of on a second read of the fp32 result.  Both arithmetic orders are the originals': y / dx / stats equal
+// the row kernels' bits, planes / sexp / rnorm equal svl_split_planes_f16x2 over that result.
+// A block owns HALF a 32-row pack block (16 rows, 8 waves x 2 rows: both rows of a wave are in flight at once, where the
+// earlier fused kernel left a wave 8 sequential rows); 16 x 772 floats of LDS = 48 KiB, three blocks = 24 waves per CU.
+// The row stride 772 = 4 (mod 64 banks) keeps the column-wise 16 B reads of phase 2 conflict-free (16 rows x 4 banks);
+// phase 1's 8-threads-per-row reads take a 2-way conflict on a quarter of the data volume per thread.  A half block's
+// planes are 256 contiguous bytes per (k-group, lane half, plane).
+// ---------------------------------------------------------------------------------------------
+constexpr int LNP_C = 768, LNP_LD = 772, LNP_ROWS = 16, LNP_NT = 512;
+
+struct LnPackOut {
+  char* planes;
+  long p_ks, row_off;
+  int* sexp;
+  float* rnorm;
+  unsigned* tensor_amax;
+};
+
+// Phases 1 and 2 of the pack pass over tile[16][LNP_LD] (rows past `rows` hold zeros).  from_rows: the row pass already
+// left each row's exponent in s_e and its |max| in s_amax (and wrote sexp / rnorm itself): phase 1 is skipped.
+__device__ __forceinline__ void lnp_pack_tile(const float* tile, int* s_e, float* s_amax, long r0, long rows,
+                                              const LnPackOut& o, bool from_rows) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  if (!from_rows && tid < LNP_ROWS * 8) {   // 8 threads per row, 16 B each, the pack pass's strides and combine order
+    const int row = tid >> 3, sub = tid & 7;
+    const long r = r0 + row;
+    float amax = 0.f;
+    double sq = 0.0;
+    if (r < rows) {
+      const float* src = tile + row * LNP_LD;
+      for (int k = sub * 4; k < LNP_C; k += 32) {
+        const float4 f = *reinterpret_cast<const float4*>(src + k);
+        amax = fmaxf(fmaxf(amax, fabsf(f.x)), fmaxf(fabsf(f.y), fmaxf(fabsf(f.z), fabsf(f.w))));
+        sq += (double)f.x * f.x + (double)f.y * f.y + ((double)f.z * f.z + (double)f.w * f.w);
+      }
+    }
+#pragma unroll
+    for (int q = 1; q < 8; q <<= 1) {
+      amax = fmaxf(amax, __shfl_xor(amax, q, 64));
+      sq += __shfl_xor(sq, q, 64);
+    }
+    if (sub == 0) {
+      const int e = r < rows ? scale_exp_of(amax) : 0;
+      s_e[row] = e;
+      s_amax[row] = amax;
+      const long rr = o.row_off + r;
+      o.sexp[rr] = e;
+      if (o.rnorm) o.rnorm[rr] = r < rows ? (float)(sqrt(sq) * (1.0 + 1e-6)) : 0.f;
+    }
+  }
+  if (!from_rows) __syncthreads();
+  if (o.tensor_amax && tid == 0) {
+    float m = 0.f;
+    for (int q = 0; q < LNP_ROWS; ++q) m = fmaxf(m, s_amax[q]);
+    if (m > 0.f) atomicMax(o.tensor_amax, __float_as_uint(m));
+  }
+  for (int idx = tid; idx < (LNP_C >> 4) * 2 * LNP_ROWS; idx += LNP_NT) {
+    const int r15 = idx & 15, h = (idx >> 4) & 1, kg = idx >> 5;
+    const float* src = tile + r15 * LNP_LD + kg * 16 + 4 * h;
+    const float4 f0 = *reinterpret_cast<const float4*>(src), f1 = *reinterpret_cast<const float4*>(src + 8);
+    const float v[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+    f16x8 h0, h1;
+    split2x8(v, s_e[r15], h0, h1);
+    const long rr = o.row_off + r0 + r15;
+    char* q_ = o.planes + (long)kg * o.p_ks + (rr >> 5) * 2048 + (h * 32 + (int)(rr & 31)) * 16;
+    *reinterpret_cast<f16x8*>(q_) = h0;
+    *reinterpret_cast<f16x8*>(q_ + 1024) = h1;
+  }
+}
+
+// row_rnorm: sexp / rnorm as the planes-only form of layernorm_fwd_kernel leaves them (exponent from the row pass, the
+// norm bound from its fp32 sum of squares, padding rows untouched) instead of as the pack pass does.
+__global__ __launch_bounds__(LNP_NT) void layernorm_fwd_pack_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, float eps, long rows, int C,
+                                                                    float* __restrict__ y, float* __restrict__ stats,
+                                                                    LnPackOut o, int row_rnorm) {
+  __shared__ __attribute__((aligned(16))) float tile[LNP_ROWS * LNP_LD];
+  __shared__ int s_e[LNP_ROWS];
+  __shared__ float s_amax[LNP_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int C4 = C >> 2;
+  const long r0 = (long)blockIdx.x * LNP_ROWS;
+#pragma unroll
+  for (int rw = 0; rw < 2; ++rw) {
+    const int row = wave + 8 * rw;
+    const long r = r0 + row;
+    float4* tr = reinterpret_cast<float4*>(tile + row * LNP_LD);
+    if (r >= rows) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) tr[lane + 64 * j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (lane == 0) { s_e[row] = 0; s_amax[row] = 0.f; }
+      continue;
+    }
+    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+    float mean, rstd, amax = 0.f, sq = 0.f;
+    // (layernorm_fwd_kernel's register-row form, operation for operation)
+    float4 v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (lane + 64 * j < C4) ? xr[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (lane + 64 * j < C4) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+    mean = wave_sum(s) / C;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (lane + 64 * j < C4) {
+        const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
+        q += (a * a + b * b) + (c * c + d * d);
+      }
+    const float var = wave_sum(q) / C;
+    rstd = 1.0f / sqrtf(var + eps);
+    float4* yr = reinterpret_cast<float4*>(y + r * C);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = lane + 64 * j;
+      if (i < C4) {
+        const float4 g = reinterpret_cast<const float4*>(gamma)[i];
+        const float4 b = reinterpret_cast<const float4*>(beta)[i];
+        float4 ov;
+        ov.x = (v[j].x - mean) * rstd * g.x + b.x;
+        ov.y = (v[j].y - mean) * rstd * g.y + b.y;
+        ov.z = (v[j].z - mean) * rstd * g.z + b.z;
+        ov.w = (v[j].w - mean) * rstd * g.w + b.w;
+        if (y) yr[i] = ov;
+        tr[i] = ov;
+        if (row_rnorm) {
+          amax = fmaxf(fmaxf(amax, fabsf(ov.x)), fmaxf(fabsf(ov.y), fmaxf(fabsf(ov.z), fabsf(ov.w))));
+          sq += (ov.x * ov.x + ov.y * ov.y) + (ov.z * ov.z + ov.w * ov.w);
+        }
+      }
+    }
+    if (row_rnorm) {
+      amax = wave_max(amax);
+      sq = wave_sum(sq);
+    }
+    if (lane == 0) {
+      stats[2 * r] = mean;
+      stats[2 * r + 1] = rstd;
+      if (row_rnorm) {
+        const int e = amax > 0.f ? scale_exp_of(amax) : -15;
+        s_e[row] = e;
+        s_amax[row] = amax;
+        o.sexp[o.row_off + r] = e;
+        if (o.rnorm) o.rnorm[o.row_off + r] = sqrtf(sq) * (1.f + 2e-5f);
+      }
+    }
+  }
+  lnp_pack_tile(tile, s_e, s_amax, r0, rows, o, row_rnorm != 0);
+}
+
+// (no dgamma / dbeta partials: their summation order belongs to the 4-wave, 64-row blocks of layernorm_bwd_kernel)
+__global__ __launch_bounds__(LNP_NT) void layernorm_bwd_pack_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                    const float* __restrict__ stats,
+                                                                    const float* __restrict__ gamma, long rows, int C,
+                                                                    const float* __restrict__ dx_add, float* __restrict__ dx,
+                                                                    LnPackOut o) {
+  __shared__ __attribute__((aligned(16))) float tile[LNP_ROWS * LNP_LD];
+  __shared__ int s_e[LNP_ROWS];
+  __shared__ float s_amax[LNP_ROWS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int C4 = C >> 2;
+  const long r0 = (long)blockIdx.x * LNP_ROWS;
+#pragma unroll
+  for (int rw = 0; rw < 2; ++rw) {
+    const int row = wave + 8 * rw;
+    const long r = r0 + row;
+    float4* tr = reinterpret_cast<float4*>(tile + row * LNP_LD);
+    if (r >= rows) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) tr[lane + 64 * j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
+    // (layernorm_bwd_kernel's row loop, operation for operation)
+    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
+    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+    const float4* dr = reinterpret_cast<const float4*>(dy + r * C);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < LN_MAXV; ++j) {
+      const int i = lane + 64 * j;
+      if (i < C4) {
+        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
+        const float h0 = (v.x - mean) * rstd, h1 = (v.y - mean) * rstd, h2 = (v.z - mean) * rstd,
+                    h3 = (v.w - mean) * rstd;
+        const float g0 = d.x * g.x, g1 = d.y * g.y, g2 = d.z * g.z, g3 = d.w * g.w;
+        s1 += (g0 + g1) + (g2 + g3);
+        s2 += (g0 * h0 + g1 * h1) + (g2 * h2 + g3 * h3);
+      }
+    }
+    const float m1 = wave_sum(s1) / C, m2 = wave_sum(s2) / C;
+    float4* oxr = reinterpret_cast<float4*>(dx + r * C);
+#pragma unroll
+    for (int j = 0; j < LN_MAXV; ++j) {
+      const int i = lane + 64 * j;
+      if (i < C4) {
+        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
+        float4 ov;
+        ov.x = rstd * (d.x * g.x - m1 - (v.x - mean) * rstd * m2);
+        ov.y = rstd * (d.y * g.y - m1 - (v.y - mean) * rstd * m2);
+        ov.z = rstd * (d.z * g.z - m1 - (v.z - mean) * rstd * m2);
+        ov.w = rstd * (d.w * g.w - m1 - (v.w - mean) * rstd * m2);
+        if (dx_add) {
+          const float4 a = reinterpret_cast<const float4*>(dx_add + r * C)[i];
+          ov.x += a.x; ov.y += a.y; ov.z += a.z; ov.w += a.w;
+        }
+        oxr[i] = ov;
+        tr[i] = ov;
+      }
+    }
+  }
+  lnp_pack_tile(tile, s_e, s_amax, r0, rows, o, false);
+}
+
 inline dim3 gn_apply_grid(int imgs, long HW, int C) {
   const long PR = 256 / (C / 4);
   long gx = (HW + PR * 8 - 1) / (PR * 8);  // ~8 pixels per thread
@@ -824,6 +1044,49 @@ extern "C" int svl_layernorm_bwd(const float* dy, const float* x, const float* s
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)stream, dy, x, stats, gamma,
                      (long)rows, C, dx_add, dx, dgamma_part, dbeta_part, rpb);
   SVL_LAUNCH_CHECK("svl_layernorm_bwd");
+  return SVL_OK;
+}
+
+namespace {
+int lnp_check(const char* who, int64_t rows, int C, const void* planes, int64_t planes_rows, int64_t row_off, const void* sexp) {
+  if (C != LNP_C) {
+    svl_set_error("%s: C = %d is not served (768 only); use the row kernel and svl_split_planes_f16x2", who, C);
+    return SVL_ERR_UNSUPPORTED;
+  }
+  SVL_CHECK_ARG(rows > 0 && planes && sexp && row_off >= 0 && (row_off & 31) == 0 && (planes_rows & 255) == 0 &&
+                    planes_rows >= row_off + rows,
+                "%s: bad args (planes_rows %% 256, row_off %% 32 must be 0, planes_rows >= row_off + rows; sexp required)", who);
+  return SVL_OK;
+}
+}  // namespace
+
+extern "C" int svl_layernorm_fwd_pack_f16x2(const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
+                                            int C, float* y, float* stats, void* planes, int64_t planes_rows,
+                                            int64_t row_off, int32_t* sexp, float* rnorm, int row_rnorm,
+                                            unsigned* tensor_amax, svl_stream_t stream) {
+  SVL_CHECK_ARG(x && gamma && beta && stats, "svl_layernorm_fwd_pack_f16x2: bad args");
+  if (int rc = lnp_check("svl_layernorm_fwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
+  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
+  const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
+  const long nhb = (rows + 31) / 32 * 2;
+  hipLaunchKernelGGL(layernorm_fwd_pack_kernel, dim3((unsigned)nhb), dim3(LNP_NT), 0, (hipStream_t)stream, x, gamma, beta,
+                     eps, (long)rows, C, y, stats, o, row_rnorm ? 1 : 0);
+  SVL_LAUNCH_CHECK("svl_layernorm_fwd_pack_f16x2");
+  return SVL_OK;
+}
+
+extern "C" int svl_layernorm_bwd_pack_f16x2(const float* dy, const float* x, const float* stats, const float* gamma,
+                                            int64_t rows, int C, const float* dx_add, float* dx, void* planes,
+                                            int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm,
+                                            unsigned* tensor_amax, svl_stream_t stream) {
+  SVL_CHECK_ARG(dy && x && stats && gamma && dx, "svl_layernorm_bwd_pack_f16x2: bad args");
+  if (int rc = lnp_check("svl_layernorm_bwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
+  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
+  const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
+  const long nhb = (rows + 31) / 32 * 2;
+  hipLaunchKernelGGL(layernorm_bwd_pack_kernel, dim3((unsigned)nhb), dim3(LNP_NT), 0, (hipStream_t)stream, dy, x, stats,
+                     gamma, (long)rows, C, dx_add, dx, o);
+  SVL_LAUNCH_CHECK("svl_layernorm_bwd_pack_f16x2");
   return SVL_OK;
 }
 

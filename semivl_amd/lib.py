@@ -39,7 +39,8 @@ class GemmDesc(C.Structure):
                 ("preact", C.c_void_p), ("resid", C.c_void_p),
                 ("ldr_m", C.c_int64), ("ldr_n", C.c_int64), ("r_bs_outer", C.c_int64), ("r_bs_inner", C.c_int64),
                 ("accumulate", C.c_int), ("conv_w_planes", C.c_void_p), ("emu_ws", C.c_void_p),
-                ("b_stats", C.c_void_p), ("b_gamma", C.c_void_p), ("b_beta", C.c_void_p)]
+                ("b_stats", C.c_void_p), ("b_gamma", C.c_void_p), ("b_beta", C.c_void_p),
+                ("a_amax", C.c_void_p), ("b_amax", C.c_void_p)]
 
 
 class PGemmDesc(C.Structure):
@@ -87,7 +88,7 @@ SIGNATURES = {
     "svl_planes_bytes": (_L, [_L, _I]),
     "svl_split_planes_bf16x3": (_I, [_P, _L, _L, _L, _I, _P, _L, _L, _P]),
     "svl_planes_bytes_fmt": (_L, [_L, _I, _I]),
-    "svl_split_planes_f16x2": (_I, [_P, _L, _L, _L, _I, _P, _L, _L, _P, _P, _P]),
+    "svl_split_planes_f16x2": (_I, [_P, _L, _L, _L, _I, _P, _L, _L, _P, _P, _P, _P]),
     "svl_gemm_planes_f32": (_I, [C.POINTER(PGemmDesc), _P]),
     "svl_conv3x3_wgrad_tiled_groups": (_I, [_I, _I, _I, _I, _I]),
     "svl_conv3x3_wgrad_tiled": (_I, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
@@ -110,6 +111,7 @@ SIGNATURES = {
     "svl_stream_prepare": (_I, [_P]),
     "svl_stream_helper": (_I, [_P, C.POINTER(C.c_void_p)]),
     "svl_last_gemm_path": (_I, []),
+    "svl_absmax_launches": (_L, []),
     "svl_shutdown": (_I, []),
     "svl_num_stream_contexts": (_I, []),
     "svl_clock_probe": (_I, [_P, _I, C.c_uint64, _P]),
@@ -127,6 +129,8 @@ SIGNATURES = {
     "svl_layernorm_fwd": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P]),
     "svl_layernorm_fwd_planes": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P]),
     "svl_layernorm_fwd_planes_f16x2": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P, _P, _P]),
+    "svl_layernorm_fwd_pack_f16x2": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P]),
+    "svl_layernorm_bwd_pack_f16x2": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _L, _L, _P, _P, _P, _P]),
     "svl_layernorm_bwd_parts": (_I, [_L]),
     "svl_layernorm_bwd": (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P]),
     "svl_softmax_rows_fwd": (_I, [_P, _L, _I, _L, _F, _P]),

@@ -106,7 +106,8 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
         vproj = qkv[:, 2 * E:]
     v = None
     if save is not None:
-        save.update(x=x, y1=y1, st1=st1, qkv=qkv, vproj=vproj, want_v=want_v, skip_x=skip_x, eps=eps)
+        save.update(x=x, y1=y1, st1=st1, qkv=qkv, vproj=vproj, want_v=want_v, skip_x=skip_x, eps=eps,
+                    y1_amax=y1a.amax if pp else None)     # (the maximum of y1 as packed: the in_proj weight gradient's B operand)
 
     def ffn(pre, want_pre):
         """pre + FFN(LN2(pre)); returns (out, ln2 stats, saved pre-activation or None)."""
@@ -155,7 +156,7 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
     pp = ops.planes_eligible(x.shape[0], E, E)
     g = {}
     dx_res = None
-    dqkv = dqkv_p = None
+    dqkv = dqkv_p = dqkv_amax = None     # dqkv_amax: the maximum the pack pass found, valid while dqkv stays as packed
     wout_parts = []  # (dy, input) pairs contributing to out_proj wgrad
     need_h = "w1" in want or "b1" in want
 
@@ -191,6 +192,7 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
         if D == 64 and pp and ops.attention_planes_ok() and not (s["want_v"] and dv is not None):
             # dqkv also as planes (in_proj's input-gradient GEMM), from the two kernels' epilogues
             dqkv, dqkv_p = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads, planes=True)
+            dqkv_amax = dqkv_p.amax
         elif D == 64:
             dqkv = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads)
         else:
@@ -205,10 +207,10 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
     if dqkv is not None and dvproj is not None:
         rows = dqkv.shape[0]
         ops.copy2d(dvproj, 0, rows, 0, E, dqkv, 2 * E, rows, 0, 3 * E, rows, E, accumulate=True)
-        dvproj = None
+        dvproj = dqkv_amax = None        # (dqkv is written here: a maximum found before no longer describes it)
     g["wout_parts"] = wout_parts
     if dqkv is not None:
-        g["in_full"] = (dqkv, y1)
+        g["in_full"] = (dqkv, y1, dqkv_amax, s.get("y1_amax"))
         dy1 = ops.matmul_nn(dqkv_p if dqkv_p is not None else dqkv, p["win"])
     elif dvproj is not None:
         g["in_v"] = (dvproj, y1)
@@ -274,8 +276,9 @@ def attn_wgrads(p_mod, g, E):
     else:
         out["wout"] = out["bout"] = None
     if "in_full" in g:
-        dqkv, y1 = g["in_full"]
-        out["win"] = sink_grad(a.in_proj_weight, lambda dst, acc: ops.matmul_tn(dqkv, y1, out=dst, accumulate=acc))
+        dqkv, y1, dq_amax, y1_amax = g["in_full"]
+        out["win"] = sink_grad(a.in_proj_weight, lambda dst, acc: ops.matmul_tn(dqkv, y1, out=dst, accumulate=acc,
+                                                                                a_amax=dq_amax, b_amax=y1_amax))
         out["bin"] = sink_grad(a.in_proj_bias, lambda dst, acc: ops.colsum(dqkv, out=dst, accumulate=acc))
     elif "in_v" in g:
         dvp, y1 = g["in_v"]

@@ -123,8 +123,10 @@ EMU_H2_CONVFWD = True
 def gemm(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batch=1, batch_inner=1, ksplit=0,
          c_bso=0, c_bsi=0, alpha=1.0, bias=None, bias_mod=0, act=ACT_NONE, resid=None, r_off=0, ldr_m=None, ldr_n=1,
          r_bso=0, r_bsi=0, accumulate=False, out_mode=OUT_STRIDED, conv=None, ct=(0, 0, 0), preact=None, w_planes=None,
-         emu_h2=True, b_aux=None):
+         emu_h2=True, b_aux=None, amax=None):
     d = L.GemmDesc()
+    if amax is not None:    # (a_amax, b_amax): operand maxima the caller holds (Planes.amax); each may be None
+        d.a_amax, d.b_amax = _p(amax[0]), _p(amax[1])
     if b_aux is not None:   # B_NC_LN: (row statistics, gamma, beta)
         d.b_stats, d.b_gamma, d.b_beta = (_p(t) for t in b_aux)
     d.conv_w_planes = _p(w_planes)
@@ -334,15 +336,17 @@ class Planes:
     """An fp32 matrix [rows, K] in the fragment-packed operand format of svl_gemm_planes_f32 (1 KiB chunks per (k-group,
     32-row block, plane); include/semivl_hip.h).  fmt "b3": three bf16 planes x = x0 + x1 + x2.  fmt "h2": two fp16 planes
     and one scale exponent per row, x = 2^sexp[row] (h0 + h1); `rnorm` (optional) = upper bounds of the rows' L2 norms,
-    which a GEMM needs to scale a planes OUTPUT in this format.  The buffer holds `prow` = rows rounded up to 256 rows."""
-    __slots__ = ("buf", "rows", "K", "prow", "fmt", "sexp", "rnorm", "_bd")
+    which a GEMM needs to scale a planes OUTPUT in this format.  The buffer holds `prow` = rows rounded up to 256 rows.
+    `amax` (optional, h2): one int32 word, the bit pattern of the largest |x| of the matrix the planes were packed from --
+    valid for exactly that matrix (whole rows and columns) until it is written again (matmul_tn's a_amax / b_amax)."""
+    __slots__ = ("buf", "rows", "K", "prow", "fmt", "sexp", "rnorm", "amax", "_bd")
 
     def __init__(self, rows, K, device=None, buf=None, fmt=None, sexp=None, rnorm=None):
         assert K % 16 == 0
         self.fmt = fmt or PLANES_FMT
         self.rows, self.K, self.prow = rows, K, planes_rows(rows)
         dev = device if device is not None else (buf.device if buf is not None else torch.cuda.current_device())
-        self._bd = None
+        self._bd = self.amax = None
         if self.fmt == "h2":
             self.buf = buf if buf is not None else torch.empty(K // 16 * self.prow * 32, dtype=torch.float16, device=dev)
             self.sexp = sexp if sexp is not None else torch.empty(self.prow, dtype=torch.int32, device=dev)
@@ -364,10 +368,17 @@ class Planes:
                       rnorm=self.rnorm)
 
 
-def split_planes(x2d, out=None, row_off=0, transpose=False, fmt=None):
+# The ViT's glue passes read each matrix once (round 7): LayerNorm forward / backward emit their planes from an LDS copy of
+# the finished rows (svl_layernorm_{fwd,bwd}_pack_f16x2) and the pack passes hand the in_proj weight gradient its operand
+# maxima.  SVL_NO_ONEPASS=1 keeps the two-kernel sequences and the maximum passes for A/B runs (same bits either way).
+ONEPASS = not os.environ.get("SVL_NO_ONEPASS")
+
+
+def split_planes(x2d, out=None, row_off=0, transpose=False, fmt=None, want_amax=False):
     """fp32 [rows, K] -> Planes (one HBM pass: 4 B read + 6 / 4 B written per element; the h2 pass reads a 32-row block
     twice, the second time from L2, to find the row scales).  transpose=True splits x2d^T (used once per weight for the
-    input-gradient GEMMs)."""
+    input-gradient GEMMs).  want_amax (h2, a whole fresh Planes): the pass also leaves the matrix's largest |x| in
+    out.amax."""
     assert x2d.dim() == 2 and x2d.dtype == torch.float32
     if transpose:
         K, rows = x2d.shape
@@ -383,8 +394,10 @@ def split_planes(x2d, out=None, row_off=0, transpose=False, fmt=None):
     if out.fmt == "h2":
         if out.rnorm is None:
             out.rnorm = torch.empty(out.prow, dtype=torch.float32, device=x2d.device)
+        if want_amax and ONEPASS and row_off == 0 and out.rows == rows:
+            out.amax = torch.empty(1, dtype=torch.int32, device=x2d.device)
         L.check(L.load().svl_split_planes_f16x2(_p(x2d), ld, ks, rows, K, _p(out.buf), out.prow, row_off, _p(out.sexp),
-                                                _p(out.rnorm), _st()), "svl_split_planes_f16x2")
+                                                _p(out.rnorm), _p(out.amax), _st()), "svl_split_planes_f16x2")
         return out
     L.check(L.load().svl_split_planes_bf16x3(_p(x2d), ld, ks, rows, K, _p(out.buf), out.prow, row_off, _st()),
             "svl_split_planes_bf16x3")
@@ -623,8 +636,9 @@ def _ksplit_plan(M, N, K, dense=False, emu_tiles=False):
     return s, ks
 
 
-def matmul_tn(a, b, out=None, accumulate=False):
-    """out[M,N] = a[K,M]^T @ b[K,N] with deterministic split-K (wgrad: dY^T @ X)."""
+def matmul_tn(a, b, out=None, accumulate=False, a_amax=None, b_amax=None):
+    """out[M,N] = a[K,M]^T @ b[K,N] with deterministic split-K (wgrad: dY^T @ X).  a_amax / b_amax: Planes.amax of exactly
+    these matrices (packed whole, unwritten since): the fp16 x 2 form then skips its maximum pass over that operand."""
     K, M = a.shape
     N = b.shape[1]
     assert b.shape[0] == K and a.stride(1) == 1 and b.stride(1) == 1
@@ -634,16 +648,18 @@ def matmul_tn(a, b, out=None, accumulate=False):
     assert out.is_contiguous()
     s, ks = _ksplit_plan(M, N, K, dense=True)
     if s == 1:
-        gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), out, accumulate=accumulate)
+        gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), out, accumulate=accumulate, amax=(a_amax, b_amax))
         return out
     slabs = empty(s, M, N, device=a.device)
-    gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), slabs, batch=s, ksplit=ks, c_bso=M * N)
+    gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), slabs, batch=s, ksplit=ks, c_bso=M * N,
+         amax=(a_amax, b_amax))
     reduce_slabs(out, slabs, accumulate)
     return out
 
 
-def _matmul_tn_prod(a, N, b_op, b_mode, out, accumulate, conv=None, b_aux=None):
-    """out[M,N] = a[K,M]^T @ f(B)[K,N] with a B-operand producer (the split-K plan of matmul_tn)."""
+def _matmul_tn_prod(a, N, b_op, b_mode, out, accumulate, conv=None, b_aux=None, a_amax=None):
+    """out[M,N] = a[K,M]^T @ f(B)[K,N] with a B-operand producer (the split-K plan of matmul_tn).  a_amax: as matmul_tn's
+    (the producer's transformed B operand always takes its own maximum pass)."""
     K, M = a.shape
     assert a.stride(1) == 1
     if out is None:
@@ -652,18 +668,20 @@ def _matmul_tn_prod(a, N, b_op, b_mode, out, accumulate, conv=None, b_aux=None):
     assert out.is_contiguous() and out.numel() == M * N
     s, ks = _ksplit_plan(M, N, K, dense=True)
     if s == 1:
-        gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, out, accumulate=accumulate, conv=conv, b_aux=b_aux)
+        gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, out, accumulate=accumulate, conv=conv, b_aux=b_aux,
+             amax=(a_amax, None))
         return out
     slabs = empty(s, M, N, device=a.device)
-    gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, slabs, batch=s, ksplit=ks, c_bso=M * N, conv=conv, b_aux=b_aux)
+    gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, slabs, batch=s, ksplit=ks, c_bso=M * N, conv=conv, b_aux=b_aux,
+         amax=(a_amax, None))
     reduce_slabs(out, slabs, accumulate)
     return out
 
 
-def matmul_tn_gelu(a, h_pre, out=None, accumulate=False):
+def matmul_tn_gelu(a, h_pre, out=None, accumulate=False, a_amax=None):
     """out = a^T @ gelu(h_pre): the FFN-2 weight gradient from the saved pre-activation (gelu recomputed while staging)."""
     assert h_pre.shape[0] == a.shape[0] and h_pre.stride(1) == 1
-    return _matmul_tn_prod(a, h_pre.shape[1], Op(h_pre, h_pre.stride(0)), B_NC_GELU, out, accumulate)
+    return _matmul_tn_prod(a, h_pre.shape[1], Op(h_pre, h_pre.stride(0)), B_NC_GELU, out, accumulate, a_amax=a_amax)
 
 
 def matmul_tn_ln(a, x, stats, gamma, beta, out=None, accumulate=False):
@@ -761,6 +779,20 @@ def layernorm_fwd(x, gamma, beta, eps, planes=False, want_y=True):
         L.check(L.load().svl_layernorm_fwd(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, _p(y), _p(stats), _st()),
                 "svl_layernorm_fwd")
         return y, stats
+    if PLANES_FMT == "h2" and ONEPASS and Cc == 768:
+        # one streaming kernel: the row pass, then the pack pass on an LDS copy of the finished rows (bit-identical to the
+        # sequences below; want_y: y, the pack pass's row norms and the matrix maximum for the in_proj weight gradient).
+        # Measured at [32800, 768], sources not cache-warm: 71.7 us with y (row kernel 43 us + pack pass 58 us: 98.2 us in
+        # sequence), 48.2 us planes only (svl_layernorm_fwd_planes_f16x2: 73.9 us)
+        pl = Planes(rows, Cc, device=x.device, fmt="h2")
+        pl.rnorm = torch.empty(pl.prow, dtype=torch.float32, device=x.device)
+        y = torch.empty_like(x) if want_y else None
+        if want_y:
+            pl.amax = torch.empty(1, dtype=torch.int32, device=x.device)
+        L.check(L.load().svl_layernorm_fwd_pack_f16x2(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, _p(y), _p(stats),
+                                                      _p(pl.buf), pl.prow, 0, _p(pl.sexp), _p(pl.rnorm), 0 if want_y else 1,
+                                                      _p(pl.amax), _st()), "svl_layernorm_fwd_pack_f16x2")
+        return y, stats, pl
     if PLANES_FMT == "h2" and not want_y:    # planes only: one kernel (row statistics, exponents, planes)
         pl = Planes(rows, Cc, device=x.device, fmt="h2")
         pl.rnorm = torch.empty(pl.prow, dtype=torch.float32, device=x.device)
@@ -768,11 +800,11 @@ def layernorm_fwd(x, gamma, beta, eps, planes=False, want_y=True):
                                                         _p(pl.buf), pl.prow, _p(pl.sexp), _p(pl.rnorm), _st()),
                 "svl_layernorm_fwd_planes_f16x2")
         return None, stats, pl
-    if want_y or PLANES_FMT == "h2":   # measured at [32800, 768]: row pass (39 us) + pack pass over the cache-warm result (38 us) beats the fused
-        y = torch.empty_like(x)      # kernel (102 us: its 32-row blocks leave 8 sequential rows per wave); planes-only
+    if want_y or PLANES_FMT == "h2":   # other widths / SVL_NO_ONEPASS: row pass + pack pass (98 us at [32800, 768]); the 32-row fused
+        y = torch.empty_like(x)      # kernel above serves planes-only alone (74 us: its blocks leave 8 sequential rows per wave)
         L.check(L.load().svl_layernorm_fwd(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, _p(y), _p(stats), _st()),
-                "svl_layernorm_fwd")                                                 # is faster fused (60 us vs 77)
-        return (y if want_y else None), stats, split_planes(y)      # (h2: the pack pass finds the row scales; no fused form yet)
+                "svl_layernorm_fwd")
+        return (y if want_y else None), stats, split_planes(y, want_amax=True)   # (h2: the pack pass finds the row scales)
     pl = Planes(rows, Cc, device=x.device, fmt="b3")
     L.check(L.load().svl_layernorm_fwd_planes(_p(x), _p(gamma), _p(beta), float(eps), rows, Cc, None, _p(stats),
                                               _p(pl.buf), pl.prow, _st()), "svl_layernorm_fwd_planes")
@@ -784,6 +816,16 @@ def layernorm_bwd(dy, x, stats, gamma, dx_add=None, want_wgrad=False, planes=Fal
     rows, Cc = x.shape
     dx = torch.empty_like(x)
     lib = L.load()
+    if planes and not want_wgrad and PLANES_FMT == "h2" and ONEPASS and Cc == 768:
+        # one streaming kernel (as layernorm_fwd): 111.7 us at [32800, 768] with dx_add, 91.6 us without, against 135.6 /
+        # 115.8 us for the sequence below.  With weight gradients that sequence stays: the partial sums' order belongs to the
+        # row kernel's 4-wave blocks.
+        pl = Planes(rows, Cc, device=x.device, fmt="h2")
+        pl.rnorm = torch.empty(pl.prow, dtype=torch.float32, device=x.device)
+        L.check(lib.svl_layernorm_bwd_pack_f16x2(_p(dy), _p(x), _p(stats), _p(gamma), rows, Cc, _p(dx_add), _p(dx), _p(pl.buf),
+                                                 pl.prow, 0, _p(pl.sexp), _p(pl.rnorm), None, _st()),
+                "svl_layernorm_bwd_pack_f16x2")
+        return dx, pl
     dgp = dbp = None
     if want_wgrad:
         nparts = lib.svl_layernorm_bwd_parts(rows)
@@ -792,7 +834,7 @@ def layernorm_bwd(dy, x, stats, gamma, dx_add=None, want_wgrad=False, planes=Fal
     L.check(lib.svl_layernorm_bwd(_p(dy), _p(x), _p(stats), _p(gamma), rows, Cc, _p(dx_add), _p(dx), _p(dgp), _p(dbp),
                                   _st()), "svl_layernorm_bwd")
     res = (dx, colsum(dgp), colsum(dbp)) if want_wgrad else (dx,)
-    if planes:   # (measured: 81 us + a 38 us pack pass over the cache-warm dx vs 162 us for svl_layernorm_bwd_planes)
+    if planes:   # (row kernel + pack pass: 116 - 136 us at [32800, 768]; the 32-row svl_layernorm_bwd_planes was measured at 162 us)
         res = res + (split_planes(dx),)
     return res if len(res) > 1 else res[0]
 
@@ -983,7 +1025,7 @@ def attention_bwd(dout, qkv, out, lse, Bn, T, H, planes=False):
         L.check(L.load().svl_attention_bwd(_p(qkv), _p(out), _p(dout), _p(lse), Bn, T, H, _p(ws), _p(dqkv), None, 0, _st()),
                 "svl_attention_bwd")
     _prof_end(_attn_family(), e0, 14.0 * Bn * H * T * T * 64, ("bwd_h2" if attention_h2() else "bwd", Bn, T, H))
-    return (dqkv, split_planes(dqkv)) if planes else dqkv
+    return (dqkv, split_planes(dqkv, want_amax=True)) if planes else dqkv   # (amax: for the in_proj weight gradient)
 
 
 # ------------------------------------------------------------------------------------------------ ViT attention (materialised probabilities; head dims != 64)

@@ -61,8 +61,8 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(dbias, hbias.data(), N * 4, hipMemcpyHostToDevice));
   CK(hipMemset(pA, 0, svl_planes_bytes(M, K))); CK(hipMemset(pB, 0, svl_planes_bytes(N, K)));
   if (fmt == 1) {
-    SV(svl_split_planes_f16x2(dA, K, 1, M, K, pA, Mp, 0, seA, rnA, nullptr));
-    SV(svl_split_planes_f16x2(dB, K, 1, N, K, pB, Np, 0, seB, rnB, nullptr));
+    SV(svl_split_planes_f16x2(dA, K, 1, M, K, pA, Mp, 0, seA, rnA, nullptr, nullptr));
+    SV(svl_split_planes_f16x2(dB, K, 1, N, K, pB, Np, 0, seB, rnB, nullptr, nullptr));
     std::vector<float> hrn(Np);
     CK(hipMemcpy(hrn.data(), rnB, Np * 4, hipMemcpyDeviceToHost));
     float hbd[2] = {0.f, 0.f};
