@@ -704,6 +704,19 @@ int svl_avgpool_cat_bwd_text(const float* dy, int imgs, int64_t HWp, int C, int 
 int svl_adamw_step(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const float* seg_lr,
                    const float* seg_wd, int nseg, int64_t total, float beta1, float beta2, float eps, int step,
                    float gscale, float* ema, float ema_decay, svl_stream_t stream);
+/* torch.optim.SGD (maximize=False) on the same arena: the optimizer of semivl.py:118-121 (cfg without an 'optimizer' key:
+ * SGD([backbone @ lr, every parameter whose name lacks 'backbone' @ lr * lr_multi], momentum=0.9, weight_decay=1e-4)), whose
+ * two learning rates the host re-schedules into seg_lr after every step (semivl.py:330-337).  Per element, in this order:
+ *   d = g * gscale + wd * p;
+ *   if momentum != 0:  m = d when step == 1 (torch clones the gradient), else m = momentum * m + (1 - dampening) * d;
+ *                      d = d + momentum * m if nesterov, else d = m;
+ *   p -= lr * d;   if ema != NULL: ema = ema_decay * ema + (1 - ema_decay) * p.
+ * m may be NULL only when momentum == 0; nesterov with momentum <= 0 or dampening != 0 is SVL_ERR_INVALID_ARG (torch raises).
+ * p, g, m, ema 16-byte aligned and every seg_off[s] a multiple of 4 (FusedAdamW's / FusedSGD's arenas): the kernel moves
+ * one float4 per lane and array, 20 B per parameter (28 with ema).  Padding between segments (p = g = m = 0) stays 0. */
+int svl_sgd_step(float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr, const float* seg_wd,
+                 int nseg, int64_t total, float momentum, float dampening, int nesterov, int step, float gscale,
+                 float* ema, float ema_decay, svl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * BatchNorm2d (batch statistics, SyncBN-ready) and MaxPool2d(3, 2, 1) on channels-last [rows, C] activations: the ops of

@@ -1586,6 +1586,14 @@ def adamw_step(p, g, m, v, seg_off, seg_lr, seg_wd, nseg, beta1, beta2, eps, ste
                                     float(ema_decay), _st()), "svl_adamw_step")
 
 
+def sgd_step(p, g, m, seg_off, seg_lr, seg_wd, nseg, momentum, dampening, nesterov, step, gscale=1.0, ema=None,
+             ema_decay=0.0):
+    """torch.optim.SGD over the flat arena (svl_sgd_step); m is None without momentum."""
+    L.check(L.load().svl_sgd_step(_p(p), _p(g), _p(m), _p(seg_off), _p(seg_lr), _p(seg_wd), nseg, p.numel(),
+                                  float(momentum), float(dampening), int(bool(nesterov)), int(step), float(gscale),
+                                  _p(ema), float(ema_decay), _st()), "svl_sgd_step")
+
+
 def semivl_gscale(counts_i64, numel_u, lam, gscale_out, factors=None, mc_counts=None):
     L.check(L.load().svl_semivl_gscale(_p(counts_i64), float(numel_u), float(lam), _p(factors), _p(mc_counts),
                                        _p(gscale_out), _st()), "svl_semivl_gscale")
