@@ -404,7 +404,7 @@ def split_planes(x2d, out=None, row_off=0, transpose=False, fmt=None, want_amax=
     return out
 
 
-WEIGHT_EPOCH = 0          # bumped by FusedAdamW.step(): its kernel rewrites the parameter arena behind torch's back
+WEIGHT_EPOCH = 0          # bumped by ArenaOptimizer.step(): its kernel rewrites the parameter arena behind torch's back
 _WPLANES = {}
 
 

@@ -1,0 +1,404 @@
+"""The fused optimizers: ONE flat fp32 arena per optimizer (ArenaOptimizer), one kernel launch per step.
+
+  semivl.py:123-125,339-345    mmcv param-wise AdamW + poly LR          -> FusedAdamW
+  semivl.py:118-121,330-337    two-group SGD when cfg has no optimizer  -> FusedSGD.original
+  mmseg build_optimizer        cfg['optimizer'] type AdamW / SGD        -> build_optimizer, optimizer_from_cfg
+"""
+import torch
+
+from . import ops
+
+
+def mmcv_param_groups(named_params, lr, weight_decay, custom_keys):
+    """mmcv 1.4.4 DefaultOptimizerConstructor semantics (recalled): one group per parameter; custom keys
+    sorted alphabetically then longest-first; the FIRST key contained in the parameter name sets lr_mult/decay_mult."""
+    keys = sorted(sorted(custom_keys.keys()), key=len, reverse=True)
+    out = []
+    for name, p in named_params:
+        g = dict(name=name, param=p, lr=lr, weight_decay=weight_decay)
+        for k in keys:
+            if k in name:
+                g["lr"] = lr * custom_keys[k].get("lr_mult", 1.0)
+                g["weight_decay"] = weight_decay * custom_keys[k].get("decay_mult", 1.0)
+                break
+        out.append(g)
+    return out
+
+
+def _trainable(name, prm):
+    """The arena rule of every optimizer here: tensors that can receive a gradient.  `clip_encoder.*` (registered with
+    requires_grad=True in the reference, never given a grad -- SURVEY App. E.2) and frozen backbone tensors are left
+    untouched, which is also what torch's optimizers do for params whose .grad is None."""
+    return prm.requires_grad and not name.startswith("clip_encoder.")
+
+
+def arena_layout(sizes):
+    """(offsets, total) of segments of `sizes` floats, each padded to 4 floats: 16-byte aligned, so a float4 of the SGD
+    kernel never straddles two segments.  No sizes: ([], 0)."""
+    offs, o = [], 0
+    for s in sizes:
+        offs.append(o)
+        o += (s + 3) // 4 * 4
+    return offs, o
+
+
+class ArenaOptimizer:
+    """ONE flat fp32 arena: parameters `p`, gradients `g` (`main_grad` views the model's backward writes into), the
+    subclass's state buffers and optionally the EMA teacher, all laid out by arena_layout over `groups` (one dict per
+    arena tensor: name, param, lr, weight_decay).  GradAllReducer and semivl_train_step rely on these attributes.
+
+    A subclass validates its hyper-parameters, calls __init__ with its groups and the names of its state buffers, and
+    supplies `_launch()` (the step's one kernel), `_hyper()` (the hyper-parameters every param group of state_dict()
+    carries), `_state_entry(ai)` (state_dict()'s entry of arena tensor ai, or None) and `_load_state(sd, index)` (copies
+    the entries in, returns the step count)."""
+
+    def __init__(self, model, groups, lr, wd, ema_decay, state):
+        self.lr, self.wd, self.groups = lr, wd, groups
+        arena_index = {id(g_["param"]): i for i, g_ in enumerate(groups)}
+        self.all_params = [(n, arena_index.get(id(p))) for n, p in model.named_parameters()]   # (name, arena slot | None)
+        sizes = [g_["param"].numel() for g_ in groups]
+        self._offs, self.total = arena_layout(sizes)
+        dev = groups[0]["param"].device
+        self.p = ops.zeros(self.total, device=dev)
+        self.g = ops.zeros(self.total, device=dev)
+        for name in state:
+            setattr(self, name, ops.zeros(self.total, device=dev))
+        for g_, off, s in zip(groups, self._offs, sizes):
+            prm = g_["param"]
+            view = self.p[off:off + s].view(prm.shape)
+            ops.eltwise(4, prm.data.contiguous().view(-1), None, out=view.view(-1))
+            prm.data = view
+            prm.main_grad = self.g[off:off + s].view(prm.shape)
+            g_["initial_lr"] = g_["lr"]
+        self.ema = self.p.clone() if ema_decay is not None else None
+        self.ema_decay = ema_decay or 0.0
+        self.seg_off = torch.tensor(self._offs + [self.total], dtype=torch.int64, device=dev)
+        self.seg_wd = torch.tensor([g_["weight_decay"] for g_ in groups], dtype=torch.float32, device=dev)
+        self._lr_host = torch.tensor([g_["lr"] for g_ in groups], dtype=torch.float32)
+        if torch.cuda.is_available():
+            self._lr_host = self._lr_host.pin_memory()
+        self.seg_lr = self._lr_host.to(dev)
+        self._lr_evt = None
+        self.step_count = 0
+        self.grad_scale = 1.0
+        self._lr_factor = 1.0     # the schedule's current factor (poly_lr): lr of the groups outside the arena
+
+    @property
+    def param_groups(self):
+        return self.groups
+
+    def zero_grad(self):
+        ops.fill(self.g, 0.0)
+
+    def _fold_autograd_grads(self):
+        """Gradients that reached a parameter through torch autograd instead of the main_grad sink (e.g. pos_embed
+        behind its bicubic resize at 801x801) are added to the arena."""
+        for g_ in self.groups:
+            prm = g_["param"]
+            if prm.grad is not None:
+                ops.add(prm.main_grad.view(-1), prm.grad.contiguous().view(-1), out=prm.main_grad.view(-1))
+                prm.grad = None
+
+    def step(self):
+        self._fold_autograd_grads()
+        self.step_count += 1
+        self._launch()
+        ops.weights_changed()    # cached bf16 planes of the trainable weights are stale now (ops.weight_planes)
+
+    def _seg(self, buf, ai):
+        """Arena tensor ai's part of `buf`, in the parameter's shape."""
+        off, prm = self._offs[ai], self.groups[ai]["param"]
+        return buf[off:off + prm.numel()].view(prm.shape)
+
+    def _stage_lr(self, lrs):
+        """New per-segment learning rates (Python floats; fp32 only here) through the pinned staging buffer."""
+        # the buffer may still be the source of the previous call's queued copy: wait for THAT copy (issued a whole step
+        # ago in the training loop, so this never stalls there) before overwriting it
+        if self._lr_evt is not None:
+            self._lr_evt.synchronize()
+        for i, lr in enumerate(lrs):
+            self._lr_host[i] = lr
+        self.seg_lr.copy_(self._lr_host, non_blocking=True)
+        if self.seg_lr.is_cuda:
+            self._lr_evt = torch.cuda.Event()
+            self._lr_evt.record()
+
+    def poly_lr(self, iters, max_iters, power=0.9, warmup_iters=0, warmup_ratio=1e-6):
+        """semivl.py:339-345: applied after the step, for the next one; linear warm-up while iters < warmup_iters
+        (semivl.py:339-342: lr = initial_lr * (1 - (1 - iters / warmup_iters) * (1 - warmup_ratio)))."""
+        if iters < warmup_iters:
+            f = 1 - (1 - iters / warmup_iters) * (1 - warmup_ratio)
+        else:
+            f = (1 - iters / max_iters) ** power
+        self._lr_factor = f
+        for g_ in self.groups:
+            g_["lr"] = g_["initial_lr"] * f
+        self._stage_lr([g_["lr"] for g_ in self.groups])
+
+    def state_dict(self):
+        """The layout of the reference's checkpoint entry (`semivl.py:428` stores `optimizer.state_dict()` of a torch
+        optimizer built by mmcv's DefaultOptimizerConstructor): ONE param group per tensor of `model.named_parameters()`,
+        in that order, frozen tensors and `clip_encoder.*` included (mmcv lists them with the base lr / weight decay; they
+        never receive a gradient, so they have no `state` entry); state[i] = the subclass's entry for the tensors of the
+        arena.  Index-compatible with the reference in both directions
+        (tests/test_model_gpu.py::test_optimizer_state_dict_is_index_compatible).  `names` (all parameters, same order) is
+        stored in addition and verified on load."""
+        state, groups = {}, []
+        for j, (name, ai) in enumerate(self.all_params):
+            if ai is None:      # mmcv lists them with the base lr; semivl.py:124-125 gives EVERY group an initial_lr and
+                # :341-345 re-schedules every group from it, so a reference-style loop can load this dict as it is
+                groups.append(dict(lr=self.lr * self._lr_factor, initial_lr=self.lr, weight_decay=self.wd,
+                                   **self._hyper(), params=[j]))
+                continue
+            g_ = self.groups[ai]
+            entry = self._state_entry(ai)
+            if entry is not None:
+                state[j] = entry
+            groups.append(dict(lr=g_["lr"], initial_lr=g_["initial_lr"], weight_decay=g_["weight_decay"],
+                               **self._hyper(), params=[j]))
+        return dict(state=state, param_groups=groups, names=[n for n, _ in self.all_params])
+
+    def load_state_dict(self, sd):
+        """Accepts what state_dict() returns and what the torch optimizer, built by mmcv's constructor, returns."""
+        pg = sd["param_groups"]
+        assert len(pg) == len(self.all_params), "optimizer state does not match this model"
+        self._load_tensor_groups(sd, [(j, ai) for j, (_, ai) in enumerate(self.all_params) if ai is not None],
+                                 [n for n, _ in self.all_params])
+        for j, (_, ai) in enumerate(self.all_params):
+            if ai is None and pg[j].get("initial_lr"):
+                self._lr_factor = pg[j]["lr"] / pg[j]["initial_lr"]
+                break
+
+    def _load_tensor_groups(self, sd, index, names):
+        """One param group per tensor: index = [(number in sd, arena slot)], names = sd's parameter names in its order."""
+        for j, ai in index:
+            g_, sg = self.groups[ai], sd["param_groups"][j]
+            assert [int(k) for k in sg["params"]] == [j], "one parameter per group expected (mmcv constructor layout)"
+            g_["lr"], g_["initial_lr"] = sg["lr"], sg.get("initial_lr", g_["initial_lr"])
+        self._finish_load(sd, index, names)
+
+    def _finish_load(self, sd, index, names):
+        """What every layout shares once the groups' lr is set: the checks, the state entries, the step count, seg_lr."""
+        if "names" in sd:
+            assert list(sd["names"]) == names, "optimizer state was saved for different parameters: %s" % (
+                sorted(set(sd["names"]) ^ set(names))[:6],)
+        stray = set(sd["state"]) - {j for j, _ in index}
+        assert not stray, "state for parameters this model never trains: %s" % sorted(stray)[:6]
+        self.step_count = self._load_state(sd, index)
+        self._stage_lr([g_["lr"] for g_ in self.groups])
+
+
+class FusedAdamW(ArenaOptimizer):
+    """torch.optim.AdamW semantics over the arena: parameters, gradients, exp_avg `m`, exp_avg_sq `v`; one svl_adamw_step
+    launch per step (28 B/param of HBM traffic)."""
+
+    def __init__(self, model, optimizer_cfg, ema_decay=None):
+        assert optimizer_cfg.get("type", "AdamW") == "AdamW"
+        lr, wd = optimizer_cfg["lr"], optimizer_cfg.get("weight_decay", 0.01)
+        self.betas, self.eps = optimizer_cfg.get("betas", (0.9, 0.999)), optimizer_cfg.get("eps", 1e-8)
+        ck = optimizer_cfg.get("paramwise_cfg", {}).get("custom_keys", {})
+        named = [(n, p) for n, p in model.named_parameters() if _trainable(n, p)]
+        super().__init__(model, mmcv_param_groups(named, lr, wd, ck), lr, wd, ema_decay, ("m", "v"))
+
+    def _launch(self):
+        ops.adamw_step(self.p, self.g, self.m, self.v, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups),
+                       self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale, self.ema,
+                       self.ema_decay)
+
+    def _hyper(self):
+        return dict(betas=tuple(self.betas), eps=self.eps, amsgrad=False)
+
+    def _state_entry(self, ai):
+        if self.step_count > 0:
+            return dict(step=torch.tensor(float(self.step_count)),
+                        exp_avg=self._seg(self.m, ai).detach().cpu().clone(),
+                        exp_avg_sq=self._seg(self.v, ai).detach().cpu().clone())
+
+    def load_state_dict(self, sd):
+        """Accepts the reference layout (one group per model parameter) and the compact round-1/2 layout of this package
+        (one group per arena tensor)."""
+        if len(sd["param_groups"]) == len(self.all_params):
+            return super().load_state_dict(sd)
+        assert len(sd["param_groups"]) == len(self.groups), "optimizer state does not match this model"
+        self._load_tensor_groups(sd, [(i, i) for i in range(len(self.groups))], [g_.get("name", "") for g_ in self.groups])
+
+    def _load_state(self, sd, index):
+        steps = set()
+        for j, ai in index:
+            st = sd["state"].get(j)
+            if st is not None:
+                shape = tuple(self.groups[ai]["param"].shape)
+                assert tuple(st["exp_avg"].shape) == shape, (self.groups[ai].get("name"), st["exp_avg"].shape)
+                self._seg(self.m, ai).copy_(st["exp_avg"])
+                self._seg(self.v, ai).copy_(st["exp_avg_sq"].reshape(shape))
+                steps.add(int(st["step"]))
+        assert len(steps) <= 1, "per-tensor step counts differ"
+        return steps.pop() if steps else 0
+
+
+def sgd_original_groups(model, lr, lr_multi, weight_decay=1e-4):
+    """The two param groups of semivl.py:118-121, in the reference's order, as lists of (name, param): group 0 =
+    model.backbone.parameters() (frozen ones included), group 1 = every named parameter whose name lacks 'backbone'
+    (clip_encoder.* falls here).  torch numbers the parameters of a state_dict through the groups in this order.  Returns
+    (members, index, groups): members[k] = [(name, param)], index[name] = torch's parameter index, groups = one dict per
+    ARENA tensor (name, param, lr, weight_decay, group) in model.named_parameters() order, like mmcv_param_groups'."""
+    named = list(model.named_parameters())
+    members = [[("backbone." + n, p) for n, p in model.backbone.named_parameters()],
+               [(n, p) for n, p in named if "backbone" not in n]]
+    which, index = {}, {}
+    for k, mem in enumerate(members):
+        for n, p in mem:
+            if id(p) in which:
+                raise ValueError("parameter %s appears in more than one SGD param group" % n)   # torch raises too
+            which[id(p)] = k
+            index[n] = len(index)
+    stray = [n for n, p in named if id(p) not in which]
+    if stray:
+        raise ValueError("parameters in neither group of the reference's SGD recipe (name contains 'backbone' but not under "
+                         "model.backbone): %s" % stray[:6])
+    lrs = (lr, lr * lr_multi)
+    groups = [dict(name=n, param=p, lr=lrs[which[id(p)]], weight_decay=weight_decay, group=which[id(p)])
+              for n, p in named if _trainable(n, p)]
+    return members, index, groups
+
+
+def sgd_original_lr(lr, lr_multi, iters, max_iters, warmup_iters=0, warmup_ratio=1e-6):
+    """semivl.py:330-337 in its order of operations (Python floats): (lr of group 0, lr of group 1) for the next step."""
+    if iters < warmup_iters:
+        k = (1 - iters / warmup_iters) * (1 - warmup_ratio)
+        cur = lr * (1 - k)
+    else:
+        cur = lr * (1 - iters / max_iters) ** 0.9
+    return cur, cur * lr_multi
+
+
+class FusedSGD(ArenaOptimizer):
+    """torch.optim.SGD semantics over the arena (parameters, gradients, momentum buffer `m`, None without momentum): one
+    svl_sgd_step launch per step, 20 B/param of HBM traffic (28 with the EMA teacher).
+
+    FusedSGD(model, optimizer_cfg): cfg['optimizer'] = dict(type='SGD', lr, momentum, weight_decay, dampening, nesterov,
+    paramwise_cfg) through mmcv's per-parameter groups.  FusedSGD.original(model, lr, lr_multi): the optimizer the
+    reference builds when cfg has no 'optimizer' key (semivl.py:118-121), re-scheduled by semivl.py:330-337; its
+    param_groups, state_dict() and poly_lr follow the reference's two groups (`lr_multi` set), everything else is shared."""
+
+    def __init__(self, model, optimizer_cfg, ema_decay=None, *, lr_multi=None):
+        if optimizer_cfg.get("type", "SGD") != "SGD":
+            raise ValueError("FusedSGD got optimizer type %r" % (optimizer_cfg.get("type"),))
+        momentum, dampening = optimizer_cfg.get("momentum", 0.0), optimizer_cfg.get("dampening", 0.0)
+        nesterov = bool(optimizer_cfg.get("nesterov", False))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch.optim.SGD's refusal
+        self.momentum, self.dampening, self.nesterov, self.lr_multi = momentum, dampening, nesterov, lr_multi
+        lr, wd = optimizer_cfg["lr"], optimizer_cfg.get("weight_decay", 0.0)
+        if lr_multi is None:
+            ck = optimizer_cfg.get("paramwise_cfg", {}).get("custom_keys", {})
+            named = [(n, p) for n, p in model.named_parameters() if _trainable(n, p)]
+            self._members, self._index, groups = None, None, mmcv_param_groups(named, lr, wd, ck)
+        else:
+            self._members, self._index, groups = sgd_original_groups(model, lr, lr_multi, wd)
+            self._pg = [dict(lr=lr), dict(lr=lr * lr_multi)]
+        self.m = None
+        super().__init__(model, groups, lr, wd, ema_decay, ("m",) if momentum != 0 else ())
+
+    @classmethod
+    def original(cls, model, lr, lr_multi, momentum=0.9, weight_decay=1e-4, ema_decay=None):
+        return cls(model, dict(type="SGD", lr=lr, momentum=momentum, weight_decay=weight_decay), ema_decay,
+                   lr_multi=lr_multi)
+
+    @property
+    def param_groups(self):
+        """Per-tensor groups (mmcv layout), or the reference's two groups for the `original` recipe."""
+        return self.groups if self._members is None else self._pg
+
+    def _launch(self):
+        ops.sgd_step(self.p, self.g, self.m, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups), self.momentum,
+                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema, self.ema_decay)
+
+    def _hyper(self):
+        return dict(momentum=self.momentum, dampening=self.dampening, nesterov=self.nesterov, maximize=False, foreach=None,
+                    differentiable=False, fused=None)
+
+    def _state_entry(self, ai):
+        if self.step_count > 0 and self.m is not None:
+            return dict(momentum_buffer=self._seg(self.m, ai).detach().cpu().clone())
+
+    def _original_index(self):
+        """`original`: (names in torch's numbering, [(number, arena slot)] of the arena's tensors)."""
+        names, slot = sorted(self._index, key=self._index.get), dict(self.all_params)
+        return names, [(j, slot[n]) for j, n in enumerate(names) if slot[n] is not None]
+
+    def state_dict(self):
+        """torch.optim.SGD's layout, as the reference saves it (semivl.py:428).  `original`: the two param groups of
+        semivl.py:118-121 with `params` numbered through the groups in order; mmcv style: ArenaOptimizer.state_dict's
+        layout.  state[i] = {'momentum_buffer'} for the tensors of the arena once a step has run.  `step_count` and
+        `names` are stored in addition; torch ignores them, and a dict saved by torch loads without them."""
+        if self._members is None:
+            sd = super().state_dict()
+        else:
+            names, index = self._original_index()
+            entries = [(j, self._state_entry(ai)) for j, ai in index]
+            sd = dict(state={j: e for j, e in entries if e is not None},
+                      param_groups=[dict(lr=self._pg[k]["lr"], weight_decay=self.wd, **self._hyper(),
+                                         params=[self._index[n] for n, _ in mem]) for k, mem in enumerate(self._members)],
+                      names=names)
+        sd["step_count"] = self.step_count
+        return sd
+
+    def load_state_dict(self, sd):
+        """Accepts what state_dict() returns and what torch.optim.SGD, built the same way, returns."""
+        if self._members is None:
+            return super().load_state_dict(sd)
+        pg = sd["param_groups"]
+        assert len(pg) == 2, "the reference's SGD recipe has two param groups"
+        for k, mem in enumerate(self._members):
+            assert [int(i) for i in pg[k]["params"]] == [self._index[n] for n, _ in mem], "param group %d differs" % k
+            self._pg[k]["lr"] = pg[k]["lr"]
+        for g_ in self.groups:
+            g_["lr"] = pg[g_["group"]]["lr"]
+        names, index = self._original_index()
+        self._finish_load(sd, index, names)
+
+    def _load_state(self, sd, index):
+        loaded = 0
+        for j, ai in index:
+            st = sd["state"].get(j)
+            if st is not None and st.get("momentum_buffer") is not None and self.m is not None:
+                buf = self._seg(self.m, ai)
+                assert tuple(st["momentum_buffer"].shape) == tuple(buf.shape), (self.groups[ai].get("name"),
+                                                                               st["momentum_buffer"].shape)
+                buf.copy_(st["momentum_buffer"])
+                loaded += 1
+        assert loaded in (0, len(index)), "momentum buffers for only some of the trained tensors"
+        # torch's SGD keeps no step count: a momentum buffer exists <=> a step has run, which is all the update rule asks
+        return int(sd.get("step_count", 1 if loaded else 0))
+
+    def poly_lr(self, iters, max_iters, power=0.9, warmup_iters=0, warmup_ratio=1e-6):
+        """Applied after the step, for the next one.  `original`: semivl.py:330-337 (lr = cfg lr * f, then lr * lr_multi for
+        group 1, exponent 0.9); mmcv style: semivl.py:339-345, ArenaOptimizer.poly_lr.  Python floats throughout."""
+        if self._members is None:
+            return super().poly_lr(iters, max_iters, power, warmup_iters, warmup_ratio)
+        lrs = sgd_original_lr(self.lr, self.lr_multi, iters, max_iters, warmup_iters, warmup_ratio)
+        self._lr_factor = lrs[0] / self.lr if self.lr else 1.0
+        for k in (0, 1):
+            self._pg[k]["lr"] = lrs[k]
+        for g_ in self.groups:
+            g_["lr"] = lrs[g_["group"]]
+        self._stage_lr([g_["lr"] for g_ in self.groups])
+
+
+def build_optimizer(model, optimizer_cfg, ema_decay=None):
+    """mmseg's build_optimizer for the types this package runs fused: AdamW (exp 40-44) and SGD."""
+    kind = optimizer_cfg.get("type", "AdamW")
+    if kind == "AdamW":
+        return FusedAdamW(model, optimizer_cfg, ema_decay=ema_decay)
+    if kind == "SGD":
+        return FusedSGD(model, optimizer_cfg, ema_decay=ema_decay)
+    raise ValueError("optimizer type %r is not supported (AdamW, SGD)" % (kind,))
+
+
+def optimizer_from_cfg(model, cfg, ema_decay=None):
+    """semivl.py:118-125: without an 'optimizer' key the reference's two-group SGD (cfg['lr'], cfg['lr_multi']), with it
+    whatever the key builds."""
+    if "optimizer" not in cfg:
+        return FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay)
+    return build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay)

@@ -1,10 +1,11 @@
-"""The SemiVL training step on MI355X: loss helpers, the two-branch step, fused AdamW and the gradient all-reduce.
+"""The SemiVL training step on MI355X: loss helpers, the two-branch step and the gradient all-reduce; the fused optimizers
+live in optim.py and are re-exported here.
 
 Mirrors (same names / argument meaning):
   utils/train_utils.py:19-49   cutmix_img_, cutmix_mask, confidence_weighted_loss
   semivl.py:52-58              compute_mc_loss
   semivl.py:223-345            the loop body  -> semivl_train_step()
-  semivl.py:123-125,339-345    mmcv param-wise AdamW + poly LR -> FusedAdamW
+  semivl.py:118-125,330-345    the optimizers + poly LR -> optim.py (FusedAdamW, FusedSGD)
   semivl.py:139-140            DistributedDataParallel -> GradAllReducer (RCCL all-reduce of the flat grad arena)
 """
 
@@ -16,6 +17,8 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .optim import (FusedAdamW, FusedSGD, build_optimizer, mmcv_param_groups, optimizer_from_cfg,  # noqa: F401
+                    sgd_original_groups, sgd_original_lr)
 
 
 # ------------------------------------------------------------------------------------------------ reference-named helpers
@@ -395,446 +398,6 @@ def _cat2i(a, b):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ optimizer
-def mmcv_param_groups(named_params, lr, weight_decay, custom_keys):
-    """mmcv 1.4.4 DefaultOptimizerConstructor semantics (recalled): one group per parameter; custom keys
-    sorted alphabetically then longest-first; the FIRST key contained in the parameter name sets lr_mult/decay_mult."""
-    keys = sorted(sorted(custom_keys.keys()), key=len, reverse=True)
-    out = []
-    for name, p in named_params:
-        g = dict(name=name, param=p, lr=lr, weight_decay=weight_decay)
-        for k in keys:
-            if k in name:
-                g["lr"] = lr * custom_keys[k].get("lr_mult", 1.0)
-                g["weight_decay"] = weight_decay * custom_keys[k].get("decay_mult", 1.0)
-                break
-        out.append(g)
-    return out
-
-
-class FusedAdamW:
-    """torch.optim.AdamW semantics over ONE flat fp32 arena: parameters, gradients (`main_grad` views the model's
-    backward writes into), exp_avg, exp_avg_sq; one svl_adamw_step launch per step (28 B/param of HBM traffic).
-
-    Only parameters that can receive a gradient are placed in the arena: `clip_encoder.*` (registered with
-    requires_grad=True in the reference, never given a grad — SURVEY App. E.2) and frozen backbone tensors are left
-    untouched, which is also what torch's AdamW does for params whose .grad is None.
-    """
-
-    def __init__(self, model, optimizer_cfg, ema_decay=None):
-        assert optimizer_cfg.get("type", "AdamW") == "AdamW"
-        self.lr, self.wd = optimizer_cfg["lr"], optimizer_cfg.get("weight_decay", 0.01)
-        self.betas, self.eps = optimizer_cfg.get("betas", (0.9, 0.999)), optimizer_cfg.get("eps", 1e-8)
-        ck = optimizer_cfg.get("paramwise_cfg", {}).get("custom_keys", {})
-        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and not n.startswith("clip_encoder.")]
-        self.groups = mmcv_param_groups(named, self.lr, self.wd, ck)
-        arena_index = {id(p): i for i, (_, p) in enumerate(named)}
-        self.all_params = [(n, arena_index.get(id(p))) for n, p in model.named_parameters()]   # (name, arena slot | None)
-        dev = named[0][1].device
-        sizes = [g["param"].numel() for g in self.groups]
-        # 16-byte aligned segments
-        offs, o = [], 0
-        for s in sizes:
-            offs.append(o)
-            o += (s + 3) // 4 * 4
-        self.total = o
-        self.p = ops.zeros(self.total, device=dev)
-        self.g = ops.zeros(self.total, device=dev)
-        self.m = ops.zeros(self.total, device=dev)
-        self.v = ops.zeros(self.total, device=dev)
-        self.ema = None
-        for g_, off, s in zip(self.groups, offs, sizes):
-            prm = g_["param"]
-            view = self.p[off:off + s].view(prm.shape)
-            ops.eltwise(4, prm.data.contiguous().view(-1), None, out=view.view(-1))
-            prm.data = view
-            prm.main_grad = self.g[off:off + s].view(prm.shape)
-            g_["initial_lr"] = g_["lr"]
-        if ema_decay is not None:
-            self.ema = self.p.clone()
-        self.ema_decay = ema_decay or 0.0
-        self.seg_off = torch.tensor(offs + [self.total], dtype=torch.int64, device=dev)
-        self.seg_wd = torch.tensor([g_["weight_decay"] for g_ in self.groups], dtype=torch.float32, device=dev)
-        self._lr_host = torch.tensor([g_["lr"] for g_ in self.groups], dtype=torch.float32).pin_memory() \
-            if torch.cuda.is_available() else torch.tensor([g_["lr"] for g_ in self.groups], dtype=torch.float32)
-        self.seg_lr = self._lr_host.to(dev)
-        self._lr_evt = None
-        self.step_count = 0
-        self.grad_scale = 1.0
-        self._lr_factor = 1.0     # the schedule's current factor (poly_lr): lr of the groups outside the arena
-
-    @property
-    def param_groups(self):
-        return self.groups
-
-    def zero_grad(self):
-        ops.fill(self.g, 0.0)
-
-    def _fold_autograd_grads(self):
-        """Gradients that reached a parameter through torch autograd instead of the main_grad sink (e.g. pos_embed
-        behind its bicubic resize at 801x801) are added to the arena."""
-        for g_ in self.groups:
-            prm = g_["param"]
-            if prm.grad is not None:
-                ops.add(prm.main_grad.view(-1), prm.grad.contiguous().view(-1), out=prm.main_grad.view(-1))
-                prm.grad = None
-
-    def step(self):
-        self._fold_autograd_grads()
-        self.step_count += 1
-        ops.adamw_step(self.p, self.g, self.m, self.v, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups),
-                       self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale, self.ema,
-                       self.ema_decay)
-        ops.weights_changed()    # cached bf16 planes of the trainable weights are stale now (ops.weight_planes)
-
-    def state_dict(self):
-        """The layout of the reference's checkpoint entry (`semivl.py:428` stores `optimizer.state_dict()` of a
-        torch.optim.AdamW built by mmcv's DefaultOptimizerConstructor): ONE param group per tensor of
-        `model.named_parameters()`, in that order, frozen tensors and `clip_encoder.*` included (mmcv lists them with the
-        base lr / weight decay; they never receive a gradient, so they have no `state` entry); state[i] = step / exp_avg /
-        exp_avg_sq for the tensors of the arena.  Index-compatible with the reference in both directions
-        (tests/test_model_gpu.py::test_optimizer_state_dict_is_index_compatible).  `names` (all parameters, same order) is
-        stored in addition and verified on load."""
-        state, groups = {}, []
-        off = self.seg_off.tolist()
-        for j, (name, ai) in enumerate(self.all_params):
-            if ai is None:      # mmcv lists them with the base lr; semivl.py:124-125 gives EVERY group an initial_lr and
-                # :341-345 re-schedules every group from it, so a reference-style loop can load this dict as it is
-                groups.append(dict(lr=self.lr * self._lr_factor, initial_lr=self.lr, weight_decay=self.wd,
-                                   betas=tuple(self.betas), eps=self.eps, amsgrad=False, params=[j]))
-                continue
-            g_ = self.groups[ai]
-            shp, n = g_["param"].shape, g_["param"].numel()
-            if self.step_count > 0:
-                state[j] = dict(step=torch.tensor(float(self.step_count)),
-                                exp_avg=self.m[off[ai]:off[ai] + n].view(shp).detach().cpu().clone(),
-                                exp_avg_sq=self.v[off[ai]:off[ai] + n].view(shp).detach().cpu().clone())
-            groups.append(dict(lr=g_["lr"], initial_lr=g_["initial_lr"], weight_decay=g_["weight_decay"],
-                               betas=tuple(self.betas), eps=self.eps, amsgrad=False, params=[j]))
-        return dict(state=state, param_groups=groups, names=[n for n, _ in self.all_params])
-
-    def load_state_dict(self, sd):
-        """Accepts the reference layout (one group per model parameter, above) and the compact round-1/2 layout of this
-        package (one group per arena tensor)."""
-        pg = sd["param_groups"]
-        if len(pg) == len(self.all_params):
-            index = [(j, ai) for j, (_, ai) in enumerate(self.all_params) if ai is not None]
-            mine = [n for n, _ in self.all_params]
-        else:
-            assert len(pg) == len(self.groups), "optimizer state does not match this model"
-            index = [(i, i) for i in range(len(self.groups))]
-            mine = [g_.get("name", "") for g_ in self.groups]
-        if "names" in sd:
-            assert list(sd["names"]) == mine, "optimizer state was saved for different parameters: %s" % (
-                sorted(set(sd["names"]) ^ set(mine))[:6],)
-        off = self.seg_off.tolist()
-        steps = set()
-        for j, ai in index:
-            g_, sg = self.groups[ai], pg[j]
-            assert [int(k) for k in sg["params"]] == [j], "one parameter per group expected (mmcv constructor layout)"
-            g_["lr"], g_["initial_lr"] = sg["lr"], sg.get("initial_lr", g_["initial_lr"])
-            self._lr_host[ai] = g_["lr"]
-            st = sd["state"].get(j)
-            if st is not None:
-                n = g_["param"].numel()
-                assert tuple(st["exp_avg"].shape) == tuple(g_["param"].shape), (g_.get("name"), st["exp_avg"].shape)
-                self.m[off[ai]:off[ai] + n].copy_(st["exp_avg"].reshape(-1))
-                self.v[off[ai]:off[ai] + n].copy_(st["exp_avg_sq"].reshape(-1))
-                steps.add(int(st["step"]))
-        if len(pg) == len(self.all_params):
-            for j, (_, ai) in enumerate(self.all_params):
-                if ai is None and pg[j].get("initial_lr"):
-                    self._lr_factor = pg[j]["lr"] / pg[j]["initial_lr"]
-                    break
-        stray = set(sd["state"]) - {j for j, _ in index}
-        assert not stray, "state for parameters this model never trains: %s" % sorted(stray)[:6]
-        assert len(steps) <= 1, "per-tensor step counts differ"
-        self.step_count = steps.pop() if steps else 0
-        self.seg_lr.copy_(self._lr_host)
-
-    def poly_lr(self, iters, max_iters, power=0.9, warmup_iters=0, warmup_ratio=1e-6):
-        """semivl.py:339-345: applied after the step, for the next one; linear warm-up while iters < warmup_iters
-        (semivl.py:339-342: lr = initial_lr * (1 - (1 - iters / warmup_iters) * (1 - warmup_ratio)))."""
-        if iters < warmup_iters:
-            f = 1 - (1 - iters / warmup_iters) * (1 - warmup_ratio)
-        else:
-            f = (1 - iters / max_iters) ** power
-        # the pinned staging buffer may still be the source of the previous call's queued copy: wait for THAT copy
-        # (issued a whole step ago, so this never stalls in the training loop) before overwriting it
-        if self._lr_evt is not None:
-            self._lr_evt.synchronize()
-        self._lr_factor = f
-        for i, g_ in enumerate(self.groups):
-            g_["lr"] = g_["initial_lr"] * f
-            self._lr_host[i] = g_["lr"]
-        self.seg_lr.copy_(self._lr_host, non_blocking=True)
-        if self.seg_lr.is_cuda:
-            self._lr_evt = torch.cuda.Event()
-            self._lr_evt.record()
-
-
-def _trainable(name, prm):
-    """The arena rule FusedAdamW applies: tensors that can receive a gradient (torch skips params whose .grad is None)."""
-    return prm.requires_grad and not name.startswith("clip_encoder.")
-
-
-def sgd_original_groups(model, lr, lr_multi, weight_decay=1e-4):
-    """The two param groups of semivl.py:118-121, in the reference's order, as lists of (name, param): group 0 =
-    model.backbone.parameters() (frozen ones included), group 1 = every named parameter whose name lacks 'backbone'
-    (clip_encoder.* falls here).  torch numbers the parameters of a state_dict through the groups in this order.  Returns
-    (members, index, groups): members[k] = [(name, param)], index[name] = torch's parameter index, groups = one dict per
-    ARENA tensor (name, param, lr, weight_decay, group) in model.named_parameters() order, like mmcv_param_groups'."""
-    named = list(model.named_parameters())
-    members = [[("backbone." + n, p) for n, p in model.backbone.named_parameters()],
-               [(n, p) for n, p in named if "backbone" not in n]]
-    which, index = {}, {}
-    for k, mem in enumerate(members):
-        for n, p in mem:
-            if id(p) in which:
-                raise ValueError("parameter %s appears in more than one SGD param group" % n)   # torch raises too
-            which[id(p)] = k
-            index[n] = len(index)
-    stray = [n for n, p in named if id(p) not in which]
-    if stray:
-        raise ValueError("parameters in neither group of the reference's SGD recipe (name contains 'backbone' but not under "
-                         "model.backbone): %s" % stray[:6])
-    lrs = (lr, lr * lr_multi)
-    groups = [dict(name=n, param=p, lr=lrs[which[id(p)]], weight_decay=weight_decay, group=which[id(p)])
-              for n, p in named if _trainable(n, p)]
-    return members, index, groups
-
-
-def sgd_original_lr(lr, lr_multi, iters, max_iters, warmup_iters=0, warmup_ratio=1e-6):
-    """semivl.py:330-337 in its order of operations (Python floats): (lr of group 0, lr of group 1) for the next step."""
-    if iters < warmup_iters:
-        k = (1 - iters / warmup_iters) * (1 - warmup_ratio)
-        cur = lr * (1 - k)
-    else:
-        cur = lr * (1 - iters / max_iters) ** 0.9
-    return cur, cur * lr_multi
-
-
-class FusedSGD:
-    """torch.optim.SGD semantics over ONE flat fp32 arena (parameters, `main_grad` gradients, momentum buffer): one
-    svl_sgd_step launch per step, 20 B/param of HBM traffic (28 with the EMA teacher).  Same arena design and attributes as
-    FusedAdamW (GradAllReducer and semivl_train_step take either), same rule for what lives in the arena.
-
-    FusedSGD(model, optimizer_cfg): cfg['optimizer'] = dict(type='SGD', lr, momentum, weight_decay, dampening, nesterov,
-    paramwise_cfg) through mmcv's per-parameter groups.  FusedSGD.original(model, lr, lr_multi): the optimizer the
-    reference builds when cfg has no 'optimizer' key (semivl.py:118-121), re-scheduled by semivl.py:330-337."""
-
-    def __init__(self, model, optimizer_cfg, ema_decay=None):
-        if optimizer_cfg.get("type", "SGD") != "SGD":
-            raise ValueError("FusedSGD got optimizer type %r" % (optimizer_cfg.get("type"),))
-        self.lr, self.wd = optimizer_cfg["lr"], optimizer_cfg.get("weight_decay", 0.0)
-        ck = optimizer_cfg.get("paramwise_cfg", {}).get("custom_keys", {})
-        named = [(n, p) for n, p in model.named_parameters() if _trainable(n, p)]
-        self.lr_multi = self._members = self._index = None
-        self._setup(model, mmcv_param_groups(named, self.lr, self.wd, ck), optimizer_cfg.get("momentum", 0.0),
-                    optimizer_cfg.get("dampening", 0.0), optimizer_cfg.get("nesterov", False), ema_decay)
-
-    @classmethod
-    def original(cls, model, lr, lr_multi, momentum=0.9, weight_decay=1e-4, ema_decay=None):
-        self = cls.__new__(cls)
-        self.lr, self.wd, self.lr_multi = lr, weight_decay, lr_multi
-        self._members, self._index, groups = sgd_original_groups(model, lr, lr_multi, weight_decay)
-        self._setup(model, groups, momentum, 0.0, False, ema_decay)
-        self._pg = [dict(lr=lr), dict(lr=lr * lr_multi)]
-        return self
-
-    def _setup(self, model, groups, momentum, dampening, nesterov, ema_decay):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch.optim.SGD's refusal
-        self.momentum, self.dampening, self.nesterov = momentum, dampening, bool(nesterov)
-        self.groups = groups
-        arena_index = {id(g_["param"]): i for i, g_ in enumerate(groups)}
-        self.all_params = [(n, arena_index.get(id(p))) for n, p in model.named_parameters()]   # (name, arena slot | None)
-        dev = groups[0]["param"].device
-        sizes = [g_["param"].numel() for g_ in groups]
-        offs, o = [], 0
-        for s in sizes:          # 16-byte aligned segments: a float4 of the kernel never straddles two
-            offs.append(o)
-            o += (s + 3) // 4 * 4
-        self.total, self._offs = o, offs
-        self.p = ops.zeros(self.total, device=dev)
-        self.g = ops.zeros(self.total, device=dev)
-        self.m = ops.zeros(self.total, device=dev) if momentum != 0 else None
-        for g_, off, s in zip(groups, offs, sizes):
-            prm = g_["param"]
-            view = self.p[off:off + s].view(prm.shape)
-            ops.eltwise(4, prm.data.contiguous().view(-1), None, out=view.view(-1))
-            prm.data = view
-            prm.main_grad = self.g[off:off + s].view(prm.shape)
-            g_["initial_lr"] = g_["lr"]
-        self.ema = self.p.clone() if ema_decay is not None else None
-        self.ema_decay = ema_decay or 0.0
-        self.seg_off = torch.tensor(offs + [self.total], dtype=torch.int64, device=dev)
-        self.seg_wd = torch.tensor([g_["weight_decay"] for g_ in groups], dtype=torch.float32, device=dev)
-        self._lr_host = torch.tensor([g_["lr"] for g_ in groups], dtype=torch.float32)
-        if torch.cuda.is_available():
-            self._lr_host = self._lr_host.pin_memory()
-        self.seg_lr = self._lr_host.to(dev)
-        self._lr_evt = None
-        self.step_count = 0
-        self.grad_scale = 1.0
-        self._lr_factor = 1.0
-
-    @property
-    def param_groups(self):
-        """Per-tensor groups (mmcv layout), or the reference's two groups for the `original` recipe."""
-        return self.groups if self._members is None else self._pg
-
-    def zero_grad(self):
-        ops.fill(self.g, 0.0)
-
-    def _fold_autograd_grads(self):
-        """Gradients that reached a parameter through torch autograd instead of the main_grad sink are added to the arena."""
-        for g_ in self.groups:
-            prm = g_["param"]
-            if prm.grad is not None:
-                ops.add(prm.main_grad.view(-1), prm.grad.contiguous().view(-1), out=prm.main_grad.view(-1))
-                prm.grad = None
-
-    def step(self):
-        self._fold_autograd_grads()
-        self.step_count += 1
-        ops.sgd_step(self.p, self.g, self.m, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups), self.momentum,
-                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema, self.ema_decay)
-        ops.weights_changed()    # cached bf16 planes of the trainable weights are stale now (ops.weight_planes)
-
-    def _hyper(self):
-        return dict(momentum=self.momentum, dampening=self.dampening, nesterov=self.nesterov, maximize=False, foreach=None,
-                    differentiable=False, fused=None)
-
-    def _buffer(self, ai):
-        off, prm = int(self._offs[ai]), self.groups[ai]["param"]
-        return self.m[off:off + prm.numel()].view(prm.shape)
-
-    def state_dict(self):
-        """torch.optim.SGD's layout, as the reference saves it (semivl.py:428).  `original`: the two param groups of
-        semivl.py:118-121 with `params` numbered through the groups in order; mmcv style: one group per tensor of
-        model.named_parameters() (FusedAdamW.state_dict's layout, with `initial_lr` as semivl.py:124-125 sets it).
-        state[i] = {'momentum_buffer'} for the tensors of the arena once a step has run.  `step_count` and `names` are
-        stored in addition; torch ignores them, and a dict saved by torch loads without them."""
-        state, groups = {}, []
-        has_buf = self.step_count > 0 and self.m is not None
-        if self._members is not None:
-            slot = {n: ai for n, ai in self.all_params}
-            for k, mem in enumerate(self._members):
-                groups.append(dict(lr=self._pg[k]["lr"], weight_decay=self.wd, **self._hyper(),
-                                   params=[self._index[n] for n, _ in mem]))
-                for n, _ in mem:
-                    if has_buf and slot[n] is not None:
-                        state[self._index[n]] = dict(momentum_buffer=self._buffer(slot[n]).detach().cpu().clone())
-            names = sorted(self._index, key=self._index.get)
-        else:
-            for j, (name, ai) in enumerate(self.all_params):
-                if ai is None:
-                    groups.append(dict(lr=self.lr * self._lr_factor, initial_lr=self.lr, weight_decay=self.wd,
-                                       **self._hyper(), params=[j]))
-                    continue
-                g_ = self.groups[ai]
-                if has_buf:
-                    state[j] = dict(momentum_buffer=self._buffer(ai).detach().cpu().clone())
-                groups.append(dict(lr=g_["lr"], initial_lr=g_["initial_lr"], weight_decay=g_["weight_decay"],
-                                   **self._hyper(), params=[j]))
-            names = [n for n, _ in self.all_params]
-        return dict(state=state, param_groups=groups, names=names, step_count=self.step_count)
-
-    def load_state_dict(self, sd):
-        """Accepts what state_dict() returns and what torch.optim.SGD, built the same way, returns."""
-        pg = sd["param_groups"]
-        if self._members is not None:
-            assert len(pg) == 2, "the reference's SGD recipe has two param groups"
-            names = sorted(self._index, key=self._index.get)
-            slot = dict(self.all_params)
-            index = [(j, slot[n]) for j, n in enumerate(names) if slot[n] is not None]
-            for k, mem in enumerate(self._members):
-                assert [int(i) for i in pg[k]["params"]] == [self._index[n] for n, _ in mem], "param group %d differs" % k
-                self._pg[k]["lr"] = pg[k]["lr"]
-            for ai, g_ in enumerate(self.groups):
-                g_["lr"] = pg[g_["group"]]["lr"]
-                self._lr_host[ai] = g_["lr"]
-        else:
-            assert len(pg) == len(self.all_params), "optimizer state does not match this model"
-            names = [n for n, _ in self.all_params]
-            index = [(j, ai) for j, (_, ai) in enumerate(self.all_params) if ai is not None]
-            for j, ai in index:
-                g_, sg = self.groups[ai], pg[j]
-                assert [int(i) for i in sg["params"]] == [j], "one parameter per group expected (mmcv constructor layout)"
-                g_["lr"], g_["initial_lr"] = sg["lr"], sg.get("initial_lr", g_["initial_lr"])
-                self._lr_host[ai] = g_["lr"]
-            for j, (_, ai) in enumerate(self.all_params):
-                if ai is None and pg[j].get("initial_lr"):
-                    self._lr_factor = pg[j]["lr"] / pg[j]["initial_lr"]
-                    break
-        if "names" in sd:
-            assert list(sd["names"]) == names, "optimizer state was saved for different parameters: %s" % (
-                sorted(set(sd["names"]) ^ set(names))[:6],)
-        stray = set(sd["state"]) - {j for j, _ in index}
-        assert not stray, "state for parameters this model never trains: %s" % sorted(stray)[:6]
-        loaded = 0
-        for j, ai in index:
-            st = sd["state"].get(j)
-            if st is not None and st.get("momentum_buffer") is not None and self.m is not None:
-                buf = self._buffer(ai)
-                assert tuple(st["momentum_buffer"].shape) == tuple(buf.shape), (names[j], st["momentum_buffer"].shape)
-                buf.copy_(st["momentum_buffer"])
-                loaded += 1
-        assert loaded in (0, len(index)), "momentum buffers for only some of the trained tensors"
-        # torch's SGD keeps no step count: a momentum buffer exists <=> a step has run, which is all the update rule asks
-        self.step_count = int(sd.get("step_count", 1 if loaded else 0))
-        if self._lr_evt is not None:
-            self._lr_evt.synchronize()
-        self.seg_lr.copy_(self._lr_host)
-
-    def poly_lr(self, iters, max_iters, power=0.9, warmup_iters=0, warmup_ratio=1e-6):
-        """Applied after the step, for the next one.  `original`: semivl.py:330-337 (lr = cfg lr * f, then lr * lr_multi for
-        group 1, exponent 0.9); mmcv style: semivl.py:339-345 as FusedAdamW.poly_lr.  Python floats throughout; fp32 only
-        in the arena's seg_lr."""
-        if self._lr_evt is not None:
-            self._lr_evt.synchronize()      # the staging buffer may still feed the previous call's queued copy
-        if self._members is not None:
-            lrs = sgd_original_lr(self.lr, self.lr_multi, iters, max_iters, warmup_iters, warmup_ratio)
-            self._lr_factor = lrs[0] / self.lr if self.lr else 1.0
-            for k in (0, 1):
-                self._pg[k]["lr"] = lrs[k]
-            for i, g_ in enumerate(self.groups):
-                g_["lr"] = lrs[g_["group"]]
-                self._lr_host[i] = g_["lr"]
-        else:
-            if iters < warmup_iters:
-                f = 1 - (1 - iters / warmup_iters) * (1 - warmup_ratio)
-            else:
-                f = (1 - iters / max_iters) ** power
-            self._lr_factor = f
-            for i, g_ in enumerate(self.groups):
-                g_["lr"] = g_["initial_lr"] * f
-                self._lr_host[i] = g_["lr"]
-        self.seg_lr.copy_(self._lr_host, non_blocking=True)
-        if self.seg_lr.is_cuda:
-            self._lr_evt = torch.cuda.Event()
-            self._lr_evt.record()
-
-
-def build_optimizer(model, optimizer_cfg, ema_decay=None):
-    """mmseg's build_optimizer for the types this package runs fused: AdamW (exp 40-44) and SGD."""
-    kind = optimizer_cfg.get("type", "AdamW")
-    if kind == "AdamW":
-        return FusedAdamW(model, optimizer_cfg, ema_decay=ema_decay)
-    if kind == "SGD":
-        return FusedSGD(model, optimizer_cfg, ema_decay=ema_decay)
-    raise ValueError("optimizer type %r is not supported (AdamW, SGD)" % (kind,))
-
-
-def optimizer_from_cfg(model, cfg, ema_decay=None):
-    """semivl.py:118-125: without an 'optimizer' key the reference's two-group SGD (cfg['lr'], cfg['lr_multi']), with it
-    whatever the key builds."""
-    if "optimizer" not in cfg:
-        return FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay)
-    return build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay)
-
-
 # ------------------------------------------------------------------------------------------------ data parallel
 class GradAllReducer:
     """Data-parallel gradient mean over the flat grad arena, overlapped with backward (replaces DDP's reducer,
@@ -849,8 +412,8 @@ class GradAllReducer:
     last gradient write, so the collective runs under the remaining backward compute: the decoder's bucket under the
     second ViT backward, layers 11..3 under the layers below them.  `finish()` (after backward) folds gradients that
     arrived through torch autograd (pos_embed behind its resize), flushes whatever is left in bucket order (same order on
-    every rank) and makes the compute stream wait for all collectives before AdamW.  xGMI is point-to-point (~153 GB/s per
-    link): a 25 MB bucket is ~0.3 ms on the ring, so few, large buckets; the 1/W of the mean is folded into the AdamW
+    every rank) and makes the compute stream wait for all collectives before the optimizer.  xGMI is point-to-point (~153 GB/s per
+    link): a 25 MB bucket is ~0.3 ms on the ring, so few, large buckets; the 1/W of the mean is folded into the optimizer's
     kernel (grad_scale).  Loss normalisers stay per-rank as in the reference.
     With `overlap=False`, or on backends that cannot run stream-ordered collectives on GPU tensors (gloo: it stages
     through the host and stalls the launching thread), the same buckets are reduced back to back in finish()."""

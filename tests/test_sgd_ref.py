@@ -137,7 +137,7 @@ def test_original_schedule_is_the_reference_arithmetic(iters):
 
 
 def test_dispatch(monkeypatch):
-    from semivl_amd import train as T
+    from semivl_amd import optim as T
     with pytest.raises(ValueError, match="Adagrad"):
         T.build_optimizer(_Stub(), dict(type="Adagrad", lr=0.1))
     with pytest.raises(AssertionError):
