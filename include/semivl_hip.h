@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -753,6 +753,26 @@ int svl_maxpool3x3s2_fwd(const float* x, int imgs, int H, int W, int C, float* y
                          svl_stream_t stream);
 int svl_maxpool3x3s2_bwd(const float* dy, const unsigned char* idx, int imgs, int H, int W, int C, float* dx,
                          svl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Global average pooling over the pixels of each image of a channels-last token slab, and the broadcast of one row per
+ * image back over its pixels: the image-pooling branch of the DeepLabV3+ ASPP (reference
+ * third_party/unimatch/model/semseg/deeplabv3plus.py:84-95 -- the bilinear resize of a 1 x 1 map is a broadcast -- and the
+ * channel concat of :119-126 for that branch).  Rows are `ld*` floats apart; 16-byte accesses when C % 4 == 0, the strides
+ * are multiples of 4 and the pointers are 16-byte aligned, scalar otherwise.  Sums run in double in a fixed order
+ * (deterministic, no atomics) and are rounded once. */
+/* pool[img * ldp + c] = (1 / HW) * sum_{p < HW} x[(img * HW + p) * ldx + c] */
+int svl_gap_tokens_fwd(const float* x, int64_t ldx, int imgs, int64_t HW, int C, float* pool, int64_t ldp,
+                       svl_stream_t stream);
+/* dx[(img * HW + p) * lddx + c] (=|+=) dpool[img * ldp + c] / HW   (accumulate: +=) */
+int svl_gap_tokens_bwd(const float* dpool, int64_t ldp, int imgs, int64_t HW, int C, float* dx, int64_t lddx,
+                       int accumulate, svl_stream_t stream);
+/* dst[(img * HW + p) * ldd + c_off + c] = v[img * ldv + c]: the concat of a per-image row into a channel slice of a wider slab */
+int svl_bcast_rows_fwd(const float* v, int64_t ldv, int imgs, int64_t HW, int C, float* dst, int64_t ldd, int c_off,
+                       svl_stream_t stream);
+/* dv[img * ldv + c] = sum_{p < HW} dy[(img * HW + p) * lddy + c_off + c] */
+int svl_bcast_rows_bwd(const float* dy, int64_t lddy, int c_off, int imgs, int64_t HW, int C, float* dv, int64_t ldv,
+                       svl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * GPU-side input pipeline: the reference loader's per-sample PIL chain

@@ -191,6 +191,10 @@ SIGNATURES = {
     "svl_avgpool_cat_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "svl_avgpool_cat_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "svl_avgpool_cat_bwd_text": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _P]),
+    "svl_gap_tokens_fwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _P]),
+    "svl_gap_tokens_bwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _I, _P]),
+    "svl_bcast_rows_fwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _I, _P]),
+    "svl_bcast_rows_bwd": (_I, [_P, _L, _I, _I, _L, _I, _P, _L, _P]),
     "svl_adamw_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _I, _F, _P, _F, _P]),
     "svl_sgd_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _I, _I, _F, _P, _F, _P]),
 }

@@ -20,11 +20,12 @@ from .text_embeddings import aggregate_concept_predictions, get_class_to_concept
 from .resnet import ResNetV1c
 from .vit import MaskClipVisionTransformer
 from .vlg_head import VLGHead
+from .dlv3p_head import DLV3PHead
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BACKBONES = {"MaskClipVisionTransformer": MaskClipVisionTransformer, "ResNetV1c": ResNetV1c}
-HEADS = {"VLGHead": VLGHead}
+HEADS = {"VLGHead": VLGHead, "DLV3PHead": DLV3PHead}
 SEGMENTORS = {}
 
 
@@ -48,7 +49,8 @@ def _vit_cfg(img_size, out_indices):
 
 
 def builtin_model_cfg(name):
-    """Own restatement of the hyper-parameters of configs/_base_/models/{vlm-vlg-aspp-s2p4-sk04-ftap-mcvitb,mcvit16}.py."""
+    """Own restatement of the hyper-parameters of configs/_base_/models/{vlm-vlg-aspp-s2p4-sk04-ftap-mcvitb,
+    vlm-vlg-aspp-s2p4-skr04-ftap-mcvitb,vlm-dlv3p-bn12-sk4-ft-mcvitb,vlm-dlv3p-bn12-sk4-ftap-mcvitb,mcvit16}.py."""
     if name == "vlm-vlg-aspp-s2p4-sk04-ftap-mcvitb":
         return dict(img_size=512, model=dict(
             type="VLM", pretrained="pretrained/clip2mmseg_ViT16_clip_backbone.pth",
@@ -67,11 +69,21 @@ def builtin_model_cfg(name):
                                           contract_dilation=True)
         c["model"]["decode_head"].update(skip_in_channels=(768, 256), skip_channels=(32, 32), skip_from_conv_feat=True)
         return c
+    if name in ("vlm-dlv3p-bn12-sk4-ft-mcvitb", "vlm-dlv3p-bn12-sk4-ftap-mcvitb"):   # experiment 41: DeepLabV3+ decoder ablation
+        ftap = name == "vlm-dlv3p-bn12-sk4-ftap-mcvitb"    # 'ft': every ViT tensor trains; 'ftap': attention + pos_embed only
+        return dict(img_size=512, norm_cfg=dict(type="SyncBN", requires_grad=True), model=dict(
+            type="VLM", pretrained="pretrained/clip2mmseg_ViT16_clip_backbone.pth",
+            backbone=_vit_cfg(512, [4, 12]),
+            decode_head=dict(type="DLV3PHead", img_size=512, in_channels=512, in_index=3, channels=256,
+                             dilations=(6, 12, 18), c1_in_channels=768, c1_channels=48, dropout_ratio=0, num_classes=19,
+                             norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False, init_cfg=None),
+            freeze_backbone=ftap, exclude_keys=["attn", "pos_embed"] if ftap else None))
     if name == "mcvit16":
         bb = _vit_cfg(512, None)
         bb["pretrained"] = "pretrained/clip2mmseg_ViT16_clip_backbone.pth"
         return dict(img_size=512, backbone=bb)
-    raise ValueError(f"no built-in model config '{name}' (SURVEY §8(f): skr04 / dlv3p / zegclip variants are next-row or out of scope)")
+    raise ValueError(f"no built-in model config '{name}' (the timm-backbone DeepLabV3+ row vlm-dlv3p-bn11-sk4-ft-tvit-in1k and "
+                     f"the vlm-zegclip-* variants are not implemented)")
 
 
 def load_model_cfg(name):
@@ -201,6 +213,8 @@ class VLM(nn.Module):
     def head_res_size(self, in_size):
         """(h, w) of the decode head's own logit map for an input of `in_size`, when forward(head_res=True) would return
         it un-resized (the input is the training crop: ONE resize separates it from the loss), else None."""
+        if isinstance(self.decode_head, DLV3PHead):
+            return None     # its logits are at crop / 16, not crop / 4: the losses take the resized logits
         S_ = self.decode_head.image_size
         if tuple(in_size) != (S_, S_):
             return None
@@ -219,6 +233,8 @@ class VLM(nn.Module):
             raise AttributeError("'VLM' object has no attribute 'train_maskclip_trust'")
         if forward_mode != "default":
             raise ValueError(forward_mode)
+        if isinstance(self.decode_head, DLV3PHead):
+            return self._forward_dlv3p(img, need_fp, only_fp, fp_masks, split_fp)
         S_ = self.decode_head.image_size
         in_size = tuple(img.shape[2:])
         feats, _ = self.backbone.forward_tokens(self.renormalize_img_for_clip(img), need_global=False)
@@ -262,6 +278,39 @@ class VLM(nn.Module):
         if need_fp and split_fp:
             return out.chunk(2)
         return out
+
+
+def _forward_dlv3p(self, img, need_fp, only_fp, fp_masks, split_fp):
+    """forward_wrapper (builder.py:56-102) for the DeepLabV3+ head: feats = [block-4 tokens, embedding], both perturbed by
+    F.dropout2d; need_fp doubles the batch INSIDE the head (its BatchNorm statistics span plain and perturbed samples, so
+    every sample is decoded: no fp_range); the head resizes to (img_size, img_size) (dlv3p_head.py:61), the wrapper to the
+    input size (builder.py:93-97)."""
+    S_ = self.decode_head.image_size
+    in_size = tuple(img.shape[2:])
+    feats, _ = self.backbone.forward_tokens(self.renormalize_img_for_clip(img), need_global=False)
+    if len(feats) != 2 or self.conv_encoder is not None:
+        raise NotImplementedError("DLV3PHead expects backbone.out_indices = [k, num_layers] and no conv_encoder")
+    ps = self.backbone.patch_size
+    hp, wp = (img.shape[2] + ps - 1) // ps, (img.shape[3] + ps - 1) // ps
+    masks = None
+    if only_fp or need_fp:
+        masks = fp_masks
+        if masks is None:
+            masks = [ops.bernoulli((f.shape[0], f.shape[2]), 1.0 - self.fp_rate, img.device) for f in feats]
+        assert len(masks) == len(feats)
+        if only_fp:
+            sc = 1.0 / (1.0 - self.fp_rate)
+            feats = [_ChanMaskFn.apply(f, mk.contiguous(), sc) for f, mk in zip(feats, masks)]
+            masks = None
+    out = self.decode_head.forward_tokens(list(feats), None, (hp, wp), masks, self.fp_rate, out_size=(S_, S_))
+    if in_size != (S_, S_):
+        out = _PlanesResizeFn.apply(out, in_size, self.align_corners)
+    if need_fp and split_fp:
+        return out.chunk(2)
+    return out
+
+
+VLM._forward_dlv3p = _forward_dlv3p
 
 
 class _ChanMaskFn(torch.autograd.Function):

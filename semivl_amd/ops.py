@@ -1740,3 +1740,60 @@ def maxpool3x3s2_bwd(dy, idx, imgs, H, W, C, out=None):
     assert dx.is_contiguous() and dx.numel() == imgs * H * W * C
     L.check(L.load().svl_maxpool3x3s2_bwd(_p(dy), _p(idx), imgs, H, W, C, _p(dx), _st()), "svl_maxpool3x3s2_bwd")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ global pooling on token slabs
+def _rows2d(t):
+    """(tensor, row stride) of a [rows, C] view whose columns are unit-stride (a channel slice of a wider slab included)."""
+    assert t.dim() == 2 and t.dtype == torch.float32 and (t.stride(1) == 1 or t.shape[1] == 1), (t.shape, t.stride())
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def gap_tokens_fwd(x, imgs, HW, out=None):
+    """[imgs, C] per-image column mean of x [imgs * HW, C] (svl_gap_tokens_fwd: double accumulation, fixed order)."""
+    x, ldx = _rows2d(x)
+    Cc = x.shape[1]
+    assert x.shape[0] == imgs * HW
+    if out is None:
+        out = empty(imgs, Cc, device=x.device)
+    out, ldo = _rows2d(out)
+    assert tuple(out.shape) == (imgs, Cc)
+    L.check(L.load().svl_gap_tokens_fwd(_p(x), ldx, imgs, HW, Cc, _p(out), ldo, _st()), "svl_gap_tokens_fwd")
+    return out
+
+
+def gap_tokens_bwd(dpool, imgs, HW, dx=None, accumulate=False):
+    """dx [imgs * HW, C] (=|+=) dpool [imgs, C] / HW.  Without `dx` a fresh tensor is written (the plain form)."""
+    dpool, ldp = _rows2d(dpool)
+    Cc = dpool.shape[1]
+    assert dpool.shape[0] == imgs
+    if dx is None:
+        dx, accumulate = empty(imgs * HW, Cc, device=dpool.device), False
+    dx, lddx = _rows2d(dx)
+    assert tuple(dx.shape) == (imgs * HW, Cc)
+    L.check(L.load().svl_gap_tokens_bwd(_p(dpool), ldp, imgs, HW, Cc, _p(dx), lddx, 1 if accumulate else 0, _st()),
+            "svl_gap_tokens_bwd")
+    return dx
+
+
+def bcast_rows_fwd(v, imgs, HW, slab, c_off):
+    """slab[img * HW + p, c_off : c_off + C] = v[img] for every pixel p: the concat of a per-image row (svl_bcast_rows_fwd).
+    `slab`: a [imgs * HW, >= c_off + C] tensor (or row-strided view) written in place."""
+    v, ldv = _rows2d(v)
+    slab, ldd = _rows2d(slab)
+    Cc = v.shape[1]
+    assert v.shape[0] == imgs and slab.shape[0] == imgs * HW and 0 <= c_off and c_off + Cc <= slab.shape[1]
+    L.check(L.load().svl_bcast_rows_fwd(_p(v), ldv, imgs, HW, Cc, _p(slab), ldd, c_off, _st()), "svl_bcast_rows_fwd")
+    return slab
+
+
+def bcast_rows_bwd(dslab, c_off, Cc, imgs, HW, out=None):
+    """[imgs, C] per-image column sum of dslab[:, c_off : c_off + C] (svl_bcast_rows_bwd)."""
+    dslab, ldd = _rows2d(dslab)
+    assert dslab.shape[0] == imgs * HW and 0 <= c_off and c_off + Cc <= dslab.shape[1]
+    if out is None:
+        out = empty(imgs, Cc, device=dslab.device)
+    out, ldo = _rows2d(out)
+    assert tuple(out.shape) == (imgs, Cc)
+    L.check(L.load().svl_bcast_rows_bwd(_p(dslab), ldd, c_off, imgs, HW, Cc, _p(out), ldo, _st()), "svl_bcast_rows_bwd")
+    return out

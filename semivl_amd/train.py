@@ -239,7 +239,9 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         if side is None:
             side = _SIDE[dev] = torch.cuda.Stream(dev)
     main = torch.cuda.current_stream(dev) if img_x.is_cuda else None
-    pl_side = side if getattr(model, "conv_encoder", None) is None else None
+    # (the same holds for a decode head with BatchNorm -- the DeepLabV3+ head: `has_batchnorm`)
+    head_bn = bool(getattr(getattr(model, "decode_head", None), "has_batchnorm", False))
+    pl_side = side if (getattr(model, "conv_encoder", None) is None and not head_bn) else None
     # The logits stay at the head's resolution (round 5): the bilinear resize to the crop (vlg_head.py:247, builder.py:93-97)
     # is evaluated inside the softmax-max / cross-entropy kernels and the gradient comes back at the head's resolution --
     # the [B, N, H, W] tensors and the two resize passes do not exist.  `up` = (H, W, align_corners) or None (models without
@@ -300,9 +302,14 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         frac = cfg.get("act_mem_fraction", 0.70)
         head.act_limit_bytes = (None if frac is None or not img_x.is_cuda else
                                 int(frac * torch.cuda.get_device_properties(dev).total_memory))
-    preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, fp_range=(0, B), **fwd_kw)
+    # A head with BatchNorm decodes all 4 B samples, [w, x, w_fp, x_fp]: with batch statistics x_fp enters every mean and
+    # variance of the reference's need_fp forward (cat((f, dropout2d(f))) over [x, w], builder.py:78-89), so it cannot be
+    # left out; its dlogits are zero like pred_w's, and backward runs on the whole batch (the statistics terms carry
+    # gradient into those rows).
+    fp_kw = {} if head_bn else dict(fp_range=(0, B))
+    preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **fwd_kw)
     preds_s = model(_cat2(img_s1, img_s2), **fwd_kw)                                       # [s1, s2]
-    pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:]
+    pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:3 * B]
     pred_s1, pred_s2 = preds_s[:B], preds_s[B:]
     conf_w, mask_w = smax(pred_w.detach())
     if side is not None:        # join: the label maps of the side stream are consumed from here on
@@ -345,6 +352,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     dl4 = torch.empty_like(preds4)
     dls = torch.empty_like(preds_s)
     ops.fill(dl4[:B], 0.0)  # pred_w is detached (semivl.py:251)
+    if head_bn:
+        ops.fill(dl4[3 * B:], 0.0)   # pred_x_fp is never read (semivl.py:247)
     sums = ops.empty(4, 4, dtype=torch.float64, device=dev)
     def ce(pred, *a_, **kw):
         if up is not None:
@@ -357,7 +366,7 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     ce(pred_s2.detach(), mw2, False, conf=cw2, ign=ig2, conf_thresh=thr, mc=mc2, dlogits=dls[B:],
        gscale=gscale[2], sums_out=sums[2], all_pixels=whole_map, img_weight=ratios[1])
     ce(pred_w_fp.detach(), mask_w, False, conf=conf_w, ign=ign, conf_thresh=thr, mc=mclip,
-       dlogits=dl4[2 * B:], gscale=gscale[3], sums_out=sums[3], all_pixels=whole_map, img_weight=ratios[2])
+       dlogits=dl4[2 * B:3 * B], gscale=gscale[3], sums_out=sums[3], all_pixels=whole_map, img_weight=ratios[2])
     losses = ops.empty(8, device=dev)
     ops.semivl_loss(sums, numel_u, lam, losses, factors, mc_counts)
     # backward (+ all-reduce) + optimizer
