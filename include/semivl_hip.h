@@ -614,8 +614,22 @@ int svl_attention_bwd(const float* qkv, const float* out, const float* dout, con
  * fp32 kernels' (tests/test_ops_gpu.py).  `ws` = caller-provided scratch of svl_attention_h2_ws_bytes(B, T, H, backward)
  * bytes, 1 KiB aligned, private to the call's stream until the call's work has finished.  Results, argument meaning and the
  * optional bf16 x 3 planes outputs as above (the planes outputs need no emulation mode here).  Match
- * maskclip_vit.py:77-84,141 (q pre-scaled by 64^-0.5 -- exact --, fp32 softmax). */
+ * maskclip_vit.py:77-84,141 (q pre-scaled by 64^-0.5 -- exact --, fp32 softmax).
+ * Operand sets are ROW-MAJOR only (the kernels form the transposed fragments while reading LDS): with S = B H roundup(T, 64)
+ * 256 bytes per set the workspace holds 3 sets forward (backward = 0: Q | K | V), 4 backward (backward = 1: + dO) and 1
+ * (backward = 2: dO alone) for svl_attention_bwd_h2_sets, each plus a few KiB of exponents, norms and per-query pairs.
+ * KEPT SETS: svl_attention_fwd_h2 leaves its workspace valid -- Q | K | V sets, exponents, norms, a pure function of qkv --
+ * and svl_attention_bwd_h2_sets takes it as `sets` (sets_bytes >= the backward = 0 size; read only, 1 KiB aligned) together
+ * with a backward = 2 workspace: it packs dout alone and launches the same grids as svl_attention_bwd_h2, whose results it
+ * reproduces bit for bit when `sets` came from the forward of the same qkv (qkv itself is then not read).
+ * svl_attention_h2_tr_sets(on): the A/B switch (also SVL_ATTN_TR_SETS=1 in the environment at first use).  on = 1 restores
+ * the previous sequence -- transposed sets packed and read, 7 sets backward, svl_attention_bwd_h2_sets refused --, on = 0 the
+ * default, on < 0 only queries; returns the value that held before.  Same bits either way; the workspace sizes follow it. */
 int64_t svl_attention_h2_ws_bytes(int B, int T, int H, int backward);
+int svl_attention_h2_tr_sets(int on);
+int svl_attention_bwd_h2_sets(const float* qkv, const float* out, const float* dout, const float* lse, int B, int T, int H,
+                              float* dsum_ws, float* dqkv, const void* sets, int64_t sets_bytes, void* ws, int64_t ws_bytes,
+                              svl_stream_t stream);
 int svl_attention_fwd_h2(const float* qkv, int B, int T, int H, float* out, float* lse, void* out_planes,
                          int64_t planes_rows, void* ws, int64_t ws_bytes, svl_stream_t stream);
 int svl_attention_bwd_h2(const float* qkv, const float* out, const float* dout, const float* lse, int B, int T, int H,

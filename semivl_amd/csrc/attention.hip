@@ -627,9 +627,11 @@ extern "C" int svl_attention_bwd(const float* qkv, const float* out, const float
 
 // ---- fp16 x 2 path (attn_h2.hip): operands pre-packed into a caller-provided workspace, three products per term
 extern "C" int64_t svl_attention_h2_ws_bytes(int B, int T, int H, int backward) {
-  if (B <= 0 || T <= 0 || H <= 0) return 0;
-  return svl_attn_h2::ws_bytes(B, T, H, backward);
+  if (B <= 0 || T <= 0 || H <= 0 || backward < 0 || backward > 2) return 0;
+  return svl_attn_h2::ws_bytes(B, T, H, backward, svl_attn_h2::tr_sets(-1));
 }
+
+extern "C" int svl_attention_h2_tr_sets(int on) { return svl_attn_h2::tr_sets(on); }
 
 extern "C" int svl_attention_fwd_h2(const float* qkv, int B, int T, int H, float* out, float* lse, void* out_planes,
                                     int64_t planes_rows, void* ws, int64_t ws_bytes, svl_stream_t stream) {
@@ -645,35 +647,37 @@ extern "C" int svl_attention_fwd_h2(const float* qkv, int B, int T, int H, float
   hipStream_t st = (hipStream_t)stream;
   int nb = 0;
   const int r = rows_split(T, &nb, FQ);
-  rc = svl_attn_h2::fwd_pack(p, ws, ws_bytes, st);
+  const int tr = svl_attn_h2::tr_sets(-1);
+  rc = svl_attn_h2::fwd_pack(p, ws, ws_bytes, tr, st);
   if (rc) return rc;
   if (r > 0) {   // the leftover rows: single-wave MFMA workgroups on the packed operands, on the helper stream (after the pack)
     hipStream_t aux = nullptr;
     rc = svl_fork(st, &aux);
     if (rc) return rc;
-    rc = svl_attn_h2::fwd_tail(p, nb * FQ, ws, aux);
+    rc = svl_attn_h2::fwd_tail(p, nb * FQ, ws, tr, aux);
     if (rc) return rc;
   }
-  rc = svl_attn_h2::fwd(p, nb, ws, ws_bytes, st);
+  rc = svl_attn_h2::fwd(p, nb, ws, ws_bytes, tr, st);
   if (rc) return rc;
   return r > 0 ? svl_join(st) : SVL_OK;
 }
 
-extern "C" int svl_attention_bwd_h2(const float* qkv, const float* out, const float* dout, const float* lse, int B, int T,
-                                    int H, float* dsum_ws, float* dqkv, void* dq_planes, int64_t planes_rows, void* ws,
-                                    int64_t ws_bytes, svl_stream_t stream) {
-  int rc = check(qkv, B, T, H, "svl_attention_bwd_h2");
+namespace {
+int bwd_h2(const char* who, const float* qkv, const float* out, const float* dout, const float* lse, int B, int T, int H,
+           float* dsum_ws, float* dqkv, void* dq_planes, const void* sets, int64_t sets_bytes, void* ws, int64_t ws_bytes,
+           svl_stream_t stream) {
+  int rc = check(qkv, B, T, H, who);
   if (rc) return rc;
-  SVL_CHECK_ARG(out && dout && lse && dsum_ws && dqkv, "svl_attention_bwd_h2: null args");
-  (void)planes_rows;
-  rc = no_planes(dq_planes, "svl_attention_bwd_h2");
+  SVL_CHECK_ARG(out && dout && lse && dsum_ws && dqkv, "%s: null args", who);
+  rc = no_planes(dq_planes, who);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   AttnP p;
   memset(&p, 0, sizeof(p));
   p.qkv = qkv; p.dout = dout; p.lse = const_cast<float*>(lse); p.dsum = dsum_ws; p.dqkv = dqkv;
   p.B = B; p.T = T; p.H = H; p.E = (long)H * D; p.ld = 3 * p.E; p.scale = 0.125f;
-  rc = svl_attn_h2::bwd_prepare(p, out, dsum_ws, ws, ws_bytes, st);
+  const int tr = svl_attn_h2::tr_sets(-1);
+  rc = svl_attn_h2::bwd_prepare(p, out, dsum_ws, ws, ws_bytes, sets, sets_bytes, tr, st);
   if (rc) return rc;
   int nb = 0;
   const int r = rows_split(T, &nb, FQ);
@@ -681,10 +685,26 @@ extern "C" int svl_attention_bwd_h2(const float* qkv, const float* out, const fl
     hipStream_t aux = nullptr;
     rc = svl_fork(st, &aux);
     if (rc) return rc;
-    rc = svl_attn_h2::bwd_tail(p, nb * FQ, ws, aux);
+    rc = svl_attn_h2::bwd_tail(p, nb * FQ, ws, sets, tr, aux);
     if (rc) return rc;
   }
-  rc = svl_attn_h2::bwd_main(p, nb, ws, st);
+  rc = svl_attn_h2::bwd_main(p, nb, ws, sets, tr, st);
   if (rc) return rc;
   return r > 0 ? svl_join(st) : SVL_OK;
+}
+}  // namespace
+
+extern "C" int svl_attention_bwd_h2(const float* qkv, const float* out, const float* dout, const float* lse, int B, int T,
+                                    int H, float* dsum_ws, float* dqkv, void* dq_planes, int64_t planes_rows, void* ws,
+                                    int64_t ws_bytes, svl_stream_t stream) {
+  (void)planes_rows;
+  return bwd_h2("svl_attention_bwd_h2", qkv, out, dout, lse, B, T, H, dsum_ws, dqkv, dq_planes, nullptr, 0, ws, ws_bytes, stream);
+}
+
+extern "C" int svl_attention_bwd_h2_sets(const float* qkv, const float* out, const float* dout, const float* lse, int B, int T,
+                                         int H, float* dsum_ws, float* dqkv, const void* sets, int64_t sets_bytes, void* ws,
+                                         int64_t ws_bytes, svl_stream_t stream) {
+  SVL_CHECK_ARG(sets, "svl_attention_bwd_h2_sets: sets missing");
+  return bwd_h2("svl_attention_bwd_h2_sets", qkv, out, dout, lse, B, T, H, dsum_ws, dqkv, nullptr, sets, sets_bytes, ws, ws_bytes,
+                stream);
 }

@@ -13,17 +13,22 @@
 //                     (contraction over the head dim: S = Q K^T, dP = dO V^T);
 //   transposed "tr":  chunk (kgt, rbd, pl) at ((kgt 2 + rbd) 2 + pl) KiB: rows d = 32 rbd + r, tokens 16 kgt + 4 hh +
 //                     {0..3, 8..11} (contraction over tokens: O = P V, dV = P^T dO, dK = dS^T Q, dQ = dS K).
+// Round 8: only the rm sets exist in memory.  A tr fragment holds the same halfs as the rm chunks of its 32-row block in
+// another order, and the kernels form it while READING the block's LDS image (ds_read_b64_tr_b16, see tr_lane below): the pack
+// writes Q, K, V forward and dO backward once, and a backward may take Q, K, V from the workspace its forward left (mode 2).
+// Every fragment, exponent and product order is what it was: same bits.  SVL_ATTN_TR_SETS=1 / svl_attention_h2_tr_sets(1)
+// restores the tr sets -- packed, moved and read as before (the V = 3 instantiations; V = 7 = row-major sets only).
 // The token order inside a 16-group is the row order of an MFMA accumulator's 8-register run, so P / dS leave the softmax
 // as B (or A) operands by conversion alone.  P and dS are the only values split inside the kernels: P 2^7 (forward; the lazy
 // rescale keeps P <= 2^8), P 2^14 (backward, P <= 1) and dS 2^(14 - g) with g from |dP - D| <= 2 max|dO_i| max|V_j|.
 //
 // Kernels (512 threads = 8 waves x 32 rows, one block per CU, three LDS stages, one raw s_barrier per interval, LDS-DMA in
 // flight across barriers with counted vmcnt -- the loops issue no other vector-memory instruction):
-//   forward : block = 256 queries, 64-key tiles (K rm 16 KiB + V tr 16 KiB per stage).  Waves 4..7 run one interval behind
+//   forward : block = 256 queries, 64-key tiles (K rm 16 KiB + V tr 16 KiB per stage; round 8: V rm, the same 16 KiB).  Waves 4..7 run one interval behind
 //             waves 0..3: on every SIMD one wave is in the MFMA-only S^T phase while its partner does softmax + P V.
-//   dQ      : block = 256 queries, 64-key tiles (K rm + V rm + K tr = 48 KiB per stage).
+//   dQ      : block = 256 queries, 64-key tiles (K rm + V rm + K tr = 48 KiB per stage; round 8: K rm + V rm = 32 KiB).
 //   dK, dV  : block = 256 keys (their K / V fragments in registers), 32-query tiles (Q rm, dO rm, Q tr, dO tr + the
-//             queries' (-LSE log2 e, D 2^(14 - g)) pairs = 33 KiB per stage).
+//             queries' (-LSE log2 e, D 2^(14 - g)) pairs = 33 KiB per stage; round 8: Q rm, dO rm + the pairs = 17 KiB).
 // S is recomputed in the backward with the forward's products in the forward's order (dK / dV: operand roles swapped, same
 // terms): bit-identical, so P = exp(S - LSE) is consistent with the forward's softmax.
 #include "attn_h2.h"
@@ -122,6 +127,60 @@ __device__ __forceinline__ void frag2(f16x8 (&a)[2], const char* chunk0) {
   a[0] = *reinterpret_cast<const f16x8*>(chunk0);
   a[1] = *reinterpret_cast<const f16x8*>(chunk0 + 1024);
 }
+// Transposed fragments from the ROW-MAJOR image (round 8, V & 4).  A 32-row block of an rm set is 8 chunks (kg, pl) at
+// (kg 2 + pl) KiB; ds_read_b64_tr_b16 hands lane i of a 16-lane group column i of a 4-row x 16-column block of halfs whose
+// row q, columns 4p..4p+3 lane 4q + p of the group addresses.  For the tr fragment (tokens 16 kgl + 4 hh + {0..3, 8..11} of the
+// block, d = 32 rbd + r) the group (hh, g = r >> 4) takes chunk kg = 2 rbd + g: row q = token 16 kgl + 4 hh + q, column quad
+// p = the 8 bytes (p >> 1) of lane slot (hh' = p & 1, token); a second read with the tokens + 8 completes the eight halfs.
+// Unswizzled, the two lane halves of a chunk (512 B apart) and the chunks kg, kg + 1 (2 KiB apart) fall on the same banks
+// (4-way).  The LDS-DMA's SOURCE offset is per lane, so the image is stored with the 16-byte slots permuted inside each chunk:
+// LDS slot hh 32 + t holds the set's slot hh 32 + (t ^ (4 hh + 8 (kg & 1))) -- an involution.  Both the transposed reads (one
+// 32-lane half covers 32 distinct 8-byte slots of a 256-byte bank row) and the row reads (each ds_read_b128 lane group still
+// covers 16 distinct 16-byte slots) are then conflict-free.
+typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
+typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
+struct TrLane {
+  unsigned rm[2];    // byte offset of this lane's 16 bytes in a swizzled chunk with kg & 1 = 0 / 1 (row reads AND DMA source)
+  unsigned tr[2];    // byte offsets in the swizzled row-block image of this lane's address for tokens + 0 / + 8
+};
+__device__ __forceinline__ TrLane tr_lane(int lane) {
+  const int hh = lane >> 5, r = lane & 31, g = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3;
+  TrLane t;
+  t.rm[0] = (unsigned)(hh * 32 + (r ^ (4 * hh))) * 16u;
+  t.rm[1] = (unsigned)(hh * 32 + (r ^ (4 * hh + 8))) * 16u;
+  t.tr[0] = (unsigned)(g * 2048 + ((p & 1) * 32 + ((4 * hh + q) ^ (4 * (p & 1) + 8 * g))) * 16 + (p >> 1) * 8);
+  t.tr[1] = t.tr[0] ^ 128u;
+  return t;
+}
+typedef __attribute__((address_space(3))) char lchar;
+// An image's read base (image + this lane's tr[0] / tr[1]) as ONE 32-bit LDS address the optimiser cannot take apart: every
+// read is then that register + an immediate.  (Left transparent, the loop-invariant part of each (base + constant) is hoisted
+// into a register of its own -- 16 of them in the dK / dV kernel, 235 registers instead of 184 -- and no leftover-row wave fits
+// beside two such waves per SIMD any more.)
+__device__ __forceinline__ const lchar* tr_base(const char* img, unsigned off) {
+  const lchar* b = (const lchar*)(img + off);
+  asm("" : "+v"(b));
+  return b;
+}
+__device__ __forceinline__ f16x8 tr_read8(const lchar* a0, const lchar* a1) {
+  typedef __attribute__((address_space(3))) s16x4 lds4;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a1);
+  return __builtin_bit_cast(f16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// the tr fragment (tokens 16 kgl .., d block rbd; both planes) of the swizzled row-block image `img` (LDS, 8 KiB).  EXEC must be
+// all ones (the gather crosses lanes): every call site sits under wave-uniform control flow only.
+__device__ __forceinline__ void frag2(f16x8 (&a)[2], const lchar* chunk0) {
+  typedef __attribute__((address_space(3))) f16x8 lds8;
+  a[0] = *reinterpret_cast<const lds8*>(chunk0);
+  a[1] = *reinterpret_cast<const lds8*>(chunk0 + 1024);
+}
+// (t0 / t1 = tr_base of the image with this lane's tr[0] / tr[1])
+__device__ __forceinline__ void frag2_tr(f16x8 (&a)[2], const lchar* t0, const lchar* t1, int kgl, int rbd) {
+  const int o = kgl * 256 + rbd * 4096;
+  a[0] = tr_read8(t0 + o, t1 + o);
+  a[1] = tr_read8(t0 + o + 1024, t1 + o + 1024);
+}
 // exponent g of the dS scale: |dP - D| <= 2 max_i |dO_i| max_j |V_j| = f 2^g with f in [0.5, 1)
 __device__ __forceinline__ int ds_exp(float nrm_do, float nrm_v) {
   const float bt = 2.f * nrm_do * nrm_v;
@@ -138,6 +197,8 @@ struct PackP {
   int which[4];          // tensors of this launch (blockIdx.y -> which[y])
   int* exps;
   float* nrm;
+  const int* exps_in;    // kept sets (the launch packs dO alone): q, k, v exponents and norms are copied from here
+  const float* nrm_in;
   int B, T, H, Tp;
 };
 
@@ -232,6 +293,10 @@ __global__ __launch_bounds__(256) void attn_pack_kernel(const PackP p) {
     p.exps[z * 4 + w] = e;
     p.nrm[z * 4 + w] = sqrtf(nr);
   }
+  if (p.exps_in && tid < 3) {
+    p.exps[z * 4 + tid] = p.exps_in[z * 4 + tid];
+    p.nrm[z * 4 + tid] = p.nrm_in[z * 4 + tid];
+  }
 }
 
 // D = rowsum(dO * O) per (z, query) -> dsum [z][T] (the leftover-row kernels' input) and the backward kernels' per-query pair
@@ -271,6 +336,7 @@ constexpr int STG_F = 32 * 1024;   // K rm (16 chunks) | V tr (16 chunks) of one
 template <int V>
 __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H2W w) {
   constexpr bool MIX = (V & 1) != 0;
+  constexpr bool RM = (V & 4) != 0;      // V as its row-major set (same 16 KiB per tile), fragments by transposed reads
   extern __shared__ __attribute__((aligned(1024))) char sm[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -284,8 +350,10 @@ __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H
   const int nkt = w.Tp >> 6;
   const long rmz = (long)(w.Tp >> 5) * 8192, trz = (long)w.Tp * 256;
   const char* ksrc = w.k_rm + z * rmz;
-  const char* vsrc = w.v_tr + z * trz;
+  const char* vsrc = RM ? w.v_rm + z * rmz : w.v_tr + z * trz;
   const unsigned lane16 = lane * 16;
+  const TrLane tl = tr_lane(lane);
+  const unsigned lane_v = RM ? (wave & 1 ? tl.rm[1] : tl.rm[0]) : lane16;   // (a wave moves chunks kg = wave & 3 of a part)
   const unsigned sm_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
   f16x8 qf[2][4];
   {
@@ -303,8 +371,9 @@ __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H
     const int tc = min(tile, nkt - 1);
     const char* s = (part ? vsrc : ksrc) + (long)tc * 16384 + wave * 2048;
     const unsigned dst = sm_base + stage * STG_F + part * 16384 + wave * 2048;
-    glds16(s, lane16, dst);
-    glds16(s + 1024, lane16, dst + 1024);
+    const unsigned lo = part ? lane_v : lane16;
+    glds16(s, lo, dst);
+    glds16(s + 1024, lo, dst + 1024);
   };
   f32x16 o0, o1, s0, s1;
 #pragma unroll
@@ -347,6 +416,8 @@ __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H
   auto phase2 = [&](int kt, auto last_c) __attribute__((always_inline)) {   // softmax, O^T += V^T P^T
     constexpr bool LAST = decltype(last_c)::value;
     const char* Vt = sm + (kt % 3) * STG_F + 16384 + lane16;
+    const lchar* Vt0 = RM ? tr_base(sm + (kt % 3) * STG_F + 16384, tl.tr[0]) : nullptr;     // (RM: the swizzled V image, 2 row blocks)
+    const lchar* Vt1 = RM ? tr_base(sm + (kt % 3) * STG_F + 16384, tl.tr[1]) : nullptr;
     if (LAST) {   // keys past T (zero rows) are masked
       const int j0 = kt * 64;
 #pragma unroll
@@ -397,8 +468,13 @@ __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H
       }
       f16x8 pb[2], a0[2], a1[2];
       split2x8<MIX>(x, pb);
-      frag2(a0, Vt + ((tp * 2) * 2) * 1024);
-      frag2(a1, Vt + ((tp * 2 + 1) * 2) * 1024);
+      if constexpr (RM) {
+        frag2_tr(a0, Vt0 + (tp >> 1) * 8192, Vt1 + (tp >> 1) * 8192, tp & 1, 0);
+        frag2_tr(a1, Vt0 + (tp >> 1) * 8192, Vt1 + (tp >> 1) * 8192, tp & 1, 1);
+      } else {
+        frag2(a0, Vt + ((tp * 2) * 2) * 1024);
+        frag2(a1, Vt + ((tp * 2 + 1) * 2) * 1024);
+      }
       H2_PAIR(o0, a0, o1, a1, pb)
     }
     l += sum0 + sum1;
@@ -462,11 +538,14 @@ __global__ __launch_bounds__(512) void attn_fwd_h2_kernel(const AttnP p, const H
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dQ
-constexpr int STG_Q = 48 * 1024;   // K rm | V rm | K tr of one 64-key tile
+constexpr int STG_Q = 48 * 1024;      // K rm | V rm | K tr of one 64-key tile
+constexpr int STG_Q_RM = 32 * 1024;   // K rm (swizzled: read both ways) | V rm
 
 template <int V>
 __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2W w) {
   constexpr bool MIX = (V & 1) != 0;
+  constexpr bool RM = (V & 4) != 0;
+  constexpr int STG = RM ? STG_Q_RM : STG_Q, NCH = RM ? 4 : 6;     // bytes per stage, chunks per wave and tile
   extern __shared__ __attribute__((aligned(1024))) char sm[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -478,8 +557,9 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
   const bool wave_active = q0 < p.T;
   const int nkt = w.Tp >> 6;
   const long rmz = (long)(w.Tp >> 5) * 8192, trz = (long)w.Tp * 256;
-  const char* src3[3] = {w.k_rm + z * rmz, w.v_rm + z * rmz, w.k_tr + z * trz};
+  const char* src3[3] = {w.k_rm + z * rmz, w.v_rm + z * rmz, RM ? nullptr : w.k_tr + z * trz};
   const unsigned lane16 = lane * 16;
+  const TrLane tl = tr_lane(lane);
   const unsigned sm_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
   f16x8 qf[2][4], of[2][4];
   {
@@ -501,24 +581,30 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
   f32x16 dq0, dq1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dq0[r] = 0.f; dq1[r] = 0.f; }
-  // 48 chunks per tile, six per wave (chunk 6 wave + i; 16 per part)
+  // 48 (RM: 32) chunks per tile, six (four) per wave (chunk NCH wave + i; 16 per part; chunk cc of a part is (rb, kg, pl) =
+  // (cc >> 3, (cc >> 1) & 3, cc & 1): with four per wave kg & 1 = i >> 1)
   auto issue_tile = [&](int tile, int stage) __attribute__((always_inline)) {
     const int tc = min(tile, nkt - 1);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int cidx = wave * 6 + i, part = cidx >> 4, cc = cidx & 15;
+    for (int i = 0; i < NCH; ++i) {
+      const int cidx = wave * NCH + i, part = cidx >> 4, cc = cidx & 15;
       const char* s = (part == 0 ? src3[0] : part == 1 ? src3[1] : src3[2]) + (long)tc * 16384 + cc * 1024;
-      glds16(s, lane16, sm_base + stage * STG_Q + cidx * 1024);
+      const unsigned lo = RM && part == 0 ? tl.rm[(i >> 1) & 1] : lane16;
+      glds16(s, lo, sm_base + stage * STG + cidx * 1024);
     }
   };
   issue_tile(0, 0);
   issue_tile(1, 1);
-  wait_vm<6>();
+  wait_vm<NCH>();
   interval_barrier();
   auto tile = [&](int kt, auto last_c) __attribute__((always_inline)) {
     constexpr bool last = decltype(last_c)::value;      // (compile-time: the key mask lives in the peeled last tile only)
     {
-      const char* Ks = sm + (kt % 3) * STG_Q + lane16;
+      const char* Ki = sm + (kt % 3) * STG;      // (RM: the swizzled K image, 2 row blocks)
+      const lchar* Kr[2] = {RM ? tr_base(Ki, tl.rm[0]) : nullptr, RM ? tr_base(Ki, tl.rm[1]) : nullptr};
+      const lchar* Kt0 = RM ? tr_base(Ki, tl.tr[0]) : nullptr;
+      const lchar* Kt1 = RM ? tr_base(Ki, tl.tr[1]) : nullptr;
+      const char* Ks = Ki + lane16;
       const char* Vs = Ks + 16384;
       const char* Kt = Ks + 32768;
 #pragma unroll
@@ -530,7 +616,8 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
 #pragma unroll
           for (int kg = 0; kg < 4; ++kg) {
             f16x8 ka[2], va[2], bq[2] = {qf[0][kg], qf[1][kg]}, bo[2] = {of[0][kg], of[1][kg]};
-            frag2(ka, Ks + ((jt * 4 + kg) * 2) * 1024);
+            if constexpr (RM) frag2(ka, Kr[kg & 1] + ((jt * 4 + kg) * 2) * 1024);
+            else frag2(ka, Ks + ((jt * 4 + kg) * 2) * 1024);
             frag2(va, Vs + ((jt * 4 + kg) * 2) * 1024);
             H2_2(sa, ka, bq, dp, va, bo)
           }
@@ -547,8 +634,14 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
               x[j] = __builtin_amdgcn_exp2f(fmaf(sa[8 * t + j], c, a_i)) * fmaf(dp[8 * t + j], cdp, -d_i);
             f16x8 pb[2], a0[2], a1[2];
             split2x8<MIX>(x, pb);
-            frag2(a0, Kt + (((2 * jt + t) * 2) * 2) * 1024);
-            frag2(a1, Kt + (((2 * jt + t) * 2 + 1) * 2) * 1024);
+            if constexpr (RM) {
+              __builtin_amdgcn_sched_barrier(0);     // (as in the dK / dV kernel: keeps the transposed reads by their products)
+              frag2_tr(a0, Kt0 + jt * 8192, Kt1 + jt * 8192, t, 0);
+              frag2_tr(a1, Kt0 + jt * 8192, Kt1 + jt * 8192, t, 1);
+            } else {
+              frag2(a0, Kt + (((2 * jt + t) * 2) * 2) * 1024);
+              frag2(a1, Kt + (((2 * jt + t) * 2 + 1) * 2) * 1024);
+            }
             H2_PAIR(dq0, a0, dq1, a1, pb)
           }
         }
@@ -558,7 +651,7 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
   for (int kt = 0; kt < nkt - 1; ++kt) {
     issue_tile(kt + 2, (kt + 2) % 3);
     if (wave_active) tile(kt, std::false_type{});
-    wait_vm<6>();                      // tile kt + 1 (issued one tile ago) has landed
+    wait_vm<NCH>();                     // tile kt + 1 (issued one tile ago) has landed
     interval_barrier();
   }
   if (wave_active) tile(nkt - 1, std::true_type{});
@@ -576,11 +669,14 @@ __global__ __launch_bounds__(512) void attn_dq_h2_kernel(const AttnP p, const H2
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
-constexpr int STG_K = 33 * 1024;   // Q rm | dO rm | Q tr | dO tr (8 chunks each) | the 32 queries' (a, d') pairs (+ over-read)
+constexpr int STG_K = 33 * 1024;      // Q rm | dO rm | Q tr | dO tr (8 chunks each) | the 32 queries' (a, d') pairs (+ over-read)
+constexpr int STG_K_RM = 17 * 1024;   // Q rm | dO rm (both swizzled: read both ways) | the pairs
 
 template <int V>
 __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H2W w) {
   constexpr bool MIX = (V & 1) != 0;
+  constexpr bool RM = (V & 4) != 0;
+  constexpr int STG = RM ? STG_K_RM : STG_K, NCH = RM ? 2 : 4, LDO = RM ? 16384 : 32768;   // (LDO: the pairs' offset in a stage)
   extern __shared__ __attribute__((aligned(1024))) char sm[];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -591,7 +687,8 @@ __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H
   const bool wave_active = k0 < p.T;
   const int nqt = (p.T + 31) >> 5;          // 32-query tiles that hold a query (the operand sets are padded to 64)
   const long rmz = (long)(w.Tp >> 5) * 8192, trz = (long)w.Tp * 256;
-  const char* src4[4] = {w.q_rm + z * rmz, w.do_rm + z * rmz, w.q_tr + z * trz, w.do_tr + z * trz};
+  const char* src4[4] = {w.q_rm + z * rmz, w.do_rm + z * rmz, RM ? nullptr : w.q_tr + z * trz, RM ? nullptr : w.do_tr + z * trz};
+  const TrLane tl = tr_lane(lane);
   const char* ldsrc = reinterpret_cast<const char*>(w.ld + (long)z * w.Tp * 2);
   const unsigned lane16 = lane * 16;
   const unsigned sm_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)sm;
@@ -613,20 +710,22 @@ __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H
   f32x16 dv0, dv1, dk0, dk1;
 #pragma unroll
   for (int r = 0; r < 16; ++r) { dv0[r] = 0.f; dv1[r] = 0.f; dk0[r] = 0.f; dk1[r] = 0.f; }
-  // 32 chunks per tile, four per wave (chunk 4 wave + i; 8 per part); wave 0 also moves the queries' pairs
+  // 32 (RM: 16) chunks per tile, four (two) per wave (chunk NCH wave + i; 8 per part; chunk cc of a part is (kg, pl) =
+  // (cc >> 1, cc & 1): with two per wave kg & 1 = wave & 1); wave 0 also moves the queries' pairs
+  const unsigned lane_s = RM ? (wave & 1 ? tl.rm[1] : tl.rm[0]) : lane16;
   auto issue_tile = [&](int tile, int stage) __attribute__((always_inline)) {
     const int tc = min(tile, nqt - 1);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int cidx = wave * 4 + i, part = cidx >> 3, cc = cidx & 7;
+    for (int i = 0; i < NCH; ++i) {
+      const int cidx = wave * NCH + i, part = cidx >> 3, cc = cidx & 7;
       const char* s = (part == 0 ? src4[0] : part == 1 ? src4[1] : part == 2 ? src4[2] : src4[3]) + (long)tc * 8192 + cc * 1024;
-      glds16(s, lane16, sm_base + stage * STG_K + cidx * 1024);
+      glds16(s, lane_s, sm_base + stage * STG + cidx * 1024);
     }
-    if (wave == 0) glds16(ldsrc + (long)tc * 256, lane16, sm_base + stage * STG_K + 32768);
+    if (wave == 0) glds16(ldsrc + (long)tc * 256, lane16, sm_base + stage * STG + LDO);
   };
   auto wait_older = [&]() __attribute__((always_inline)) {
-    if (wave == 0) wait_vm<5>();
-    else wait_vm<4>();
+    if (wave == 0) wait_vm<NCH + 1>();
+    else wait_vm<NCH>();
   };
   issue_tile(0, 0);
   issue_tile(1, 1);
@@ -635,19 +734,28 @@ __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H
   for (int qt = 0; qt < nqt; ++qt) {
     issue_tile(qt + 2, (qt + 2) % 3);
     if (wave_active) {
-      const char* Qs = sm + (qt % 3) * STG_K + lane16;
+      const char* Qi = sm + (qt % 3) * STG;      // (RM: the swizzled Q image, dO's 8 KiB behind)
+      const lchar* Qr[2] = {RM ? tr_base(Qi, tl.rm[0]) : nullptr, RM ? tr_base(Qi, tl.rm[1]) : nullptr};
+      const lchar* Qt0 = RM ? tr_base(Qi, tl.tr[0]) : nullptr;
+      const lchar* Qt1 = RM ? tr_base(Qi, tl.tr[1]) : nullptr;
+      const char* Qs = Qi + lane16;
       const char* Os = Qs + 8192;
       const char* Qt = Qs + 16384;
       const char* Ot = Qs + 24576;
-      const float* LD = reinterpret_cast<const float*>(sm + (qt % 3) * STG_K + 32768);
+      const float* LD = reinterpret_cast<const float*>(sm + (qt % 3) * STG + LDO);
       f32x16 sa, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { sa[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
       for (int kg = 0; kg < 4; ++kg) {
         f16x8 qa[2], oa[2], bk[2] = {kf[0][kg], kf[1][kg]}, bv[2] = {vf[0][kg], vf[1][kg]};
-        frag2(qa, Qs + (kg * 2) * 1024);
-        frag2(oa, Os + (kg * 2) * 1024);
+        if constexpr (RM) {
+          frag2(qa, Qr[kg & 1] + (kg * 2) * 1024);
+          frag2(oa, Qr[kg & 1] + 8192 + (kg * 2) * 1024);
+        } else {
+          frag2(qa, Qs + (kg * 2) * 1024);
+          frag2(oa, Os + (kg * 2) * 1024);
+        }
         H2_2T(sa, qa, bk, dp, oa, bv)
       }
 #pragma unroll
@@ -669,11 +777,25 @@ __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H
         f16x8 pa[2], sa2[2], o0[2], o1[2], q0f[2], q1f[2];
         split2x8<MIX>(xp, pa);
         split2x8<MIX>(xs, sa2);
-        frag2(o0, Ot + ((t * 2) * 2) * 1024);
-        frag2(o1, Ot + ((t * 2 + 1) * 2) * 1024);
+        // (the scheduler otherwise issues all 32 transposed reads of the tile at once and holds 64 registers of fragments: 246
+        //  registers, and no leftover-row wave fits beside two such waves per SIMD any more)
+        if constexpr (RM) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (RM) {
+          frag2_tr(o0, Qt0 + 8192, Qt1 + 8192, t, 0);
+          frag2_tr(o1, Qt0 + 8192, Qt1 + 8192, t, 1);
+        } else {
+          frag2(o0, Ot + ((t * 2) * 2) * 1024);
+          frag2(o1, Ot + ((t * 2 + 1) * 2) * 1024);
+        }
         H2_2(dv0, pa, o0, dv1, pa, o1)
-        frag2(q0f, Qt + ((t * 2) * 2) * 1024);
-        frag2(q1f, Qt + ((t * 2 + 1) * 2) * 1024);
+        if constexpr (RM) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (RM) {
+          frag2_tr(q0f, Qt0, Qt1, t, 0);
+          frag2_tr(q1f, Qt0, Qt1, t, 1);
+        } else {
+          frag2(q0f, Qt + ((t * 2) * 2) * 1024);
+          frag2(q1f, Qt + ((t * 2 + 1) * 2) * 1024);
+        }
         H2_2(dk0, sa2, q0f, dk1, sa2, q1f)
       }
     }
@@ -713,18 +835,34 @@ __global__ __launch_bounds__(512) void attn_dkv_h2_kernel(const AttnP p, const H
 // robin to the four waves of a 256-thread workgroup and their partial results -- (running maximum, sum, O) of the online
 // softmax; dQ; dK | dV -- are combined through a few hundred bytes of LDS: only the <= 4 valid rows of the tile travel.
 // 128 registers per wave, so that the workgroup's waves fit beside the two resident waves per SIMD of every main kernel.
+// Round 8 (RM): the fragments that came from tr chunks are read from the row-major set instead -- each wave moves the 32-row
+// block it needs (8 chunks, swizzled as in the main grids) into 8 KiB of LDS of its own by LDS-DMA while it works on the row
+// products, and reads it with ds_read_b64_tr_b16.  No workgroup barrier is involved: a wave waits for its own DMAs (vmcnt(0);
+// the compiler's counted waits for the plain loads issued after a DMA are only stricter for it) and for its own LDS reads
+// (lgkmcnt(0)) before it overwrites the block.  32 KiB per workgroup: it still fits beside every main kernel's stages.
 constexpr int TAILW = 4;     // waves per leftover tile
-template <bool MIX>
+__device__ __forceinline__ void tail_stage(const char* blk, const TrLane& tl, unsigned dst) {   // one row block -> this wave's LDS
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the reads of the block held before have returned
+#pragma unroll
+  for (int c = 0; c < 8; ++c) glds16(blk + c * 1024, tl.rm[(c >> 1) & 1], dst + c * 1024);
+}
+template <bool MIX, bool RM>
 __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_tail_h2_kernel(const AttnP p, const H2W w, int row0) {
+  __shared__ __attribute__((aligned(1024))) char stg[RM ? TAILW * 8192 : 16];
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const TrLane tl = tr_lane(lane);
+  const char* stw = stg + (RM ? wave * 8192 : 0);
+  const lchar* st0 = RM ? tr_base(stw, tl.tr[0]) : nullptr;
+  const lchar* st1 = RM ? tr_base(stw, tl.tr[1]) : nullptr;
+  const unsigned stw_a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)stg + (RM ? wave * 8192 : 0);
   const int z = blockIdx.x, b = z / p.H, h = z - b * p.H;
   const int q0 = row0 + 32 * (int)blockIdx.y, qi = q0 + l31;
   const int nkt = w.Tp >> 6;
   const long rmz = (long)(w.Tp >> 5) * 8192, trz = (long)w.Tp * 256;
   const unsigned lane16 = lane * 16;
   const char* ksrc = w.k_rm + z * rmz + lane16;
-  const char* vsrc = w.v_tr + z * trz + lane16;
+  const char* vsrc = RM ? w.v_rm + z * rmz : w.v_tr + z * trz + lane16;
   // (the wave's own Q fragments are re-read per tile -- 8 KiB, cache-resident -- instead of held: the kernel keeps to 128
   //  registers so that a wave fits beside the two resident waves per SIMD of the main grid)
   const char* qs = w.q_rm + z * rmz + (long)(q0 >> 5) * 8192 + lane16;
@@ -739,6 +877,7 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
     const char* Ks = ksrc + (long)kt * 16384;
     const char* Vt = vsrc + (long)kt * 16384;
     const bool last = kt == nkt - 1, half = last && short_last;
+    if constexpr (RM) tail_stage(Vt, tl, stw_a);     // keys 0..31 of the tile
     f32x16 s0, s1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
@@ -792,8 +931,15 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
       }
       f16x8 pb[2], a0[2], a1[2];
       split2x8<MIX>(x, pb);
-      frag2(a0, Vt + ((tp * 2) * 2) * 1024);
-      frag2(a1, Vt + ((tp * 2 + 1) * 2) * 1024);
+      if constexpr (RM) {
+        if (tp == 2) tail_stage(Vt + 8192, tl, stw_a);   // keys 32..63
+        if (tp == 0 || tp == 2) wait_vm<0>();
+        frag2_tr(a0, st0, st1, tp & 1, 0);
+        frag2_tr(a1, st0, st1, tp & 1, 1);
+      } else {
+        frag2(a0, Vt + ((tp * 2) * 2) * 1024);
+        frag2(a1, Vt + ((tp * 2 + 1) * 2) * 1024);
+      }
       H2_PAIR(o0, a0, o1, a1, pb)
     }
     l += sum;
@@ -845,10 +991,16 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
-template <bool MIX>
+template <bool MIX, bool RM>
 __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_dq_tail_h2_kernel(const AttnP p, const H2W w, int row0) {
+  __shared__ __attribute__((aligned(1024))) char stg[RM ? TAILW * 8192 : 16];
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const TrLane tl = tr_lane(lane);
+  const char* stw = stg + (RM ? wave * 8192 : 0);
+  const lchar* st0 = RM ? tr_base(stw, tl.tr[0]) : nullptr;
+  const lchar* st1 = RM ? tr_base(stw, tl.tr[1]) : nullptr;
+  const unsigned stw_a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)stg + (RM ? wave * 8192 : 0);
   const int z = blockIdx.x, b = z / p.H, h = z - b * p.H;
   const int q0 = row0 + 32 * (int)blockIdx.y, qi = q0 + l31;
   const int nkt = w.Tp >> 6;
@@ -856,7 +1008,7 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
   const unsigned lane16 = lane * 16;
   const char* k_rm = w.k_rm + z * rmz + lane16;
   const char* v_rm = w.v_rm + z * rmz + lane16;
-  const char* k_tr = w.k_tr + z * trz + lane16;
+  const char* k_tr = RM ? w.k_rm + z * rmz : w.k_tr + z * trz + lane16;     // (RM: the row-major set, staged per 32-key block)
   const char* qs = w.q_rm + z * rmz + (long)(q0 >> 5) * 8192 + lane16;      // (re-read per tile, see the forward)
   const char* os = w.do_rm + z * rmz + (long)(q0 >> 5) * 8192 + lane16;
   const float2 ad = *reinterpret_cast<const float2*>(w.ld + ((long)z * w.Tp + min(qi, w.Tp - 1)) * 2);
@@ -876,6 +1028,7 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt) {
       if (!last || jt == 0 || p.T - kt * 64 > 32) {
+        if constexpr (RM) tail_stage(Kt + jt * 8192, tl, stw_a);
         f32x16 sa, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sa[r] = 0.f; dp[r] = 0.f; }
@@ -914,8 +1067,14 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
             x[j] = __builtin_amdgcn_exp2f(fmaf(sa[8 * t + j], c, a_i)) * fmaf(dp[8 * t + j], cdp, -d_i);
           f16x8 pb[2], a0[2], a1[2];
           split2x8<MIX>(x, pb);
-          frag2(a0, Kt + (((2 * jt + t) * 2) * 2) * 1024);
-          frag2(a1, Kt + (((2 * jt + t) * 2 + 1) * 2) * 1024);
+          if constexpr (RM) {
+            if (t == 0) wait_vm<0>();
+            frag2_tr(a0, st0, st1, t, 0);
+            frag2_tr(a1, st0, st1, t, 1);
+          } else {
+            frag2(a0, Kt + (((2 * jt + t) * 2) * 2) * 1024);
+            frag2(a1, Kt + (((2 * jt + t) * 2 + 1) * 2) * 1024);
+          }
           H2_PAIR(dq0, a0, dq1, a1, pb)
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -950,10 +1109,16 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
-template <bool MIX>
+template <bool MIX, bool RM>
 __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_dkv_tail_h2_kernel(const AttnP p, const H2W w, int row0) {
+  __shared__ __attribute__((aligned(1024))) char stg[RM ? TAILW * 8192 : 16];
   const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const TrLane tl = tr_lane(lane);
+  const char* stw = stg + (RM ? wave * 8192 : 0);
+  const lchar* st0 = RM ? tr_base(stw, tl.tr[0]) : nullptr;
+  const lchar* st1 = RM ? tr_base(stw, tl.tr[1]) : nullptr;
+  const unsigned stw_a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)stg + (RM ? wave * 8192 : 0);
   const int z = blockIdx.x, b = z / p.H, h = z - b * p.H;
   const int k0 = row0 + 32 * (int)blockIdx.y;
   const int nqt = (p.T + 31) >> 5;
@@ -962,8 +1127,8 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
   // (wave-uniform bases + the 32-bit lane offset at every use: scalar base / vector offset addressing, no 64-bit pointer pairs)
   const char* q_rm = w.q_rm + z * rmz;
   const char* o_rm = w.do_rm + z * rmz;
-  const char* q_tr = w.q_tr + z * trz;
-  const char* o_tr = w.do_tr + z * trz;
+  const char* q_tr = RM ? nullptr : w.q_tr + z * trz;
+  const char* o_tr = RM ? nullptr : w.do_tr + z * trz;
   const float* ldz = w.ld + (long)z * w.Tp * 2;
   const char* ks = w.k_rm + z * rmz + (long)(k0 >> 5) * 8192;      // (re-read per tile, see the forward)
   const char* vs = w.v_rm + z * rmz + (long)(k0 >> 5) * 8192;
@@ -980,6 +1145,7 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
     const char* Qt = q_tr + (long)qt * 8192;
     const char* Ot = o_tr + (long)qt * 8192;
     const float* LD = ldz + qt * 64;
+    if constexpr (RM) tail_stage(Os, tl, stw_a);       // dO's block first (dV), then Q's (dK) through the same 8 KiB
     f32x16 sa, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { sa[r] = 0.f; dp[r] = 0.f; }
@@ -1025,6 +1191,28 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
       split2x8<MIX>(xs, sa2[t]);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (RM) {     // (per accumulator the products and their order are those of the interleaved form below)
+      wait_vm<0>();
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f16x8 o0[2], o1[2];
+        frag2_tr(o0, st0, st1, t, 0);
+        frag2_tr(o1, st0, st1, t, 1);
+        H2_2(dv0, pa[t], o0, dv1, pa[t], o1)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      tail_stage(Qs, tl, stw_a);
+      wait_vm<0>();
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f16x8 q0f[2], q1f[2];
+        frag2_tr(q0f, st0, st1, t, 0);
+        frag2_tr(q1f, st0, st1, t, 1);
+        H2_2(dk0, sa2[t], q0f, dk1, sa2[t], q1f)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      continue;
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       f16x8 o0[2], o1[2], q0f[2], q1f[2];
@@ -1073,25 +1261,30 @@ __global__ __launch_bounds__(64 * TAILW) __attribute__((amdgpu_waves_per_eu(4, 4
 }
 
 // ------------------------------------------------------------------------------------------------ host
+// Workspace modes: 0 = forward, 1 = backward (packs all four tensors), 2 = backward on the forward's kept sets (packs dO only).
+// Row-major sets only (round 8): forward Q | K | V, backward Q | K | V | dO, mode 2 dO alone; then exps, nrm (and ld).  Under the
+// tr switch (SVL_ATTN_TR_SETS, the sequence of rounds 5-7): forward Q rm | K rm | V tr, backward + V rm, dO rm, Q tr, K tr, dO tr.
 struct Layout {
   long set;        // bytes of one operand set: B H Tp 256
   long exps, nrm, ld, total;
   int Tp;
 };
-Layout layout(int B, int T, int H, int backward) {
+Layout layout(int B, int T, int H, int mode, int tr) {
   Layout l;
   l.Tp = (T + 63) / 64 * 64;
   l.set = (long)B * H * l.Tp * 256;
-  const long nset = backward ? 7 : 3;
+  const long nset = mode == 0 ? 3 : mode == 2 ? 1 : tr ? 7 : 4;
   l.exps = nset * l.set;
   l.nrm = l.exps + (((long)B * H * 16 + 1023) & ~1023L);
   l.ld = l.nrm + (((long)B * H * 16 + 1023) & ~1023L);
-  l.total = l.ld + (backward ? (((long)B * H * l.Tp * 8 + 1023) & ~1023L) + 1024 : 0);
+  l.total = l.ld + (mode ? (((long)B * H * l.Tp * 8 + 1023) & ~1023L) + 1024 : 0);
   return l;
 }
 
+std::atomic<int> g_tr{-1};     // the tr switch: -1 = not yet taken from the environment
+
 // (rounds 5's A/B variants -- the split without v_fma_mix, the forward with a half-tile skew between its wave groups -- measured
-//  slower and were retired in round 6: one instantiation per kernel, V = 3)
+//  slower and were retired in round 6: per kernel V = 3 on the tr sets and V = 7 on row-major sets only)
 template <typename K>
 int set_lds(K kernel, std::atomic<uint64_t>& mask, int bytes) {   // per device, the bit set only after the call succeeded
   int dev = 0;
@@ -1103,20 +1296,32 @@ int set_lds(K kernel, std::atomic<uint64_t>& mask, int bytes) {   // per device,
   return SVL_OK;
 }
 
-H2W views(const Layout& l, char* ws, int backward) {
+// `sets`: the kept forward workspace of mode 2 (its Q | K | V row-major sets are read in place)
+H2W views(const Layout& l, char* ws, int mode, int tr, const char* sets = nullptr) {
   H2W w;
   memset(&w, 0, sizeof(w));
   w.Tp = l.Tp;
-  w.q_rm = ws;
-  w.k_rm = ws + l.set;
-  if (backward) {
-    w.v_rm = ws + 2 * l.set;
-    w.do_rm = ws + 3 * l.set;
-    w.q_tr = ws + 4 * l.set;
-    w.k_tr = ws + 5 * l.set;
-    w.do_tr = ws + 6 * l.set;
+  if (mode == 2) {
+    w.q_rm = sets;
+    w.k_rm = sets + l.set;
+    w.v_rm = sets + 2 * l.set;
+    w.do_rm = ws;
   } else {
-    w.v_tr = ws + 2 * l.set;
+    w.q_rm = ws;
+    w.k_rm = ws + l.set;
+    if (mode == 1) {
+      w.v_rm = ws + 2 * l.set;
+      w.do_rm = ws + 3 * l.set;
+      if (tr) {
+        w.q_tr = ws + 4 * l.set;
+        w.k_tr = ws + 5 * l.set;
+        w.do_tr = ws + 6 * l.set;
+      }
+    } else if (tr) {
+      w.v_tr = ws + 2 * l.set;
+    } else {
+      w.v_rm = ws + 2 * l.set;
+    }
   }
   w.exps = reinterpret_cast<const int*>(ws + l.exps);
   w.nrm = reinterpret_cast<const float*>(ws + l.nrm);
@@ -1124,8 +1329,8 @@ H2W views(const Layout& l, char* ws, int backward) {
   return w;
 }
 
-int check_ws(const AttnP& p, const void* ws, long wsb, int backward, const char* who) {
-  const Layout l = layout(p.B, p.T, p.H, backward);
+int check_ws(const AttnP& p, const void* ws, long wsb, int mode, int tr, const char* who) {
+  const Layout l = layout(p.B, p.T, p.H, mode, tr);
   SVL_CHECK_ARG(ws && ((uintptr_t)ws & 1023) == 0 && wsb >= l.total, "%s: workspace of %ld bytes (1 KiB aligned) needed, got %ld",
                 who, l.total, wsb);
   return SVL_OK;
@@ -1135,14 +1340,26 @@ int check_ws(const AttnP& p, const void* ws, long wsb, int backward, const char*
 
 namespace svl_attn_h2 {
 
-long ws_bytes(int B, int T, int H, int backward) { return layout(B, T, H, backward).total; }
+int tr_sets(int on) {
+  int cur = g_tr.load(std::memory_order_acquire);
+  if (cur < 0) {
+    const char* e = getenv("SVL_ATTN_TR_SETS");
+    int expect = -1;
+    g_tr.compare_exchange_strong(expect, e && *e && *e != '0' ? 1 : 0);
+    cur = g_tr.load(std::memory_order_acquire);
+  }
+  if (on >= 0) g_tr.store(on ? 1 : 0, std::memory_order_release);
+  return cur;
+}
 
-int fwd_pack(const AttnP& p, void* ws_, long wsb, hipStream_t st) {
-  int rc = check_ws(p, ws_, wsb, 0, "svl_attention_fwd_h2");
+long ws_bytes(int B, int T, int H, int mode, int tr) { return layout(B, T, H, mode, tr).total; }
+
+int fwd_pack(const AttnP& p, void* ws_, long wsb, int tr, hipStream_t st) {
+  int rc = check_ws(p, ws_, wsb, 0, tr, "svl_attention_fwd_h2");
   if (rc) return rc;
-  const Layout l = layout(p.B, p.T, p.H, 0);
+  const Layout l = layout(p.B, p.T, p.H, 0, tr);
   char* ws = static_cast<char*>(ws_);
-  const H2W w = views(l, ws, 0);
+  const H2W w = views(l, ws, 0, tr);
   PackP q;
   memset(&q, 0, sizeof(q));
   for (int i = 0; i < 3; ++i) {
@@ -1152,6 +1369,7 @@ int fwd_pack(const AttnP& p, void* ws_, long wsb, hipStream_t st) {
   }
   q.rm[0] = const_cast<char*>(w.q_rm);
   q.rm[1] = const_cast<char*>(w.k_rm);
+  q.rm[2] = const_cast<char*>(w.v_rm);      // (null under the tr switch, and v_tr null without it)
   q.tr[2] = const_cast<char*>(w.v_tr);
   q.exps = const_cast<int*>(w.exps);
   q.nrm = const_cast<float*>(w.nrm);
@@ -1161,30 +1379,44 @@ int fwd_pack(const AttnP& p, void* ws_, long wsb, hipStream_t st) {
   return SVL_OK;
 }
 
-#define SVL_LAUNCH_V(KERN, LDS)                                       \
-    rc = set_lds(KERN<3>, mask, LDS);                                   \
+#define SVL_LAUNCH_V(KERN, VV, LDS)                                   \
+    rc = set_lds(KERN<VV>, mask, LDS);                                  \
     if (rc) return rc;                                                  \
-    hipLaunchKernelGGL(KERN<3>, grid, dim3(512), LDS, st, p, w);
+    hipLaunchKernelGGL(KERN<VV>, grid, dim3(512), LDS, st, p, w);
 
-int fwd(const AttnP& p, int nb, void* ws_, long wsb, hipStream_t st) {   // the MFMA grid over `nb` blocks per (image, head)
+int fwd(const AttnP& p, int nb, void* ws_, long wsb, int tr, hipStream_t st) {   // the MFMA grid over `nb` blocks per (image, head)
   (void)wsb;
   if (nb <= 0) return SVL_OK;
-  const Layout l = layout(p.B, p.T, p.H, 0);
-  const H2W w = views(l, static_cast<char*>(ws_), 0);
+  const Layout l = layout(p.B, p.T, p.H, 0, tr);
+  const H2W w = views(l, static_cast<char*>(ws_), 0, tr);
   int rc = SVL_OK;
-  static std::atomic<uint64_t> mask;
   const dim3 grid(nb * p.B * p.H);
-  SVL_LAUNCH_V(attn_fwd_h2_kernel, 3 * STG_F)
+  if (tr) {
+    static std::atomic<uint64_t> mask;
+    SVL_LAUNCH_V(attn_fwd_h2_kernel, 3, 3 * STG_F)
+  } else {
+    static std::atomic<uint64_t> mask;
+    SVL_LAUNCH_V(attn_fwd_h2_kernel, 7, 3 * STG_F)
+  }
   SVL_LAUNCH_CHECK("svl_attention_fwd_h2");
   return SVL_OK;
 }
 
-int bwd_prepare(const AttnP& p, const float* out, float* dsum_ws, void* ws_, long wsb, hipStream_t st) {
-  int rc = check_ws(p, ws_, wsb, 1, "svl_attention_bwd_h2");
+// mode 1: packs q, k, v, dO; mode 2 (`sets` = the workspace the forward of the same qkv left, row-major sets only): packs dO
+// alone and takes the three exponents and norms from `sets`
+int bwd_prepare(const AttnP& p, const float* out, float* dsum_ws, void* ws_, long wsb, const void* sets, long setsb, int tr,
+                hipStream_t st) {
+  const int mode = sets ? 2 : 1;
+  int rc = check_ws(p, ws_, wsb, mode, tr, "svl_attention_bwd_h2");
   if (rc) return rc;
-  const Layout l = layout(p.B, p.T, p.H, 1);
+  if (sets) {
+    SVL_CHECK_ARG(!tr, "svl_attention_bwd_h2_sets: kept sets are row-major sets only (the tr switch is on)");
+    rc = check_ws(p, sets, setsb, 0, 0, "svl_attention_bwd_h2_sets (sets)");
+    if (rc) return rc;
+  }
+  const Layout l = layout(p.B, p.T, p.H, mode, tr);
   char* ws = static_cast<char*>(ws_);
-  const H2W w = views(l, ws, 1);
+  const H2W w = views(l, ws, mode, tr, static_cast<const char*>(sets));
   PackP q;
   memset(&q, 0, sizeof(q));
   for (int i = 0; i < 3; ++i) {
@@ -1193,18 +1425,25 @@ int bwd_prepare(const AttnP& p, const float* out, float* dsum_ws, void* ws_, lon
   }
   q.src[3] = p.dout;
   q.ld[3] = p.E;
-  for (int i = 0; i < 4; ++i) q.which[i] = i;
-  q.rm[0] = const_cast<char*>(w.q_rm);
-  q.rm[1] = const_cast<char*>(w.k_rm);
-  q.rm[2] = const_cast<char*>(w.v_rm);
   q.rm[3] = const_cast<char*>(w.do_rm);
-  q.tr[0] = const_cast<char*>(w.q_tr);
-  q.tr[1] = const_cast<char*>(w.k_tr);
   q.tr[3] = const_cast<char*>(w.do_tr);
+  if (sets) {
+    const Layout lf = layout(p.B, p.T, p.H, 0, 0);
+    q.which[0] = 3;
+    q.exps_in = reinterpret_cast<const int*>(static_cast<const char*>(sets) + lf.exps);
+    q.nrm_in = reinterpret_cast<const float*>(static_cast<const char*>(sets) + lf.nrm);
+  } else {
+    for (int i = 0; i < 4; ++i) q.which[i] = i;
+    q.rm[0] = const_cast<char*>(w.q_rm);
+    q.rm[1] = const_cast<char*>(w.k_rm);
+    q.rm[2] = const_cast<char*>(w.v_rm);
+    q.tr[0] = const_cast<char*>(w.q_tr);
+    q.tr[1] = const_cast<char*>(w.k_tr);
+  }
   q.exps = const_cast<int*>(w.exps);
   q.nrm = const_cast<float*>(w.nrm);
   q.B = p.B; q.T = p.T; q.H = p.H; q.Tp = l.Tp;
-  hipLaunchKernelGGL(attn_pack_kernel, dim3(p.B * p.H, 4), dim3(256), 0, st, q);
+  hipLaunchKernelGGL(attn_pack_kernel, dim3(p.B * p.H, sets ? 1 : 4), dim3(256), 0, st, q);
   SVL_LAUNCH_CHECK("svl_attention_bwd_h2/pack");
   const long groups = (long)p.B * p.H * l.Tp;
   hipLaunchKernelGGL(attn_ld_kernel, dim3((unsigned)((groups * 16 + 255) / 256)), dim3(256), 0, st, p.dout, out, p.lse, w.nrm,
@@ -1214,41 +1453,55 @@ int bwd_prepare(const AttnP& p, const float* out, float* dsum_ws, void* ws_, lon
 }
 
 // the leftover rows [row0, T) (at most 4: one 32-row tile) beside the main grid: `aux` = the caller's helper stream
-int fwd_tail(const AttnP& p, int row0, void* ws_, hipStream_t aux) {
-  const Layout l = layout(p.B, p.T, p.H, 0);
-  const H2W w = views(l, static_cast<char*>(ws_), 0);
+int fwd_tail(const AttnP& p, int row0, void* ws_, int tr, hipStream_t aux) {
+  const Layout l = layout(p.B, p.T, p.H, 0, tr);
+  const H2W w = views(l, static_cast<char*>(ws_), 0, tr);
   const dim3 grid(p.B * p.H, (p.T - row0 + 31) / 32);
-  hipLaunchKernelGGL(attn_fwd_tail_h2_kernel<true>, grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+  if (tr) hipLaunchKernelGGL((attn_fwd_tail_h2_kernel<true, false>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+  else hipLaunchKernelGGL((attn_fwd_tail_h2_kernel<true, true>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
   SVL_LAUNCH_CHECK("svl_attention_fwd_h2/tail");
   return SVL_OK;
 }
 
-int bwd_tail(const AttnP& p, int row0, void* ws_, hipStream_t aux) {
-  const Layout l = layout(p.B, p.T, p.H, 1);
-  const H2W w = views(l, static_cast<char*>(ws_), 1);
+int bwd_tail(const AttnP& p, int row0, void* ws_, const void* sets, int tr, hipStream_t aux) {
+  const int mode = sets ? 2 : 1;
+  const Layout l = layout(p.B, p.T, p.H, mode, tr);
+  const H2W w = views(l, static_cast<char*>(ws_), mode, tr, static_cast<const char*>(sets));
   const dim3 grid(p.B * p.H, (p.T - row0 + 31) / 32);
-  hipLaunchKernelGGL(attn_dkv_tail_h2_kernel<true>, grid, dim3(64 * TAILW), 0, aux, p, w, row0);
-  hipLaunchKernelGGL(attn_dq_tail_h2_kernel<true>, grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+  if (tr) {
+    hipLaunchKernelGGL((attn_dkv_tail_h2_kernel<true, false>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+    hipLaunchKernelGGL((attn_dq_tail_h2_kernel<true, false>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+  } else {
+    hipLaunchKernelGGL((attn_dkv_tail_h2_kernel<true, true>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+    hipLaunchKernelGGL((attn_dq_tail_h2_kernel<true, true>), grid, dim3(64 * TAILW), 0, aux, p, w, row0);
+  }
   SVL_LAUNCH_CHECK("svl_attention_bwd_h2/tail");
   return SVL_OK;
 }
 
-int bwd_main(const AttnP& p, int nb, void* ws_, hipStream_t st) {
+int bwd_main(const AttnP& p, int nb, void* ws_, const void* sets, int tr, hipStream_t st) {
   if (nb <= 0) return SVL_OK;
-  const Layout l = layout(p.B, p.T, p.H, 1);
-  const H2W w = views(l, static_cast<char*>(ws_), 1);
+  const int mode = sets ? 2 : 1;
+  const Layout l = layout(p.B, p.T, p.H, mode, tr);
+  const H2W w = views(l, static_cast<char*>(ws_), mode, tr, static_cast<const char*>(sets));
   int rc = SVL_OK;
   const dim3 grid(nb * p.B * p.H);
-  {
+  if (tr) {
     static std::atomic<uint64_t> mask;
-    SVL_LAUNCH_V(attn_dkv_h2_kernel, 3 * STG_K)
-    SVL_LAUNCH_CHECK("svl_attention_bwd_h2/dkv");
-  }
-  {
+    SVL_LAUNCH_V(attn_dkv_h2_kernel, 3, 3 * STG_K)
+  } else {
     static std::atomic<uint64_t> mask;
-    SVL_LAUNCH_V(attn_dq_h2_kernel, 3 * STG_Q)
-    SVL_LAUNCH_CHECK("svl_attention_bwd_h2/dq");
+    SVL_LAUNCH_V(attn_dkv_h2_kernel, 7, 3 * STG_K_RM)
   }
+  SVL_LAUNCH_CHECK("svl_attention_bwd_h2/dkv");
+  if (tr) {
+    static std::atomic<uint64_t> mask;
+    SVL_LAUNCH_V(attn_dq_h2_kernel, 3, 3 * STG_Q)
+  } else {
+    static std::atomic<uint64_t> mask;
+    SVL_LAUNCH_V(attn_dq_h2_kernel, 7, 3 * STG_Q_RM)
+  }
+  SVL_LAUNCH_CHECK("svl_attention_bwd_h2/dq");
   return SVL_OK;
 }
 

@@ -177,6 +177,8 @@ SIGNATURES = {
     "svl_attention_h2_ws_bytes": (_L, [_I, _I, _I, _I]),
     "svl_attention_fwd_h2": (_I, [_P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P]),
     "svl_attention_bwd_h2": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P]),
+    "svl_attention_h2_tr_sets": (_I, [_I]),
+    "svl_attention_bwd_h2_sets": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P]),
     "svl_conv_cout1_fwd": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "svl_conv_cout1_wgrad_blocks": (_I, [_I, _I, _I]),
     "svl_conv_cout1_wgrad": (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -130,15 +130,18 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
         if D == 64 and pp and ops.attention_planes_ok():
             # the kernel's epilogue emits the output as planes (the out-projection's A operand); its fp32 copy is only
             # kept for backward (dsum, out_proj weight gradient)
-            o, P, o_p = ops.attention_fwd(qkv, Bn, T, heads, want_lse=save is not None, planes=True, want_out=save is not None)
+            # (a pass that saves for backward also keeps the packed Q | K | V operand sets: the backward then packs dO alone)
+            o, P, o_p, *sets = ops.attention_fwd(qkv, Bn, T, heads, want_lse=save is not None, planes=True,
+                                                 want_out=save is not None, keep_sets=save is not None)
         elif D == 64:
-            o, P = ops.attention_fwd(qkv, Bn, T, heads, want_lse=save is not None)  # P := log-sum-exp rows
+            o, P, *sets = ops.attention_fwd(qkv, Bn, T, heads, want_lse=save is not None, keep_sets=save is not None)  # P := log-sum-exp rows
         else:  # generic head dim: batched-GEMM attention with materialised probabilities
             o, P = ops.vit_attention_fwd(qkv, Bn, T, heads, D)
+            sets = []
         x2 = ops.linear(o_p if o_p is not None else (ops.split_planes(o) if pp else o), p["wout"], p["bout"], resid=x)
         xo, st2, h_pre = ffn(x2, save is not None)
         if save is not None:
-            save.update(o=o, P=P, x2=x2, st2=st2, h_pre=h_pre)
+            save.update(o=o, P=P, x2=x2, st2=st2, h_pre=h_pre, sets=sets[0] if sets else None)
     return xo, v
 
 
@@ -191,10 +194,10 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
         wout_parts.append((dx2, s["o"]))
         if D == 64 and pp and ops.attention_planes_ok() and not (s["want_v"] and dv is not None):
             # dqkv also as planes (in_proj's input-gradient GEMM), from the two kernels' epilogues
-            dqkv, dqkv_p = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads, planes=True)
+            dqkv, dqkv_p = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads, planes=True, sets=s.get("sets"))
             dqkv_amax = dqkv_p.amax
         elif D == 64:
-            dqkv = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads)
+            dqkv = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads, sets=s.get("sets"))
         else:
             dqkv = ops.vit_attention_bwd(do, s["qkv"], s["P"], Bn, T, heads, D)
         dx_res = dx2

@@ -978,47 +978,65 @@ def attention_planes_ok():
 
 
 def _attn_ws(Bn, T, H, backward, dev):
-    n = L.load().svl_attention_h2_ws_bytes(Bn, T, H, 1 if backward else 0)
+    n = L.load().svl_attention_h2_ws_bytes(Bn, T, H, int(backward))
     return torch.empty(n + 1024, dtype=torch.uint8, device=dev), n
+
+
+def attention_tr_sets(on=None):
+    """The operand-set switch of the fp16 x 2 attention (SVL_ATTN_TR_SETS=1 in the environment, or here per process):
+    True restores the sequence of rounds 5-7 -- transposed operand sets packed and read, the backward packs q, k, v again --
+    for A/B runs; same bits either way.  Returns the value that held before; on=None only queries."""
+    return bool(L.load().svl_attention_h2_tr_sets(-1 if on is None else int(bool(on))))
 
 
 def _ws_ptr(ws):
     return (ws.data_ptr() + 1023) // 1024 * 1024
 
 
-def attention_fwd(qkv, Bn, T, H, want_lse=True, planes=False, want_out=True):
+def attention_fwd(qkv, Bn, T, H, want_lse=True, planes=False, want_out=True, keep_sets=False):
     """Flash-style fused attention: qkv [Bn*T, 3E] -> (out [Bn*T, E] or None, lse [Bn*H*T] or None[, out as Planes]).
     planes=True (attention_planes_ok()) additionally returns the output as packed planes -- 38 us at [32800, 768] for the
     pack pass, less than what the out-projection saves on fp16 x 2 operands; want_out=False then drops the fp32 copy
-    (gradient-free passes)."""
+    (gradient-free passes).
+    keep_sets=True appends the call's operand workspace (the packed Q | K | V sets: attention_bwd's `sets`), or None where there
+    is none to keep (exact fp32 kernels, attention_tr_sets())."""
     E = H * 64
     if planes and not attention_planes_ok():
         raise RuntimeError("attention_fwd: planes outputs need emulation mode 6 (attention_planes_ok())")
     out = empty(Bn * T, E, device=qkv.device)
     lse = empty(Bn * H * T, device=qkv.device) if want_lse else None
     e0 = _prof_begin()
+    sets = None
     if attention_h2():
-        ws, n = _attn_ws(Bn, T, H, False, qkv.device)
+        ws, n = _attn_ws(Bn, T, H, 0, qkv.device)
         L.check(L.load().svl_attention_fwd_h2(_p(qkv), Bn, T, H, _p(out), _p(lse), None, 0, _ws_ptr(ws), n, _st()),
                 "svl_attention_fwd_h2")
+        if keep_sets and not attention_tr_sets():
+            sets = ws
     else:
         L.check(L.load().svl_attention_fwd(_p(qkv), Bn, T, H, _p(out), _p(lse), None, 0, _st()), "svl_attention_fwd")
     _prof_end(_attn_family(), e0, 4.0 * Bn * H * T * T * 64, ("fwd_h2" if attention_h2() else "fwd", Bn, T, H))
     if not planes:
-        return out, lse
+        return (out, lse, sets) if keep_sets else (out, lse)
     op = split_planes(out)
-    return (out if want_out else None), lse, op
+    return ((out if want_out else None), lse, op) + ((sets,) if keep_sets else ())
 
 
-def attention_bwd(dout, qkv, out, lse, Bn, T, H, planes=False):
-    """-> dqkv [Bn*T, 3E] (and, with planes=True, the same as Planes through the generic pack pass)."""
+def attention_bwd(dout, qkv, out, lse, Bn, T, H, planes=False, sets=None):
+    """-> dqkv [Bn*T, 3E] (and, with planes=True, the same as Planes through the generic pack pass).
+    sets: what attention_fwd(..., keep_sets=True) of the same qkv returned -- the backward then packs dout alone (same bits)."""
     if planes and not attention_planes_ok():
         raise RuntimeError("attention_bwd: planes outputs need emulation mode 6 (attention_planes_ok())")
     dqkv = torch.empty_like(qkv)
     ws = empty(Bn * H * T, device=qkv.device)
     e0 = _prof_begin()
-    if attention_h2():
-        wsb, n = _attn_ws(Bn, T, H, True, qkv.device)
+    if attention_h2() and sets is not None and not attention_tr_sets():
+        wsb, n = _attn_ws(Bn, T, H, 2, qkv.device)
+        L.check(L.load().svl_attention_bwd_h2_sets(_p(qkv), _p(out), _p(dout), _p(lse), Bn, T, H, _p(ws), _p(dqkv), _ws_ptr(sets),
+                                                   sets.numel() - (_ws_ptr(sets) - sets.data_ptr()), _ws_ptr(wsb), n, _st()),
+                "svl_attention_bwd_h2_sets")
+    elif attention_h2():
+        wsb, n = _attn_ws(Bn, T, H, 1, qkv.device)
         L.check(L.load().svl_attention_bwd_h2(_p(qkv), _p(out), _p(dout), _p(lse), Bn, T, H, _p(ws), _p(dqkv), None, 0,
                                               _ws_ptr(wsb), n, _st()), "svl_attention_bwd_h2")
     else:
