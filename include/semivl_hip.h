@@ -812,6 +812,26 @@ int svl_aug_photometric_u8(unsigned char* img, int npix, int op, float factor, u
 int svl_aug_gaussian_blur_u8(const unsigned char* src, int H, int W, float sigma, unsigned char* tmp, unsigned char* dst,
                              svl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * LoRA adapters of the CLIP ViT as merged weights (model/backbone/lora.py; maskclip_vit.py:85-88,123-137).  With
+ * lora_dropout == 0, F.linear(x, W) + s * b(a(x)) == F.linear(x, W + s * B @ A) for A = a.weight [r, E], B = b.weight
+ * [rows, r]: a LoRA block runs the ordinary kernels on the effective weight.  fp32 throughout; 1 <= r <= 64, E % 4 == 0,
+ * every E-wide matrix 16-byte aligned with a leading dimension % 4 == 0; anything else (or a null pointer) is
+ * SVL_ERR_INVALID_ARG and nothing is written.  No atomics: results are bitwise reproducible.
+ *   svl_lora_merge_f32   row block i < nblk (<= 3) of W / Weff is rows [i * rows, (i + 1) * rows):
+ *                        Weff[i] = W[i] + s * B[i] @ A[i].  A, B: HOST arrays of nblk device pointers; a block with
+ *                        A[i] == B[i] == NULL is a plain copy (the k rows of in_proj under lora_targets='qv').
+ *                        One read of W, one write of Weff.
+ *   svl_lora_wgrad_f32   from one dW [rows, E] block: dB [rows, r] (+)= s * dW @ A^T and dA [r, E] (+)= s * B^T @ dW, one
+ *                        read of dW for both.  dB: one fp32 chain over E per element.  dA: a 16-row fp32 chain per row tile
+ *                        into ws (svl_lora_wgrad_ws_floats(rows, E, r) floats), then the tiles in order in double
+ *                        (svl_reduce_slabs_f32, launched here).  Each result has its own accumulate flag. */
+int svl_lora_merge_f32(const float* W, int64_t ldw, float* Weff, int64_t ldo, int nblk, int rows, int E, int r, float s,
+                       const float* const* A, const float* const* B, int64_t ldb, svl_stream_t stream);
+int64_t svl_lora_wgrad_ws_floats(int rows, int E, int r);
+int svl_lora_wgrad_f32(const float* dW, int64_t lddw, const float* A, const float* B, int64_t ldb, int rows, int E, int r,
+                       float s, float* dB, int accumulate_b, float* dA, int accumulate_a, float* ws, svl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,11 @@
 
 Mirror of `MaskClipVisionTransformer` / `TransformerEncoderLayer`
 (/root/reference third_party/maskclip/models/backbones/maskclip_vit.py:29-144,147-603) for the configurations on
-the SemiVL hot path (pre_norm, final_norm, return_clip_embed, return_qkv=True, no LoRA / prompt tokens), with the
-same constructor kwargs and the same `state_dict` key schema.
+the SemiVL hot path (pre_norm, final_norm, return_clip_embed, return_qkv=True, no prompt tokens), with the
+same constructor kwargs and the same `state_dict` key schema.  LoRA adapters (`lora_layers`,
+model/backbone/lora.py) run as MERGED weights: with lora_dropout == 0 the adapter is linear in the projection's own input,
+so a block with adapters runs the same kernels on W + s * B @ A (ops.lora_merge) and its adapters' gradients are projected
+out of the projection's weight gradient (ops.lora_wgrad).
 
 The whole forward AND backward of the encoder is hand-scheduled over libsemivl_hip.so (one autograd.Function for
 the region): tokens stay in [B*T, C] row-major, attention/FFN/LN backward are explicit kernel sequences, weight
@@ -47,14 +50,42 @@ class _FFNParams(nn.Module):
                                     nn.Linear(hidden, dims), nn.Identity())
 
 
-class TransformerEncoderLayer(nn.Module):
-    """Parameter container with the reference's names: ln1, attn.attn.{in_proj_*,out_proj}, ln2, ffn.layers.{0.0,1}."""
+class _LoRAParams(nn.Module):
+    """model/backbone/lora.py:21-57: a_<t> / b_<t> (bias-free Linears, a before b, q k v o) for each t in `targets`;
+    kaiming_uniform_(a=sqrt(5)) for a_*, zeros for b_*."""
 
-    def __init__(self, embed_dims, num_heads, feedforward_channels, eps=1e-5):
+    def __init__(self, dim, r, scaling=1., targets="qkvo"):
+        super().__init__()
+        self.dim, self.r, self.scaling, self.targets = dim, r, float(scaling), targets
+        for t in "qkvo":
+            if t in targets:
+                setattr(self, "a_" + t, nn.Linear(dim, r, bias=False))
+                setattr(self, "b_" + t, nn.Linear(r, dim, bias=False))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for t in "qkvo":
+            if t in self.targets:
+                nn.init.kaiming_uniform_(getattr(self, "a_" + t).weight, a=math.sqrt(5))
+                nn.init.zeros_(getattr(self, "b_" + t).weight)
+
+    def pair(self, t):
+        """(A [r, E], B [E, r]) of target t, or None"""
+        if t not in self.targets:
+            return None
+        return getattr(self, "a_" + t).weight, getattr(self, "b_" + t).weight
+
+
+class TransformerEncoderLayer(nn.Module):
+    """Parameter container with the reference's names: ln1, attn.attn.{in_proj_*,out_proj}, [lora.{a,b}_{q,k,v,o}], ln2,
+    ffn.layers.{0.0,1} (registered in the reference's order, maskclip_vit.py:73-100)."""
+
+    def __init__(self, embed_dims, num_heads, feedforward_channels, eps=1e-5, lora=None):
         super().__init__()
         self.embed_dims, self.num_heads, self.eps = embed_dims, num_heads, eps
         self.ln1 = nn.LayerNorm(embed_dims, eps=eps)
         self.attn = _AttnParams(embed_dims)
+        self.lora = _LoRAParams(embed_dims, **lora) if lora is not None else None
         self.ln2 = nn.LayerNorm(embed_dims, eps=eps)
         self.ffn = _FFNParams(embed_dims, feedforward_channels)
 
@@ -63,6 +94,19 @@ class TransformerEncoderLayer(nn.Module):
         return dict(ln1w=self.ln1.weight, ln1b=self.ln1.bias, win=a.in_proj_weight, bin=a.in_proj_bias,
                     wout=a.out_proj.weight, bout=a.out_proj.bias, ln2w=self.ln2.weight, ln2b=self.ln2.bias,
                     w1=f[0][0].weight, b1=f[0][0].bias, w2=f[1].weight, b2=f[1].bias)
+
+    def merged_plist(self):
+        """plist() of a block with adapters: `win` / `wout` are the effective weights W + s * B @ A (plain tensors, not
+        parameters: built once per encoder call, kept by that call's backward).  The q | k | v row blocks of in_proj merge
+        in one launch; a block without a target is copied."""
+        lo, a, p = self.lora, self.attn.attn, self.plist()
+        pairs = [lo.pair(t) for t in "qkv"]
+        with torch.no_grad():
+            if any(pr is not None for pr in pairs):
+                p["win"] = ops.lora_merge(a.in_proj_weight, pairs, lo.scaling)
+            if "o" in lo.targets:
+                p["wout"] = ops.lora_merge(a.out_proj.weight, [lo.pair("o")], lo.scaling)
+        return p
 
 
 class _PatchEmbedParams(nn.Module):
@@ -260,6 +304,8 @@ def attn_wgrads(p_mod, g, E):
     Returns a dict name -> tensor|None (None when written into main_grad)."""
     a = p_mod.attn.attn
     out = {}
+    if p_mod.lora is not None:
+        return _lora_attn_wgrads(p_mod, g, E)
 
     def wout_fn(dst, acc):
         first = not acc
@@ -303,6 +349,83 @@ def attn_wgrads(p_mod, g, E):
     return out
 
 
+def _lora_attn_wgrads(p_mod, g, E):
+    """attn_wgrads for a block with adapters.  Each projection's weight gradient OF THIS BACKWARD CALL ALONE goes to a
+    scratch matrix dW_eff (never main_grad: the step runs the encoder backward twice and main_grad then holds both);
+    ops.lora_wgrad folds it into the adapters' sinks (dB = s dW_eff A^T, dA = s B^T dW_eff), and a base projection that
+    trains too adds the same scratch to its own sink.  A frozen base projection's sink is not touched.  out["lora"]:
+    id(adapter tensor) -> tensor|None (a v-only block: v and o; its q and k adapters get zeros, like the q | k rows of its
+    in_proj)."""
+    a, lo = p_mod.attn.attn, p_mod.lora
+    out = dict(win=None, bin=None, wout=None, bout=None, lora={})
+
+    def adapters(t, dW):
+        pr = lo.pair(t)
+        if pr is None or not (pr[0].requires_grad or pr[1].requires_grad):
+            return
+        dst = []
+        for prm in pr:
+            mg = getattr(prm, "main_grad", None)
+            dst.append((mg, True) if mg is not None else (ops.empty(*prm.shape, device=prm.device), False))
+        ops.lora_wgrad(dW, pr[0].detach(), pr[1].detach(), lo.scaling, out_b=dst[1][0], out_a=dst[0][0],
+                       accumulate_b=dst[1][1], accumulate_a=dst[0][1])
+        for prm, (t_, acc) in zip(pr, dst):
+            if prm.requires_grad:
+                out["lora"][id(prm)] = None if acc else t_
+
+    def base(prm, dW, row0=0):
+        """dW (rows [row0, row0 + dW.shape[0]) of prm's gradient, zero elsewhere) into prm's sink"""
+        mg = getattr(prm, "main_grad", None)
+        if mg is not None:
+            dst = mg[row0:row0 + dW.shape[0]]
+            ops.add(dst, dW, out=dst)
+            return None
+        if dW.shape[0] == prm.shape[0]:
+            return dW
+        full = ops.zeros(*prm.shape, device=prm.device)
+        ops.eltwise(4, dW, None, out=full[row0:row0 + dW.shape[0]])
+        return full
+
+    if g["wout_parts"]:
+        dWo = ops.empty(E, E, device=a.out_proj.weight.device)
+        for j, (dy, xin) in enumerate(g["wout_parts"]):
+            ops.matmul_tn(dy, xin, out=dWo, accumulate=j > 0)
+        adapters("o", dWo)
+        if a.out_proj.weight.requires_grad:
+            out["wout"] = base(a.out_proj.weight, dWo)
+        if a.out_proj.bias.requires_grad:
+            def bout_fn(dst, acc):
+                for j, (dy, _) in enumerate(g["wout_parts"]):
+                    ops.colsum(dy, out=dst, accumulate=acc or j > 0)
+            out["bout"] = sink_grad(a.out_proj.bias, bout_fn)
+    if "in_full" in g:
+        dqkv, y1, dq_amax, y1_amax = g["in_full"]
+        dWin = ops.matmul_tn(dqkv, y1, a_amax=dq_amax, b_amax=y1_amax)
+        for i, t in enumerate("qkv"):
+            adapters(t, dWin[i * E:(i + 1) * E])
+        if a.in_proj_weight.requires_grad:
+            out["win"] = base(a.in_proj_weight, dWin)
+        if a.in_proj_bias.requires_grad:
+            out["bin"] = sink_grad(a.in_proj_bias, lambda dst, acc: ops.colsum(dqkv, out=dst, accumulate=acc))
+    elif "in_v" in g:
+        dvp, y1 = g["in_v"]
+        dWv = ops.matmul_tn(dvp, y1)
+        adapters("v", dWv)
+        for t in "qk":      # the reference's v path adds their (unused) rows too: all-zero gradients, not absent ones
+            for prm in lo.pair(t) or ():
+                if prm.requires_grad and getattr(prm, "main_grad", None) is None:
+                    out["lora"][id(prm)] = ops.zeros(*prm.shape, device=prm.device)
+        if a.in_proj_weight.requires_grad:
+            out["win"] = base(a.in_proj_weight, dWv, 2 * E)
+        if a.in_proj_bias.requires_grad:
+            def bin_fn(dst, acc):
+                if not acc:
+                    ops.fill(dst, 0.0)
+                ops.colsum(dvp, out=dst[2 * E:], accumulate=acc)
+            out["bin"] = sink_grad(a.in_proj_bias, bin_fn)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ encoder
 class MaskClipVisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, patch_bias=True, in_channels=3, embed_dims=768, num_layers=12,
@@ -319,7 +442,7 @@ class MaskClipVisionTransformer(nn.Module):
         unsupported = dict(patch_bias=patch_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
                            drop_path_rate=drop_path_rate, patch_norm=patch_norm, skip_last_attn=skip_last_attn,
                            output_cls_token=output_cls_token, num_prompt_tokens=num_prompt_tokens,
-                           lora_layers=list(lora_layers))
+                           lora_dropout=lora_dropout if len(lora_layers) else 0)   # (the one part of LoRA that does not merge)
         bad = {k: v for k, v in unsupported.items() if v not in (False, 0, 0.0, None, [])}
         if bad or not (pre_norm and final_norm and return_clip_embed and with_cls_token and qkv_bias):
             raise NotImplementedError(f"MaskClipVisionTransformer (HIP): only the SemiVL hot-path configuration is "
@@ -340,8 +463,10 @@ class MaskClipVisionTransformer(nn.Module):
             self.out_indices = [num_layers - 1 if out_indices == -1 else out_indices]
         else:
             self.out_indices = list(out_indices)
-        self.layers = nn.ModuleList([TransformerEncoderLayer(embed_dims, num_heads, mlp_ratio * embed_dims, self.eps)
-                                     for _ in range(num_layers)])
+        lora = dict(r=lora_r, scaling=lora_scaling, targets=lora_targets)
+        self.layers = nn.ModuleList([TransformerEncoderLayer(embed_dims, num_heads, mlp_ratio * embed_dims, self.eps,
+                                                             lora=lora if i in lora_layers else None)
+                                     for i in range(num_layers)])
         self.ln0 = nn.LayerNorm(embed_dims, eps=self.eps)
         self.ln1 = nn.LayerNorm(embed_dims, eps=self.eps)
         self.proj = nn.Conv2d(embed_dims, 512, 1, bias=False)
@@ -383,13 +508,16 @@ class MaskClipVisionTransformer(nn.Module):
             if "proj.weight" in sd and sd["proj.weight"].dim() == 2:
                 sd["proj.weight"] = sd["proj.weight"][:, :, None, None]
             res = self.load_state_dict(sd, strict=False)
-            if res.missing_keys or res.unexpected_keys:
-                warnings.warn(f"{self.pretrained}: missing keys {res.missing_keys}, unexpected keys {res.unexpected_keys}")
+            missing = [k for k in res.missing_keys if ".lora." not in k]    # (adapters keep LoRA.reset_parameters' init)
+            if missing or res.unexpected_keys:
+                warnings.warn(f"{self.pretrained}: missing keys {missing}, unexpected keys {res.unexpected_keys}")
             return
         with torch.no_grad():
             nn.init.trunc_normal_(self.pos_embed, std=.02)
             nn.init.trunc_normal_(self.cls_token, std=.02)
             for n, m in self.named_modules():
+                if ".lora." in n:       # adapters keep LoRA.reset_parameters' init (b_* = 0: the model starts as its base)
+                    continue
                 if isinstance(m, nn.Linear):
                     nn.init.trunc_normal_(m.weight, std=.02)
                     if m.bias is not None:
@@ -425,6 +553,7 @@ class MaskClipVisionTransformer(nn.Module):
         ruled = self.__dict__.get("_ruled")
         if ruled is None:
             ruled = {id(t) for l_ in self.layers for t in l_.plist().values()}
+            ruled |= {id(t) for l_ in self.layers if l_.lora is not None for t in l_.lora.parameters()}
             ruled |= {id(t) for t in (self.ln0.weight, self.ln0.bias, self.ln1.weight, self.ln1.bias, self.cls_token,
                                       self.pos_embed, self.patch_embed.projection.weight, self.proj.weight)}
             self.__dict__["_ruled"] = ruled
@@ -511,8 +640,11 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         want_v = m.return_qkv[i]
         skip_x = last and not need_global
         sv = {} if saved is not None else None
-        xo, v = block_forward(x, layer.plist(), m.num_heads, m.eps, B, T, want_v, skip_x, sv)
+        pl = layer.plist() if layer.lora is None else layer.merged_plist()
+        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, T, want_v, skip_x, sv)
         if saved is not None:
+            if layer.lora is not None:
+                sv["plist"] = pl      # the backward's input-gradient GEMMs run on the same effective weights
             saved["layers"].append(sv)
         if i in m.out_indices:
             f = ops.empty(B * NP, E, device=dev)
@@ -642,7 +774,7 @@ class _EncoderFn(torch.autograd.Function):
             sv = s["layers"][i]
             pl = layer.plist()
             want = frozenset(k_ for k_ in FFN_LN_KEYS if pl[k_].requires_grad)
-            dx, dxp, g = block_backward(dx, dvs.get(i), pl, sv, m.num_heads, B, T, want=want, dxo_p=dxp)
+            dx, dxp, g = block_backward(dx, dvs.get(i), sv.get("plist", pl), sv, m.num_heads, B, T, want=want, dxo_p=dxp)
             # this block's weight gradients (two split-K GEMMs, their slab reductions, two column sums; with a trained FFN
             # two more GEMM families on B-operand producers) are off the dependency chain: they go to the weight-gradient
             # stream and run next to the chain's LayerNorm-backward / pack passes of the blocks below (ops.wgrad_side)
@@ -654,6 +786,7 @@ class _EncoderFn(torch.autograd.Function):
             a = layer.attn.attn
             grads[id(a.in_proj_weight)], grads[id(a.in_proj_bias)] = wg["win"], wg["bin"]
             grads[id(a.out_proj.weight)], grads[id(a.out_proj.bias)] = wg["wout"], wg["bout"]
+            grads.update(wg.get("lora", ()))
             for k_, v_ in fg.items():
                 grads[id(pl[k_])] = v_
             s["layers"][i] = None  # free this block's activations

@@ -706,6 +706,57 @@ def reduce_slabs(out, slabs, accumulate=False):
                                           _st()), "svl_reduce_slabs_f32")
 
 
+def lora_merge(W, pairs, s, out=None):
+    """Weff = W + s * B @ A per row block (svl_lora_merge_f32): `pairs` lists, for each of the len(pairs) <= 3 equal row
+    blocks of W [n * rows, E], the adapter (A [r, E], B [rows, r]) or None for a block that is copied (all adapters of
+    one call share r).  One read of W, one write of `out` (a fresh tensor unless given)."""
+    n = len(pairs)
+    rows, E = W.shape[0] // n, W.shape[1]
+    assert W.dim() == 2 and W.shape[0] == rows * n and W.stride(1) == 1
+    if out is None:
+        out = empty(*W.shape, device=W.device)
+    assert out.shape == W.shape and out.stride(1) == 1 and out.dtype == torch.float32
+    Ap, Bp = (C.c_void_p * n)(), (C.c_void_p * n)()
+    r, ldb = 1, 1
+    for i, pr in enumerate(pairs):
+        if pr is None:
+            continue
+        A, B = pr
+        assert A.dim() == 2 and A.shape[1] == E and A.is_contiguous() and _chk(A) is A and _chk(B) is B
+        assert tuple(B.shape) == (rows, A.shape[0]) and (B.stride(1) == 1 or A.shape[0] == 1)
+        assert not any(Ap) or (r, ldb) == (A.shape[0], B.stride(0)), "lora_merge: the adapters of one call share r"
+        r, ldb = A.shape[0], B.stride(0)
+        Ap[i], Bp[i] = A.data_ptr(), B.data_ptr()
+    e0 = _prof_begin()
+    L.check(L.load().svl_lora_merge_f32(_p(_chk(W)), W.stride(0), _p(out), out.stride(0), n, rows, E, r, float(s), Ap, Bp,
+                                        ldb, _st()), "svl_lora_merge_f32")
+    _prof_end("lora_merge", e0, 8.0 * W.numel(), (n, rows, E, r))
+    return out
+
+
+def lora_wgrad(dW, A, B, s, out_b=None, out_a=None, accumulate_b=False, accumulate_a=False):
+    """(dB [rows, r], dA [r, E]) with dB (+)= s * dW @ A^T and dA (+)= s * B^T @ dW from one read of dW [rows, E]
+    (svl_lora_wgrad_f32: dA through per-row-tile partials and a fixed-order second stage -- bitwise reproducible).
+    out_b / out_a: contiguous tensors to write (accumulate_* adds onto them); fresh ones otherwise."""
+    rows, E = dW.shape
+    r = A.shape[0]
+    assert dW.stride(1) == 1 and tuple(A.shape) == (r, E) and A.is_contiguous() and tuple(B.shape) == (rows, r)
+    assert B.stride(1) == 1 or r == 1
+    if out_b is None:
+        out_b, accumulate_b = empty(rows, r, device=dW.device), False
+    if out_a is None:
+        out_a, accumulate_a = empty(r, E, device=dW.device), False
+    assert out_b.is_contiguous() and out_a.is_contiguous() and out_b.numel() == rows * r and out_a.numel() == r * E
+    lib = L.load()
+    ws = empty(max(int(lib.svl_lora_wgrad_ws_floats(rows, E, r)), 4), device=dW.device)
+    e0 = _prof_begin()
+    L.check(lib.svl_lora_wgrad_f32(_p(_chk(dW)), dW.stride(0), _p(_chk(A)), _p(_chk(B)), B.stride(0), rows, E, r, float(s),
+                                   _p(_chk(out_b)), 1 if accumulate_b else 0, _p(_chk(out_a)), 1 if accumulate_a else 0,
+                                   _p(ws), _st()), "svl_lora_wgrad_f32")
+    _prof_end("lora_wgrad", e0, 4.0 * dW.numel(), (rows, E, r))
+    return out_b, out_a
+
+
 def colsum(x2d, out=None, accumulate=False, C_=None, ld=None):
     rows = x2d.shape[0]
     Cc = C_ if C_ is not None else x2d.shape[1]
