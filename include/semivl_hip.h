@@ -832,6 +832,26 @@ int64_t svl_lora_wgrad_ws_floats(int rows, int E, int r);
 int svl_lora_wgrad_f32(const float* dW, int64_t lddw, const float* A, const float* B, int64_t ldb, int rows, int E, int r,
                        float s, float* dB, int accumulate_b, float* dA, int accumulate_a, float* ws, svl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Deep visual prompt tokens of the CLIP ViT (maskclip_vit.py:359-368,510-536).  With num_prompt_tokens = P every block
+ * runs on [class token | P prompt rows | patch tokens] = T + P rows per image; the prompt rows are written before the block
+ * and dropped after it.  fp32, row-major [B, rows, E] matrices without padding.  mask [B, P, E] of 0 / 1 floats, or NULL (no
+ * dropout: scale is ignored).  16-byte accesses when E % 4 == 0 and every pointer is 16-byte aligned, scalar otherwise.  A
+ * null required pointer or a non-positive size is SVL_ERR_INVALID_ARG and nothing is written.  No atomics: results are
+ * bitwise reproducible.
+ *   svl_prompt_rows_fwd_f32  expand (src [B, T, E] != NULL): dst [B, T + P, E] with dst[b, 0] = src[b, 0],
+ *                            dst[b, 1 + j] = emb[j] * (mask[b, j] * scale), dst[b, 1 + P + t] = src[b, 1 + t]; one read of
+ *                            src, one write of dst.  in place (src == NULL): only the B * P prompt rows of dst are written;
+ *                            the other rows are neither read nor written.  emb [P, E].
+ *   svl_prompt_rows_bwd_f32  dx [B, T + P, E].  demb [P, E] (may be NULL: no sum): demb[j, e] (+)= sum_b dx[b, 1 + j, e] *
+ *                            (mask[b, j, e] * scale), one thread per element, b ascending, every product and sum rounded
+ *                            once.  zero (dx_out == NULL): rows 1 .. P of dx are then set to zero in place.  compact
+ *                            (dx_out [B, T, E] != NULL): dx without its prompt rows is written to dx_out; dx is only read. */
+int svl_prompt_rows_fwd_f32(const float* src, float* dst, const float* emb, const float* mask, float scale, int B, int T,
+                            int P, int E, svl_stream_t stream);
+int svl_prompt_rows_bwd_f32(float* dx, float* dx_out, float* demb, const float* mask, float scale, int accumulate, int B,
+                            int T, int P, int E, svl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

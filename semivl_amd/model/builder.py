@@ -388,6 +388,8 @@ def build_model(cfg):
     mdict = dict(mcfg["model"])
     model = SEGMENTORS[mdict.pop("type")](**mdict)
     model.disable_dropout = cfg["disable_dropout"]
+    if hasattr(model.backbone, "disable_dropout"):    # the ViT's prompt_dropout (builder.py:61-64 puts every nn.Dropout into eval mode)
+        model.backbone.disable_dropout = cfg["disable_dropout"]
     model.fp_rate = cfg["fp_rate"]
     model.init_weights()
     return model

@@ -2,11 +2,13 @@
 
 Mirror of `MaskClipVisionTransformer` / `TransformerEncoderLayer`
 (/root/reference third_party/maskclip/models/backbones/maskclip_vit.py:29-144,147-603) for the configurations on
-the SemiVL hot path (pre_norm, final_norm, return_clip_embed, return_qkv=True, no prompt tokens), with the
+the SemiVL hot path (pre_norm, final_norm, return_clip_embed, return_qkv=True), with the
 same constructor kwargs and the same `state_dict` key schema.  LoRA adapters (`lora_layers`,
 model/backbone/lora.py) run as MERGED weights: with lora_dropout == 0 the adapter is linear in the projection's own input,
 so a block with adapters runs the same kernels on W + s * B @ A (ops.lora_merge) and its adapters' gradients are projected
-out of the projection's weight gradient (ops.lora_wgrad).
+out of the projection's weight gradient (ops.lora_wgrad).  Deep visual prompts (`num_prompt_tokens` = P) put P rows between
+the class token and the patch tokens of every block's input (ops.prompt_rows_fwd) and take them out of its outputs again;
+their gradient is the batch sum of the block's input gradient on those rows (ops.prompt_rows_bwd).
 
 The whole forward AND backward of the encoder is hand-scheduled over libsemivl_hip.so (one autograd.Function for
 the region): tokens stay in [B*T, C] row-major, attention/FFN/LN backward are explicit kernel sequences, weight
@@ -306,6 +308,10 @@ def attn_wgrads(p_mod, g, E):
     out = {}
     if p_mod.lora is not None:
         return _lora_attn_wgrads(p_mod, g, E)
+    # a projection whose weight and bias are both frozen launches nothing (a prompts-only recipe: no weight-gradient GEMM,
+    # column sum or slab reduction for the blocks at all)
+    train_out = a.out_proj.weight.requires_grad or a.out_proj.bias.requires_grad
+    train_in = a.in_proj_weight.requires_grad or a.in_proj_bias.requires_grad
 
     def wout_fn(dst, acc):
         first = not acc
@@ -319,12 +325,14 @@ def attn_wgrads(p_mod, g, E):
             ops.colsum(dy, out=dst, accumulate=not first)
             first = False
 
-    if g["wout_parts"]:
+    if g["wout_parts"] and train_out:
         out["wout"] = sink_grad(a.out_proj.weight, wout_fn)
         out["bout"] = sink_grad(a.out_proj.bias, bout_fn)
     else:
         out["wout"] = out["bout"] = None
-    if "in_full" in g:
+    if not train_in:
+        out["win"] = out["bin"] = None
+    elif "in_full" in g:
         dqkv, y1, dq_amax, y1_amax = g["in_full"]
         out["win"] = sink_grad(a.in_proj_weight, lambda dst, acc: ops.matmul_tn(dqkv, y1, out=dst, accumulate=acc,
                                                                                 a_amax=dq_amax, b_amax=y1_amax))
@@ -441,7 +449,7 @@ class MaskClipVisionTransformer(nn.Module):
             img_size = (img_size, img_size)
         unsupported = dict(patch_bias=patch_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
                            drop_path_rate=drop_path_rate, patch_norm=patch_norm, skip_last_attn=skip_last_attn,
-                           output_cls_token=output_cls_token, num_prompt_tokens=num_prompt_tokens,
+                           output_cls_token=output_cls_token,
                            lora_dropout=lora_dropout if len(lora_layers) else 0)   # (the one part of LoRA that does not merge)
         bad = {k: v for k, v in unsupported.items() if v not in (False, 0, 0.0, None, [])}
         if bad or not (pre_norm and final_norm and return_clip_embed and with_cls_token and qkv_bias):
@@ -480,6 +488,21 @@ class MaskClipVisionTransformer(nn.Module):
         for o in self.out_indices:
             if o < num_layers and not self.return_qkv[o]:
                 raise NotImplementedError("out_indices without return_qkv is off the SemiVL path")
+        # deep visual prompts (maskclip_vit.py:359-368).  prompt_norm is never called by the reference's forward: its two
+        # tensors are state_dict entries that never receive a gradient (_trainable, optim._trainable).
+        self.num_prompt_tokens = num_prompt_tokens
+        self.disable_dropout = True         # build_model: cfg['disable_dropout'] (prompt_dropout is live in train mode only when False)
+        self.prompt_mask_hook = None        # tests: callable (layer, B) -> {0, 1} mask [B, P, E] (or None) in place of ops.bernoulli
+        if num_prompt_tokens is not None:
+            if not isinstance(num_prompt_tokens, int) or num_prompt_tokens < 1:
+                raise ValueError(f"num_prompt_tokens must be a positive int or None, got {num_prompt_tokens!r}")
+            val = math.sqrt(6. / float(3 * patch_size * patch_size + embed_dims))
+            self.deep_prompt_embeddings = nn.Parameter(torch.zeros(num_layers, num_prompt_tokens, embed_dims))
+            nn.init.uniform_(self.deep_prompt_embeddings.data, -val, val)
+            self.prompt_proj = nn.Linear(embed_dims, embed_dims)
+            nn.init.kaiming_normal_(self.prompt_proj.weight, a=0, mode="fan_out")
+            self.prompt_norm = nn.LayerNorm(embed_dims, eps=1e-6)
+            self.prompt_dropout = nn.Dropout(0.1)
         self.init_weights()
 
     # -- init -----------------------------------------------------------------------------------------------
@@ -508,7 +531,9 @@ class MaskClipVisionTransformer(nn.Module):
             if "proj.weight" in sd and sd["proj.weight"].dim() == 2:
                 sd["proj.weight"] = sd["proj.weight"][:, :, None, None]
             res = self.load_state_dict(sd, strict=False)
-            missing = [k for k in res.missing_keys if ".lora." not in k]    # (adapters keep LoRA.reset_parameters' init)
+            # (adapters keep LoRA.reset_parameters' init; the prompt tensors keep the constructor's: a CLIP file has neither)
+            missing = [k for k in res.missing_keys if ".lora." not in k and
+                       not k.startswith(("deep_prompt_embeddings", "prompt_proj.", "prompt_norm."))]
             if missing or res.unexpected_keys:
                 warnings.warn(f"{self.pretrained}: missing keys {missing}, unexpected keys {res.unexpected_keys}")
             return
@@ -545,7 +570,10 @@ class MaskClipVisionTransformer(nn.Module):
 
     # -- forward --------------------------------------------------------------------------------------------
     def _trainable(self):
-        return [p for p in self.parameters() if p.requires_grad]
+        """Tensors the encoder's backward produces a gradient for.  prompt_norm.* is never among them: the reference's
+        forward never calls it, so its .grad stays None there whatever requires_grad says."""
+        never = set() if self.num_prompt_tokens is None else {id(t) for t in self.prompt_norm.parameters()}
+        return [p for p in self.parameters() if p.requires_grad and id(p) not in never]
 
     def _check_grad_rules(self, params):
         """Every trainable tensor handed to the encoder's backward must have a gradient rule there: a tensor without one
@@ -556,6 +584,8 @@ class MaskClipVisionTransformer(nn.Module):
             ruled |= {id(t) for l_ in self.layers if l_.lora is not None for t in l_.lora.parameters()}
             ruled |= {id(t) for t in (self.ln0.weight, self.ln0.bias, self.ln1.weight, self.ln1.bias, self.cls_token,
                                       self.pos_embed, self.patch_embed.projection.weight, self.proj.weight)}
+            if self.num_prompt_tokens is not None:
+                ruled |= {id(t) for t in (self.deep_prompt_embeddings, self.prompt_proj.weight, self.prompt_proj.bias)}
             self.__dict__["_ruled"] = ruled
         bad = [n for n, t in self.named_parameters() if t.requires_grad and id(t) not in ruled and
                any(t is q for q in params)]
@@ -626,13 +656,29 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
     cls_row = ops.add(m.cls_token.view(E), pos[0])
     ops.copy2d(cls_row, 0, 1, 0, 0, x, 0, 1, T * E, 0, B, E)  # x[b*T] = cls + pos[0]
     x0, st0 = ops.layernorm_fwd(x, m.ln0.weight, m.ln0.bias, m.eps)
+    # deep prompts: every block runs on TT = T + P rows per image, [class token | P prompt rows | patch tokens]; the patch
+    # rows of a block's outputs start at row 1 + P
+    P = m.num_prompt_tokens or 0
+    TT = T + P
     if saved is not None:
         saved["x_pre"], saved["st0"] = x, st0
         if m.patch_embed.projection.weight.requires_grad:
             saved["img"] = img     # B operand of the patch-embedding weight gradient
         saved["layers"] = []
-        saved["dims"] = (B, T, NP, hp, wp)
+        saved["dims"] = (B, T, NP, hp, wp)      # (T without the prompt rows: the row count outside the blocks)
     x = x0
+    if P:
+        # prompt_proj over all layers' embeddings in one GEMM; one dropout mask per block and forward (independent per sample)
+        pemb = ops.linear(m.deep_prompt_embeddings.detach().view(L * P, E), m.prompt_proj.weight, m.prompt_proj.bias)
+        pmasks = [None] * L
+        keep = 1.0 - m.prompt_dropout.p
+        if m.training and not m.disable_dropout:
+            for i in range(L):
+                pmasks[i] = (m.prompt_mask_hook(i, B) if m.prompt_mask_hook is not None else ops.bernoulli((B, P, E), keep, dev))
+        pscale = 1.0 / keep     # nn.Dropout's x * (mask / (1 - p)): the quotient is rounded to fp32 once, by the call
+        if saved is not None:
+            saved["prompt"] = (pmasks, pscale)
+        x = ops.prompt_rows_fwd(pemb[:P], B, P, ops.empty(B * TT, E, device=dev), src=x0, mask=pmasks[0], scale=pscale)
     feats = []
     v_last = None
     for i, layer in enumerate(m.layers):
@@ -641,14 +687,16 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         skip_x = last and not need_global
         sv = {} if saved is not None else None
         pl = layer.plist() if layer.lora is None else layer.merged_plist()
-        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, T, want_v, skip_x, sv)
+        if P and i > 0:     # in place on the block above's output (no block keeps its own output for its backward)
+            ops.prompt_rows_fwd(pemb[i * P:(i + 1) * P], B, P, x, mask=pmasks[i], scale=pscale)
+        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, TT, want_v, skip_x, sv)
         if saved is not None:
             if layer.lora is not None:
                 sv["plist"] = pl      # the backward's input-gradient GEMMs run on the same effective weights
             saved["layers"].append(sv)
         if i in m.out_indices:
             f = ops.empty(B * NP, E, device=dev)
-            ops.copy2d(v, E, NP, T * E, E, f, 0, NP, NP * E, E, B * NP, E)  # v[:, 1:]
+            ops.copy2d(v, (1 + P) * E, NP, TT * E, E, f, 0, NP, NP * E, E, B * NP, E)  # v[:, 1 + P:]
             feats.append(f.view(B, NP, E))
         if last:
             v_last = v
@@ -656,7 +704,7 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
     # tail: ln1 on v, proj 1x1, channel L2-normalise (maskclip_vit.py:537-555)
     vn, stv = ops.layernorm_fwd(v_last, m.ln1.weight, m.ln1.bias, m.eps)
     vtok = ops.empty(B * NP, E, device=dev)
-    ops.copy2d(vn, E, NP, T * E, E, vtok, 0, NP, NP * E, E, B * NP, E)
+    ops.copy2d(vn, (1 + P) * E, NP, TT * E, E, vtok, 0, NP, NP * E, E, B * NP, E)
     wproj = m.proj.weight.view(m.proj.weight.shape[0], E)
     pe = ops.linear(vtok, wproj)
     emb, inv = ops.l2norm_fwd(pe, 0.0)
@@ -670,7 +718,7 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
     if need_global:
         xn, _ = ops.layernorm_fwd(x, m.ln1.weight, m.ln1.bias, m.eps)
         c = ops.empty(B, E, device=dev)
-        ops.copy2d(xn, 0, 1, T * E, 0, c, 0, 1, E, 0, B, E)
+        ops.copy2d(xn, 0, 1, TT * E, 0, c, 0, 1, E, 0, B, E)
         gp = ops.linear(c, wproj)
         glob, _ = ops.l2norm_fwd(gp, 0.0)
     return tuple(feats) + (glob,)
@@ -733,6 +781,8 @@ class _EncoderFn(torch.autograd.Function):
         m, s = ctx.m, ctx.saved
         B, T, NP, hp, wp = s["dims"]
         E, L = m.embed_dims, m.num_layers
+        P = m.num_prompt_tokens or 0
+        TT = T + P          # rows per image inside the blocks (prompt rows: 1 .. P)
         dev = s["x_pre"].device
         dfeats = list(douts[:ctx.n_feats])
         # map feature outputs back to (layer index) order
@@ -751,8 +801,8 @@ class _EncoderFn(torch.autograd.Function):
                 vtok = s["vtok"]
                 grads[id(m.proj.weight)] = sink_grad(m.proj.weight, lambda dst, acc: ops.matmul_tn(
                     dpe, vtok, out=dst.view(wproj.shape), accumulate=acc))
-            dvn = ops.zeros(B * T, E, device=dev)
-            ops.copy2d(dvtok, 0, NP, NP * E, E, dvn, E, NP, T * E, E, B * NP, E)
+            dvn = ops.zeros(B * TT, E, device=dev)
+            ops.copy2d(dvtok, 0, NP, NP * E, E, dvn, (1 + P) * E, NP, TT * E, E, B * NP, E)
             if m.ln1.weight.requires_grad or m.ln1.bias.requires_grad:
                 dv_last, dg_, db_ = ops.layernorm_bwd(dvn, s["v_last"], s["stv"], m.ln1.weight, want_wgrad=True)
                 _sink_vectors(grads, ((m.ln1.weight, dg_), (m.ln1.bias, db_)))
@@ -764,17 +814,32 @@ class _EncoderFn(torch.autograd.Function):
             if d is None:
                 continue
             d = d.contiguous().view(B * NP, E)
-            full = ops.zeros(B * T, E, device=dev)
-            ops.copy2d(d, 0, NP, NP * E, E, full, E, NP, T * E, E, B * NP, E)
+            full = ops.zeros(B * TT, E, device=dev)
+            ops.copy2d(d, 0, NP, NP * E, E, full, (1 + P) * E, NP, TT * E, E, B * NP, E)
             dvs[li] = full if dvs.get(li) is None else ops.add(dvs[li], full)
         # ---- blocks, last to first
         dx = dxp = pend = None
+        if P:
+            # d emb_i = the batch sum of block i's input gradient on the prompt rows, of THIS backward call (the step runs
+            # the encoder backward twice and main_grad accumulates: the three products below add each call's share once)
+            pmasks, pscale = s["prompt"]
+            ptrain = any(t.requires_grad for t in (m.deep_prompt_embeddings, m.prompt_proj.weight, m.prompt_proj.bias))
+            pdemb = ops.zeros(L, P, E, device=dev) if ptrain else None
         for i in range(L - 1, -1, -1):
             layer = m.layers[i]
             sv = s["layers"][i]
             pl = layer.plist()
             want = frozenset(k_ for k_ in FFN_LN_KEYS if pl[k_].requires_grad)
-            dx, dxp, g = block_backward(dx, dvs.get(i), sv.get("plist", pl), sv, m.num_heads, B, T, want=want, dxo_p=dxp)
+            dx, dxp, g = block_backward(dx, dvs.get(i), sv.get("plist", pl), sv, m.num_heads, B, TT, want=want, dxo_p=dxp)
+            if P and dx is not None:
+                # the prompt rows of block i's input belong to emb_i alone: they are summed into pdemb[i] and do not flow
+                # into block i - 1 (whose output prompt rows were discarded).  Block i - 1 packs its planes from the zeroed
+                # fp32 matrix (dxp is dropped); block 0 hands the rows without the prompts to the ln0 backward.
+                dxp = None
+                d0 = ops.empty(B * T, E, device=dev) if i == 0 else None
+                ops.prompt_rows_bwd(dx, B, P, out=pdemb[i] if ptrain else None, mask=pmasks[i], scale=pscale, compact=d0)
+                if i == 0:
+                    dx = d0
             # this block's weight gradients (two split-K GEMMs, their slab reductions, two column sums; with a trained FFN
             # two more GEMM families on B-operand producers) are off the dependency chain: they go to the weight-gradient
             # stream and run next to the chain's LayerNorm-backward / pack passes of the blocks below (ops.wgrad_side)
@@ -799,6 +864,16 @@ class _EncoderFn(torch.autograd.Function):
         ops.wgrad_join(produced=grads.values())     # every weight gradient of this graph is complete from here on
         if pend is not None:
             gradsync.ready(pend[1])
+        if P and ptrain and dx is not None:
+            df = pdemb.view(L * P, E)
+            deep, w, bias = m.deep_prompt_embeddings, m.prompt_proj.weight, m.prompt_proj.bias
+            if deep.requires_grad:      # emb = deep @ W^T + b
+                grads[id(deep)] = sink_grad(deep, lambda dst, acc: ops.matmul_nn(df, w.detach(), out=dst.view(L * P, E), accumulate=acc))
+            if w.requires_grad:
+                dflat = deep.detach().view(L * P, E)
+                grads[id(w)] = sink_grad(w, lambda dst, acc: ops.matmul_tn(df, dflat, out=dst, accumulate=acc))
+            if bias.requires_grad:
+                grads[id(bias)] = sink_grad(bias, lambda dst, acc: ops.colsum(df, out=dst, accumulate=acc))
         rest = [q for q in ctx.params if q is m.pos_embed or not any(q is r_ for l_ in m.layers for r_ in l_.parameters())]
         if dx is None:
             gradsync.ready(rest)

@@ -757,6 +757,46 @@ def lora_wgrad(dW, A, B, s, out_b=None, out_a=None, accumulate_b=False, accumula
     return out_b, out_a
 
 
+def _prompt_dims(x, Bn, P, emb, mask):
+    """(rows per image, E) of the token matrix x [Bn * rows, E] next to emb [P, E] and mask [Bn, P, E] or None"""
+    E = x.shape[-1]
+    assert x.is_contiguous() and x.numel() % (Bn * E) == 0 and P >= 1
+    assert emb is None or (emb.is_contiguous() and tuple(emb.shape) == (P, E))
+    assert mask is None or (mask.is_contiguous() and tuple(mask.shape) == (Bn, P, E))
+    return x.numel() // (Bn * E), E
+
+
+def prompt_rows_fwd(emb, Bn, P, out, src=None, mask=None, scale=1.0):
+    """Prompt rows of a token matrix (svl_prompt_rows_fwd_f32): out [Bn * (T + P), E] gets out[b, 1 + j] = emb[j] *
+    (mask[b, j] * scale) (mask None: emb[j]).  With src [Bn * T, E] the other rows are copied from it (class token first);
+    without, they are left as they are (the in-place form)."""
+    TP, E = _prompt_dims(out, Bn, P, emb, mask)
+    T = TP - P
+    assert T >= 1 and (src is None or (src.is_contiguous() and src.numel() == Bn * T * E))
+    e0 = _prof_begin()
+    L.check(L.load().svl_prompt_rows_fwd_f32(_p(None if src is None else _chk(src)), _p(_chk(out)), _p(_chk(emb)),
+                                             _p(None if mask is None else _chk(mask)), float(scale), Bn, T, P, E, _st()),
+            "svl_prompt_rows_fwd_f32")
+    _prof_end("prompt_rows_fwd", e0, 4.0 * E * Bn * ((2 * T + P) if src is not None else P), (Bn, T, P, E, src is not None))
+    return out
+
+
+def prompt_rows_bwd(dx, Bn, P, out=None, mask=None, scale=1.0, accumulate=False, compact=None):
+    """Backward of the prompt rows of dx [Bn * (T + P), E] (svl_prompt_rows_bwd_f32): out [P, E] (+)= sum_b dx[b, 1 + j] *
+    (mask[b, j] * scale) (out None: no sum).  compact None: rows 1 .. P of dx are set to zero in place; compact [Bn * T, E]:
+    dx without its prompt rows is written there and dx is left as it is."""
+    TP, E = _prompt_dims(dx, Bn, P, out, mask)
+    T = TP - P
+    assert T >= 1 and (compact is None or (compact.is_contiguous() and compact.numel() == Bn * T * E))
+    e0 = _prof_begin()
+    L.check(L.load().svl_prompt_rows_bwd_f32(_p(_chk(dx)), _p(None if compact is None else _chk(compact)),
+                                             _p(None if out is None else _chk(out)), _p(None if mask is None else _chk(mask)),
+                                             float(scale), 1 if accumulate else 0, Bn, T, P, E, _st()),
+            "svl_prompt_rows_bwd_f32")
+    _prof_end("prompt_rows_bwd", e0, 4.0 * E * Bn * (P + (2 * T if compact is not None else 0)), (Bn, T, P, E, compact is not None))
+    return out
+
+
 def colsum(x2d, out=None, accumulate=False, C_=None, ld=None):
     rows = x2d.shape[0]
     Cc = C_ if C_ is not None else x2d.shape[1]

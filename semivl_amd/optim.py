@@ -27,9 +27,10 @@ def mmcv_param_groups(named_params, lr, weight_decay, custom_keys):
 
 def _trainable(name, prm):
     """The arena rule of every optimizer here: tensors that can receive a gradient.  `clip_encoder.*` (registered with
-    requires_grad=True in the reference, never given a grad -- SURVEY App. E.2) and frozen backbone tensors are left
-    untouched, which is also what torch's optimizers do for params whose .grad is None."""
-    return prm.requires_grad and not name.startswith("clip_encoder.")
+    requires_grad=True in the reference, never given a grad -- SURVEY App. E.2), `prompt_norm.*` of a ViT with prompt tokens
+    (never called by the reference's forward: no grad either) and frozen backbone tensors are left untouched, which is also
+    what torch's optimizers do for params whose .grad is None: no update, no weight decay."""
+    return prm.requires_grad and not name.startswith("clip_encoder.") and ".prompt_norm." not in "." + name
 
 
 def arena_layout(sizes):

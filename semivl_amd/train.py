@@ -307,7 +307,19 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     # left out; its dlogits are zero like pred_w's, and backward runs on the whole batch (the statistics terms carry
     # gradient into those rows).
     fp_kw = {} if head_bn else dict(fp_range=(0, B))
-    preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **fwd_kw)
+    # (injected prompt-dropout masks of the backbone come in the reference's [x, w] row order too)
+    bb = getattr(model, "backbone", None)
+    phook = getattr(bb, "prompt_mask_hook", None)
+    if phook is not None:
+        def _wx(layer, n, hook=phook):
+            m_ = hook(layer, n)
+            return None if m_ is None else torch.cat((m_[B:2 * B], m_[:B]))
+        bb.prompt_mask_hook = _wx
+    try:
+        preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **fwd_kw)
+    finally:
+        if phook is not None:
+            bb.prompt_mask_hook = phook
     preds_s = model(_cat2(img_s1, img_s2), **fwd_kw)                                       # [s1, s2]
     pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:3 * B]
     pred_s1, pred_s2 = preds_s[:B], preds_s[B:]
