@@ -852,6 +852,21 @@ int svl_prompt_rows_fwd_f32(const float* src, float* dst, const float* emb, cons
 int svl_prompt_rows_bwd_f32(float* dx, float* dx_out, float* demb, const float* mask, float scale, int accumulate, int B,
                             int T, int P, int E, svl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Stochastic depth (drop-path) of the CLIP ViT's residual branches (maskclip_vit.py:120-144).  One draw per sample scales
+ * the T rows of that sample: s_b = mask[b] * scale (mask [B] floats, scale = 1 / keep).  fp32, row-major [B * T, E] matrices
+ * without padding; the sample of a row is row / T.  16-byte accesses when E % 4 == 0 and the matrix pointers are 16-byte
+ * aligned, scalar otherwise.  A null pointer or a non-positive size is SVL_ERR_INVALID_ARG and nothing is written.  No
+ * atomics: results are bitwise reproducible.
+ *   svl_droppath_fwd_f32  out = resid + s_b * branch (the product and the sum rounded once each).  out may be branch (not
+ *                         resid).  Rows of a dropped sample (mask[b] == 0) are copied from resid; branch is not read there.
+ *   svl_droppath_bwd_f32  dbranch = s_b * dout (dbranch may be dout).  Rows of a dropped sample are written as zeros; dout
+ *                         is not read there. */
+int svl_droppath_fwd_f32(const float* branch, const float* resid, const float* mask, float scale, float* out, int B, int T,
+                         int E, svl_stream_t stream);
+int svl_droppath_bwd_f32(const float* dout, const float* mask, float scale, float* dbranch, int B, int T, int E,
+                         svl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,8 @@ SIGNATURES = {
     "svl_lora_wgrad_f32": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P]),
     "svl_prompt_rows_fwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _I, _P]),
     "svl_prompt_rows_bwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
+    "svl_droppath_fwd_f32": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _P]),
+    "svl_droppath_bwd_f32": (_I, [_P, _P, _F, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -8,7 +8,9 @@ model/backbone/lora.py) run as MERGED weights: with lora_dropout == 0 the adapte
 so a block with adapters runs the same kernels on W + s * B @ A (ops.lora_merge) and its adapters' gradients are projected
 out of the projection's weight gradient (ops.lora_wgrad).  Deep visual prompts (`num_prompt_tokens` = P) put P rows between
 the class token and the patch tokens of every block's input (ops.prompt_rows_fwd) and take them out of its outputs again;
-their gradient is the batch sum of the block's input gradient on those rows (ops.prompt_rows_bwd).
+their gradient is the batch sum of the block's input gradient on those rows (ops.prompt_rows_bwd).  Stochastic depth
+(`drop_path_rate`) scales a block's residual branches per sample (ops.droppath_add / ops.droppath_scale) at the sites
+DROP_PATH_SITES; a block with rate 0 and every eval-mode forward launch what they launch without the option.
 
 The whole forward AND backward of the encoder is hand-scheduled over libsemivl_hip.so (one autograd.Function for
 the region): tokens stay in [B*T, C] row-major, attention/FFN/LN backward are explicit kernel sequences, weight
@@ -131,8 +133,14 @@ def sink_grad(param, grad_fn, shape=None):
 
 
 # ------------------------------------------------------------------------------------------------ block forward / backward
-def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
+DROP_PATH_SITES = ("attn", "ffn", "ffn_v")   # x + dp(out_proj(attention)), x2 + dp(FFN(ln2 x2)), vo + dp(FFN(ln2 vo))
+
+
+def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save, dp=None):
     """x [Bn*T, E] -> (x_out or None, v or None).  `save` is a dict to stash what backward needs (or None).
+    `dp`: None, or the block's live stochastic-depth sites: dict(keep=1 - p_i, <site>=mask [Bn] fp32 ...) over DROP_PATH_SITES.
+    At a live site the branch's GEMM runs without its residual operand and ops.droppath_add forms identity + (mask_b / keep) *
+    branch in place in the branch's buffer.
     Under the packed-planes GEMM path (ops.planes_eligible) every A operand is produced directly in that format: both
     LayerNorms, the FFN-1 epilogue and the fused attention kernel emit planes (ln2's output and gelu(h) exist ONLY as
     planes, the attention output too in gradient-free passes); the v slice of qkv takes the generic split pass."""
@@ -153,21 +161,25 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
     v = None
     if save is not None:
         save.update(x=x, y1=y1, st1=st1, qkv=qkv, vproj=vproj, want_v=want_v, skip_x=skip_x, eps=eps,
-                    y1_amax=y1a.amax if pp else None)     # (the maximum of y1 as packed: the in_proj weight gradient's B operand)
+                    y1_amax=y1a.amax if pp else None,     # (the maximum of y1 as packed: the in_proj weight gradient's B operand)
+                    dp=dp)
+    dp = dp or {}
 
-    def ffn(pre, want_pre):
-        """pre + FFN(LN2(pre)); returns (out, ln2 stats, saved pre-activation or None)."""
+    def ffn(pre, want_pre, mask=None):
+        """pre + FFN(LN2(pre)); returns (out, ln2 stats, saved pre-activation or None).  `mask`: the site's drop-path draws."""
         if pp:
             _, st2_, y2a = ops.layernorm_fwd(pre, p["ln2w"], p["ln2b"], eps, planes=True, want_y=False)
         else:
             y2a, st2_ = ops.layernorm_fwd(pre, p["ln2w"], p["ln2b"], eps)
         h_pre_ = ops.empty(pre.shape[0], p["w1"].shape[0], device=x.device) if want_pre else None
         h_ = ops.linear(y2a, p["w1"], p["b1"], act=ops.ACT_GELU, preact=h_pre_, planes_only=True)   # only feeds FFN-2
+        if mask is not None:
+            return ops.droppath_add(ops.linear(h_, p["w2"], p["b2"]), pre, mask, dp["keep"], Bn, T), st2_, h_pre_
         return ops.linear(h_, p["w2"], p["b2"], resid=pre), st2_, h_pre_
 
     if want_v:
         vo = ops.linear(ops.split_planes(vproj) if pp else vproj, p["wout"], p["bout"], resid=x)  # out_proj(v) + x   (maskclip_vit.py:115-117)
-        v, st2v, hv_pre = ffn(vo, save is not None)
+        v, st2v, hv_pre = ffn(vo, save is not None, dp.get("ffn_v"))
         if save is not None:
             save.update(vo=vo, st2v=st2v, hv_pre=hv_pre)
     xo = None
@@ -184,8 +196,12 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save):
         else:  # generic head dim: batched-GEMM attention with materialised probabilities
             o, P = ops.vit_attention_fwd(qkv, Bn, T, heads, D)
             sets = []
-        x2 = ops.linear(o_p if o_p is not None else (ops.split_planes(o) if pp else o), p["wout"], p["bout"], resid=x)
-        xo, st2, h_pre = ffn(x2, save is not None)
+        o_a = o_p if o_p is not None else (ops.split_planes(o) if pp else o)
+        if dp.get("attn") is not None:
+            x2 = ops.droppath_add(ops.linear(o_a, p["wout"], p["bout"]), x, dp["attn"], dp["keep"], Bn, T)
+        else:
+            x2 = ops.linear(o_a, p["wout"], p["bout"], resid=x)
+        xo, st2, h_pre = ffn(x2, save is not None, dp.get("ffn"))
         if save is not None:
             save.update(o=o, P=P, x2=x2, st2=st2, h_pre=h_pre, sets=sets[0] if sets else None)
     return xo, v
@@ -198,7 +214,10 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
     """Returns (dx_in, dx_in planes or None, grads dict).  The attention projections' pieces are always collected (the
     `ftap` recipes train them, vlm.py:66-67); `want` names the FFN / LayerNorm tensors (plist keys, FFN_LN_KEYS) that
     train too (freeze_backbone=False or a wider exclude_keys): only their weight-gradient pieces are produced.
-    `dxo_p`: dxo as packed planes when the block above already produced them (its LN1 backward)."""
+    `dxo_p`: dxo as packed planes when the block above already produced them (its LN1 backward).
+    At a live stochastic-depth site (s["dp"]) everything below the site takes (mask_b / keep) * d out (ops.droppath_scale): the
+    input-gradient GEMMs, the weight-gradient pieces, the bias sums and the LayerNorm backward's dy; the identity path (dx_add=,
+    dx_res) takes d out as it is."""
     x, y1 = s["x"], s["y1"]
     E = x.shape[1]
     D = E // heads
@@ -208,9 +227,14 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
     dqkv = dqkv_p = dqkv_amax = None     # dqkv_amax: the maximum the pack pass found, valid while dqkv stays as packed
     wout_parts = []  # (dy, input) pairs contributing to out_proj wgrad
     need_h = "w1" in want or "b1" in want
+    dp = s.get("dp") or {}
 
-    def ffn_ln_bwd(dout, dout_p, pre_ln_in, st2, h_pre):
-        """-> (d pre_ln_in, the same as planes or None)"""
+    def ffn_ln_bwd(dout, dout_p, pre_ln_in, st2, h_pre, mask=None):
+        """-> (d pre_ln_in, the same as planes or None).  `mask`: the site's drop-path draws (the branch sees the scaled dout)."""
+        res = dout      # the identity path's share
+        if mask is not None:
+            dout = ops.droppath_scale(dout, mask, dp["keep"], Bn, T)
+            dout_p = ops.split_planes(dout) if pp else None     # (planes of the unscaled gradient do not describe it)
         # (dout W2) * GELU'(h_pre), one pass; with frozen FFN-1 weights its only consumer is the next GEMM (bf16 planes)
         a_ = dout_p if dout_p is not None else dout
         dhp = ops.matmul_nn(a_, p["w2"], dact=ops.ACT_MUL_DGELU, z=h_pre, planes_only=not need_h)
@@ -226,18 +250,22 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
         if "b1" in want:
             g.setdefault("b1", []).append(("sum", dhp))
         if "ln2w" in want or "ln2b" in want:
-            r_ = ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout, want_wgrad=True, planes=pp)
+            r_ = ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=res, want_wgrad=True, planes=pp)
             g.setdefault("ln2w", []).append(("add", r_[1]))
             g.setdefault("ln2b", []).append(("add", r_[2]))
             return r_[0], (r_[3] if pp else None)
         if pp:
-            return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout, planes=True)
-        return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=dout), None
+            return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=res, planes=True)
+        return ops.layernorm_bwd(dy2, pre_ln_in, st2, p["ln2w"], dx_add=res), None
 
     if not s["skip_x"] and dxo is not None:
-        dx2, dx2p = ffn_ln_bwd(dxo, dxo_p, s["x2"], s["st2"], s["h_pre"])
-        do = ops.matmul_nn(dx2p if dx2p is not None else dx2, p["wout"])
-        wout_parts.append((dx2, s["o"]))
+        dx2, dx2p = ffn_ln_bwd(dxo, dxo_p, s["x2"], s["st2"], s["h_pre"], dp.get("ffn"))
+        dbr, dbrp = dx2, dx2p       # d out_proj(attention): the scaled gradient at a live site
+        if dp.get("attn") is not None:
+            dbr = ops.droppath_scale(dx2, dp["attn"], dp["keep"], Bn, T)
+            dbrp = ops.split_planes(dbr) if pp else None
+        do = ops.matmul_nn(dbrp if dbrp is not None else dbr, p["wout"])
+        wout_parts.append((dbr, s["o"]))
         if D == 64 and pp and ops.attention_planes_ok() and not (s["want_v"] and dv is not None):
             # dqkv also as planes (in_proj's input-gradient GEMM), from the two kernels' epilogues
             dqkv, dqkv_p = ops.attention_bwd(do, s["qkv"], s["o"], s["P"], Bn, T, heads, planes=True, sets=s.get("sets"))
@@ -249,7 +277,7 @@ def block_backward(dxo, dv, p, s, heads, Bn, T, want=frozenset(), dxo_p=None):
         dx_res = dx2
     dvproj = None
     if s["want_v"] and dv is not None:
-        dvo, dvop = ffn_ln_bwd(dv, None, s["vo"], s["st2v"], s["hv_pre"])
+        dvo, dvop = ffn_ln_bwd(dv, None, s["vo"], s["st2v"], s["hv_pre"], dp.get("ffn_v"))
         dvproj = ops.matmul_nn(dvop if dvop is not None else dvo, p["wout"])
         wout_parts.append((dvo, s["vproj"]))
         dx_res = dvo if dx_res is None else ops.add(dx_res, dvo)
@@ -448,13 +476,16 @@ class MaskClipVisionTransformer(nn.Module):
         if isinstance(img_size, int):
             img_size = (img_size, img_size)
         unsupported = dict(patch_bias=patch_bias, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
-                           drop_path_rate=drop_path_rate, patch_norm=patch_norm, skip_last_attn=skip_last_attn,
+                           patch_norm=patch_norm, skip_last_attn=skip_last_attn,
                            output_cls_token=output_cls_token,
                            lora_dropout=lora_dropout if len(lora_layers) else 0)   # (the one part of LoRA that does not merge)
         bad = {k: v for k, v in unsupported.items() if v not in (False, 0, 0.0, None, [])}
         if bad or not (pre_norm and final_norm and return_clip_embed and with_cls_token and qkv_bias):
             raise NotImplementedError(f"MaskClipVisionTransformer (HIP): only the SemiVL hot-path configuration is "
-                                      f"implemented (off-path options: {bad})")
+                                      f"implemented (off-path options: {bad}; of the regularisers drop_path_rate is "
+                                      f"implemented, drop_rate, attn_drop_rate and lora_dropout are not)")
+        if isinstance(drop_path_rate, bool) or not isinstance(drop_path_rate, (int, float)) or not 0 <= drop_path_rate < 1:
+            raise ValueError(f"drop_path_rate must be a number in [0, 1), got {drop_path_rate!r}")
         assert act_cfg.get("type") == "GELU" and norm_cfg.get("type") == "LN" and interpolate_mode == "bicubic"
         self.img_size, self.patch_size = tuple(img_size), patch_size
         self.embed_dims, self.num_layers, self.num_heads = embed_dims, num_layers, num_heads
@@ -503,6 +534,13 @@ class MaskClipVisionTransformer(nn.Module):
             nn.init.kaiming_normal_(self.prompt_proj.weight, a=0, mode="fan_out")
             self.prompt_norm = nn.LayerNorm(embed_dims, eps=1e-6)
             self.prompt_dropout = nn.Dropout(0.1)
+        # stochastic depth (maskclip_vit.py:299-312): block i drops its residual branches per sample with rate dpr[i].  Live
+        # whenever the module is in train mode and dpr[i] > 0, whatever disable_dropout says (the reference's wrapper does
+        # not reach the DropPath of this ViT's blocks).
+        self.drop_path_rate = float(drop_path_rate)
+        # (host values in fp32, also when the model is built under a meta device or another default dtype)
+        self.dpr = [x.item() for x in torch.linspace(0, drop_path_rate, num_layers, dtype=torch.float32, device="cpu")]
+        self.drop_path_hook = None          # tests: callable (layer, site, B) -> fp32 mask [B] (or None) in place of ops.bernoulli
         self.init_weights()
 
     # -- init -----------------------------------------------------------------------------------------------
@@ -637,6 +675,23 @@ class MaskClipVisionTransformer(nn.Module):
         return [tuple(f.view(B, hp, wp, f.shape[-1]).permute(0, 3, 1, 2) for f in feats), g]
 
 
+def _drop_path_masks(m, i, B, want_v, skip_x, dev):
+    """Block i's live stochastic-depth sites for one forward: None (eval mode, or rate 0: the block runs as it does without the
+    option), or dict(keep=, <site>=mask [B]).  One draw per sample and site, only for the branches this forward runs, in the
+    reference's call order (v path first); drop_path_hook's mask takes precedence over the draw.  No device sync."""
+    rate = m.dpr[i]
+    if not (m.training and rate > 0):
+        return None
+    dp = dict(keep=1.0 - rate)
+    for site in (("ffn_v",) if want_v else ()) + (() if skip_x else ("attn", "ffn")):
+        mask = m.drop_path_hook(i, site, B) if m.drop_path_hook is not None else None
+        if mask is None:
+            mask = ops.bernoulli((B,), dp["keep"], dev)
+        assert mask.dtype == torch.float32 and mask.numel() == B, (site, mask.shape, mask.dtype)
+        dp[site] = mask.to(dev).contiguous().view(B)
+    return dp
+
+
 def _encoder_forward(m, img, need_global, saved, pos_in=None):
     assert img.is_cuda and img.dtype == torch.float32
     img = img.contiguous()
@@ -689,7 +744,7 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         pl = layer.plist() if layer.lora is None else layer.merged_plist()
         if P and i > 0:     # in place on the block above's output (no block keeps its own output for its backward)
             ops.prompt_rows_fwd(pemb[i * P:(i + 1) * P], B, P, x, mask=pmasks[i], scale=pscale)
-        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, TT, want_v, skip_x, sv)
+        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, TT, want_v, skip_x, sv, dp=_drop_path_masks(m, i, B, want_v, skip_x, dev))
         if saved is not None:
             if layer.lora is not None:
                 sv["plist"] = pl      # the backward's input-gradient GEMMs run on the same effective weights

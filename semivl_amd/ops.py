@@ -797,6 +797,41 @@ def prompt_rows_bwd(dx, Bn, P, out=None, mask=None, scale=1.0, accumulate=False,
     return out
 
 
+def _droppath_dims(x, mask, keep, Bn, T):
+    """E of the row matrix x [Bn * T, E] next to the per-sample mask [Bn]; -> (E, float32(1 / keep))"""
+    E = x.shape[-1]
+    assert x.dim() == 2 and x.is_contiguous() and x.shape[0] == Bn * T and Bn >= 1 and T >= 1 and E >= 1
+    assert mask.is_contiguous() and mask.numel() == Bn
+    assert 0.0 < keep <= 1.0, keep
+    return E, float(torch.tensor(1.0 / keep, dtype=torch.float32).item())
+
+
+def droppath_add(branch, resid, mask, keep, Bn, T, out=None):
+    """Stochastic depth at a residual site (svl_droppath_fwd_f32): out [Bn * T, E] = resid + (mask[b] / keep) * branch, b =
+    row // T; mask [Bn] fp32 (one draw per sample).  out None: in place in `branch` (out may be branch, never resid).  Rows of
+    a dropped sample are resid's own bits."""
+    E, scale = _droppath_dims(branch, mask, keep, Bn, T)
+    out = branch if out is None else out
+    assert resid.is_contiguous() and resid.shape == branch.shape and out.is_contiguous() and out.shape == branch.shape
+    e0 = _prof_begin()
+    L.check(L.load().svl_droppath_fwd_f32(_p(_chk(branch)), _p(_chk(resid)), _p(_chk(mask)), scale, _p(_chk(out)), Bn, T, E,
+                                          _st()), "svl_droppath_fwd_f32")
+    _prof_end("droppath_add", e0, 12.0 * Bn * T * E, (Bn, T, E))
+    return out
+
+
+def droppath_scale(dout, mask, keep, Bn, T):
+    """Gradient of a drop-path site's branch (svl_droppath_bwd_f32): a fresh [Bn * T, E] matrix (mask[b] / keep) * dout; rows
+    of a dropped sample are zeros."""
+    E, scale = _droppath_dims(dout, mask, keep, Bn, T)
+    out = empty(Bn * T, E, device=dout.device)
+    e0 = _prof_begin()
+    L.check(L.load().svl_droppath_bwd_f32(_p(_chk(dout)), _p(_chk(mask)), scale, _p(out), Bn, T, E, _st()),
+            "svl_droppath_bwd_f32")
+    _prof_end("droppath_scale", e0, 8.0 * Bn * T * E, (Bn, T, E))
+    return out
+
+
 def colsum(x2d, out=None, accumulate=False, C_=None, ld=None):
     rows = x2d.shape[0]
     Cc = C_ if C_ is not None else x2d.shape[1]

@@ -315,11 +315,20 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
             m_ = hook(layer, n)
             return None if m_ is None else torch.cat((m_[B:2 * B], m_[:B]))
         bb.prompt_mask_hook = _wx
+    # (and so do injected stochastic-depth masks, one value per sample)
+    dhook = getattr(bb, "drop_path_hook", None)
+    if dhook is not None:
+        def _wx_dp(layer, site, n, hook=dhook):
+            m_ = hook(layer, site, n)
+            return None if m_ is None else torch.cat((m_[B:2 * B], m_[:B]))
+        bb.drop_path_hook = _wx_dp
     try:
         preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **fwd_kw)
     finally:
         if phook is not None:
             bb.prompt_mask_hook = phook
+        if dhook is not None:
+            bb.drop_path_hook = dhook
     preds_s = model(_cat2(img_s1, img_s2), **fwd_kw)                                       # [s1, s2]
     pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:3 * B]
     pred_s1, pred_s2 = preds_s[:B], preds_s[B:]
