@@ -380,6 +380,12 @@ int svl_softmax_max_up_f32(const float* logits, int B, int N, int h, int w, int 
  * 'mean' = #(guidance label != 255) (nn.CrossEntropyLoss(ignore_index=255) mean); NULL = numel_u ('mean_all'). */
 int svl_semivl_gscale(const int64_t* counts, double numel_u, float lam, const double* factors, const int64_t* mc_counts,
                       float* gscale, svl_stream_t stream);
+/* The supervised baseline's normaliser (third_party/unimatch/supervised.py:281-283: the loss is the plain mean of the
+ * cross entropy over the kept pixels, weight 1).  out[0] (device float) = (float)(1.0 / (double)count[0]) for the device
+ * int64 count[0] >= 0 read as unsigned: the g_t of svl_ce_fused_f32 / svl_ce_up_fused_f32, formed without a host
+ * synchronisation.  Only out[0] is written: callers that pass it as `gscale` [2] zero g_m themselves.  count[0] == 0
+ * gives +inf, which no pixel then multiplies (every target is 255). */
+int svl_inv_count_f32(const int64_t* count, float* out, svl_stream_t stream);
 /* conf_mode 'pixelavg' (train_utils.py:43-46): factor[0] = sum over images b of mean_{valid pixels}(conf_b).  The
  * unsupervised branch loss is (sum over ALL pixels of CE) * factor / #valid.  `factors` above/below: double[3] device
  * for the branches {s1, s2, fp}, or NULL for 'pixelwise'. */

@@ -305,6 +305,11 @@ __global__ void semivl_gscale_kernel(const unsigned long long* counts, double nu
   gscale[4] = (float)(0.125 * f2 / c2);   gscale[5] = (float)(0.25 * lam / n2);
   gscale[6] = (float)(0.25 * f3 / c3);    gscale[7] = (float)(0.5 * lam / n3);
 }
+// out[0] = 1 / count[0]: the gradient scale of a loss that is a plain mean over `count` pixels (supervised.py:281-283)
+__global__ void inv_count_kernel(const unsigned long long* count, float* out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  out[0] = (float)(1.0 / (double)count[0]);
+}
 // factor = sum over images of (sum_p conf*valid) / (sum_p valid)   (train_utils.py:43-46, conf_mode 'pixelavg')
 // stage 1: grid (CONF_CHUNKS, B), per-(image, chunk) partial sums in double; stage 2: one block, fixed order.
 constexpr int CONF_CHUNKS = 64;
@@ -599,6 +604,13 @@ extern "C" int svl_semivl_gscale(const int64_t* counts, double numel_u, float la
   hipLaunchKernelGGL(semivl_gscale_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
                      (const unsigned long long*)counts, numel_u, lam, factors, (const unsigned long long*)mc_counts, gscale);
   SVL_LAUNCH_CHECK("svl_semivl_gscale");
+  return SVL_OK;
+}
+
+extern "C" int svl_inv_count_f32(const int64_t* count, float* out, svl_stream_t stream) {
+  SVL_CHECK_ARG(count && out, "svl_inv_count_f32: bad args");
+  hipLaunchKernelGGL(inv_count_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const unsigned long long*)count, out);
+  SVL_LAUNCH_CHECK("svl_inv_count_f32");
   return SVL_OK;
 }
 

@@ -267,28 +267,14 @@ def epoch_order(n, epoch, rank=0, world=1, seed=0):
     return idx[rank:total:world]
 
 
-class StepLoader:
-    """One epoch of `zip(loader_l, loader_u, loader_u)` (semivl.py:200-203) as ready step-input dicts on the GPU.
-
-    Both `loader_u` iterators of the reference share ONE sampler and epoch seed (SURVEY App. E.8): the "other" unlabeled
-    batch holds the same image ids as the first, re-augmented -- reproduced here by augmenting every unlabeled sample
-    twice.  Decoding runs in `workers` host threads (PIL releases the GIL), at most `prefetch` batches ahead; the GPU
-    augmentation of batch k+1 is issued on a side stream while step k runs, and the consumer's stream waits on it
-    (event-ordered, no host sync) when the batch is handed over."""
-
-    def __init__(self, labeled, unlabeled, augmenter, batch_size, epoch=0, rank=0, world=1, workers=4, prefetch=2):
-        self.l, self.u, self.aug, self.bs = labeled, unlabeled, augmenter, batch_size
-        self.order_l = epoch_order(len(labeled), epoch, rank, world)
-        self.order_u = epoch_order(len(unlabeled), epoch, rank, world)
-        self.steps = min(len(self.order_l), len(self.order_u)) // batch_size     # drop_last=True (semivl.py:171-178)
-        self.workers, self.prefetch = workers, prefetch
+class _PrefetchLoader:
+    """The hand-over both loaders share: batches are decoded in `workers` host threads (PIL releases the GIL), at most
+    `prefetch` batches ahead; the GPU augmentation of batch k+1 is issued on a side stream while step k runs, and the
+    consumer's stream waits on it (event-ordered, no host sync) when the batch is handed over.  Subclasses set `steps`,
+    `aug`, `workers`, `prefetch` and define `_decode(k)` (host side) and `_augment(host)` (-> dict of device tensors)."""
 
     def __len__(self):
         return self.steps
-
-    def _decode(self, k):
-        s = slice(k * self.bs, (k + 1) * self.bs)
-        return ([self.l[i][:2] for i in self.order_l[s]], [self.u[i][:2] for i in self.order_u[s]])
 
     def __iter__(self):
         from concurrent.futures import ThreadPoolExecutor
@@ -305,11 +291,10 @@ class StepLoader:
                 nxt += 1
 
         def augment(host):
-            lab, unl = host
             if side is None:
-                return self.aug.batch(lab, unl, unl), None
+                return self._augment(host), None
             with torch.cuda.stream(side):
-                b = self.aug.batch(lab, unl, unl)
+                b = self._augment(host)
                 ev = torch.cuda.Event()
                 ev.record(side)
             return b, ev
@@ -330,3 +315,48 @@ class StepLoader:
                 yield batch
         finally:
             pool.shutdown(wait=False, cancel_futures=True)
+
+
+class StepLoader(_PrefetchLoader):
+    """One epoch of `zip(loader_l, loader_u, loader_u)` (semivl.py:200-203) as ready step-input dicts on the GPU.
+
+    Both `loader_u` iterators of the reference share ONE sampler and epoch seed (SURVEY App. E.8): the "other" unlabeled
+    batch holds the same image ids as the first, re-augmented -- reproduced here by augmenting every unlabeled sample
+    twice.  Decoding runs in `workers` host threads (PIL releases the GIL), at most `prefetch` batches ahead; the GPU
+    augmentation of batch k+1 is issued on a side stream while step k runs, and the consumer's stream waits on it
+    (event-ordered, no host sync) when the batch is handed over."""
+
+    def __init__(self, labeled, unlabeled, augmenter, batch_size, epoch=0, rank=0, world=1, workers=4, prefetch=2):
+        self.l, self.u, self.aug, self.bs = labeled, unlabeled, augmenter, batch_size
+        self.order_l = epoch_order(len(labeled), epoch, rank, world)
+        self.order_u = epoch_order(len(unlabeled), epoch, rank, world)
+        self.steps = min(len(self.order_l), len(self.order_u)) // batch_size     # drop_last=True (semivl.py:171-178)
+        self.workers, self.prefetch = workers, prefetch
+
+    def _decode(self, k):
+        s = slice(k * self.bs, (k + 1) * self.bs)
+        return ([self.l[i][:2] for i in self.order_l[s]], [self.u[i][:2] for i in self.order_u[s]])
+
+    def _augment(self, host):
+        lab, unl = host
+        return self.aug.batch(lab, unl, unl)
+
+
+class LabeledLoader(_PrefetchLoader):
+    """One epoch of the supervised baseline's loader (third_party/unimatch/supervised.py:239-244) as ready
+    `dict(img_x, mask_x)` batches on the GPU for `train.supervised_train_step`: the labelled set as its split file lists
+    it -- build the SemiDataset WITHOUT `nsample`, the baseline does not repeat ids -- in `epoch_order`, drop_last=True,
+    every sample through `GpuAugmenter.train_l`; decode-ahead and hand-over as in StepLoader."""
+
+    def __init__(self, labeled, augmenter, batch_size, epoch=0, rank=0, world=1, workers=4, prefetch=2):
+        self.l, self.aug, self.bs = labeled, augmenter, batch_size
+        self.order_l = epoch_order(len(labeled), epoch, rank, world)
+        self.steps = len(self.order_l) // batch_size
+        self.workers, self.prefetch = workers, prefetch
+
+    def _decode(self, k):
+        return [self.l[i][:2] for i in self.order_l[k * self.bs:(k + 1) * self.bs]]
+
+    def _augment(self, host):
+        xs = [self.aug.train_l(i, m) for i, m in host]
+        return dict(img_x=torch.stack([x[0] for x in xs]), mask_x=torch.stack([x[1] for x in xs]))

@@ -104,6 +104,7 @@ SIGNATURES = {
     "svl_softmax_max_up_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "svl_semivl_gscale": (_I, [_P, _D, _F, _P, _P, _P, _P]),
     "svl_semivl_loss": (_I, [_P, _D, _F, _P, _P, _P, _P]),
+    "svl_inv_count_f32": (_I, [_P, _P, _P]),
     "svl_conf_ratio_f32": (_I, [_P, _P, _I, _L, _F, _P, _P, _P]),
     "svl_conf_avg_ws_doubles": (_L, [_I]),
     "svl_conf_avg_factor": (_I, [_P, _P, _I, _L, _P, _P, _P]),

@@ -182,6 +182,9 @@ class VLM(nn.Module):
     def forward_maskclip(self, img, conf_tresh, ignore_mask=None):
         """int64 [b, H, W] in {0..N-1, 255}.  `ignore_mask` (optional, fused form of semivl.py:239-240): pixels where
         it equals 255 are set to 255."""
+        if self.clip_encoder is None:
+            raise RuntimeError("VLM.forward_maskclip: this model was built without a clip_encoder (cfg['clip_encoder'] = "
+                               "None); there is no MaskCLIP guidance to compute")
         with torch.no_grad():
             img = self.renormalize_img_for_clip(img)
             feats, _ = self.clip_encoder.forward_tokens(img, need_global=False)

@@ -1743,6 +1743,11 @@ def semivl_gscale(counts_i64, numel_u, lam, gscale_out, factors=None, mc_counts=
                                        _p(gscale_out), _st()), "svl_semivl_gscale")
 
 
+def inv_count(count_i64, out):
+    """out[0] (fp32 view) = 1 / count_i64[0] on the device (svl_inv_count_f32): the gradient scale of a plain mean."""
+    L.check(L.load().svl_inv_count_f32(_p(count_i64), _p(out), _st()), "svl_inv_count_f32")
+
+
 def semivl_loss(sums_f64, numel_u, lam, out8, factors=None, mc_counts=None):
     L.check(L.load().svl_semivl_loss(_p(sums_f64), float(numel_u), float(lam), _p(factors), _p(mc_counts), _p(out8),
                                      _st()), "svl_semivl_loss")

@@ -162,17 +162,15 @@ def step_helper_streams(streams):
 LOSS_NAMES = ("loss", "loss_x", "loss_s1", "loss_s2", "loss_fp", "loss_mc_s1", "loss_mc_s2", "loss_mc_fp")
 
 
-def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                      return_aux=False):
-    """One iteration of semivl.py:223-328 (see _semivl_train_step for the body).  Per-step overrides taken from `cfg`
-    (`wgrad_stream`, `overlap_streams`, `head_remat`, `head_chunk_class_images`) and the decode head's per-step memory
-    plan are undone when the step ends -- also when it raises -- so that a later grad-enabled decode outside a training
-    step (validation with gradients, a test, another batch size) never inherits a stale decision."""
+@contextlib.contextmanager
+def _step_scope(model, head_attrs=("remat", "chunk_class_images")):
+    """The per-step overrides of a training step (ops.WGRAD_STREAM, the decode head's `head_attrs` and its per-step memory
+    plan) are undone when the block ends -- also when it raises."""
     head = getattr(model, "decode_head", None)
     keep_wg = ops.WGRAD_STREAM
-    keep_head = {a_: getattr(head, a_) for a_ in ("remat", "chunk_class_images") if head is not None and hasattr(head, a_)}
+    keep_head = {a_: getattr(head, a_) for a_ in head_attrs if head is not None and hasattr(head, a_)}
     try:
-        return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux)
+        yield
     finally:
         ops.WGRAD_STREAM = keep_wg
         if head is not None:
@@ -184,6 +182,117 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
             head._live_class_images = None
             for a_, v_ in keep_head.items():
                 setattr(head, a_, v_)
+
+
+def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
+                      return_aux=False):
+    """One iteration of semivl.py:223-328 (see _semivl_train_step for the body).  Per-step overrides taken from `cfg`
+    (`wgrad_stream`, `overlap_streams`, `head_remat`, `head_chunk_class_images`) and the decode head's per-step memory
+    plan are undone when the step ends -- also when it raises -- so that a later grad-enabled decode outside a training
+    step (validation with gradients, a test, another batch size) never inherits a stale decision.
+
+    The MaskCLIP guidance follows the reference's own test, `cfg['maskclip_consistency_lambda'] != 0` (semivl.py:158,234,
+    283,296,309): a scalar 0 / 0.0 switches it off -- no frozen-encoder forward, no guidance maps, `mc = NULL` in the three
+    unlabelled cross entropies, `losses[5:8]` exactly 0, `aux['mclip']` / `aux['mclip_other']` None -- whether or not the
+    model has a `clip_encoder`; a list or tuple (also [0, 0]) or a missing key keeps it on, and then a model built with
+    `clip_encoder=None` is refused with a ValueError before the step touches anything."""
+    with _step_scope(model):
+        return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux)
+
+
+def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, return_aux=False):
+    """One iteration of the labelled-only baseline, third_party/unimatch/supervised.py:268-301 (method 'supervised').
+    `batch`: dict with `img_x` [B, 3, S, S] fp32 and `mask_x` [B, S, S] int64 on the GPU (data.LabeledLoader,
+    synthetic_batch).  model.train(), ONE forward on img_x, criterion from supervised_criterion(cfg) (cross entropy with
+    ignore 255, or OHEM relabelling on the device followed by the same cross entropy), loss = the plain mean over the kept
+    pixels (weight 1, not the 1/2 of semivl.py:319); its gradient scale 1 / count is formed on the device
+    (svl_inv_count_f32): no host sync.  Then optimizer.zero_grad(), backward (reducer.begin() / finish() around it),
+    optimizer.step() and optimizer.poly_lr(iters, total_iters) -- supervised.py:294-300 has no warm-up and no
+    scheduler_max_iters, so cfg's `warmup_iters` / `scheduler_max_iters` are ignored here.
+    Returns the device tensor `loss` [1]; with `return_aux` also dict(pred_x [B, N, S, S], dlogits, mask_x_ohem (None
+    without OHEM), upsample_in_loss).  Per-step overrides taken from `cfg` (`wgrad_stream`, `overlap_streams`,
+    `head_remat`, `head_chunk_class_images`, `act_mem_fraction`) are set up for one decode of B samples and undone when
+    the step ends -- also when it raises -- as in semivl_train_step."""
+    with _step_scope(model, ("remat", "chunk_class_images", "act_limit_bytes")):
+        return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux)
+
+
+def _head_res(model, img, cfg):
+    """`up` = (H, W, align_corners) when the logits can stay at the head's resolution (the bilinear resize to the crop is then
+    evaluated inside the softmax-max / cross-entropy kernels), else None: models without the option, geometries the kernels
+    do not take, cfg['fuse_upsample_loss'] / SVL_NO_UP_LOSS."""
+    if img.is_cuda and cfg.get("fuse_upsample_loss", ops.UP_LOSS) and hasattr(model, "head_res_size"):
+        hs = model.head_res_size(tuple(img.shape[2:]))
+        if hs is not None and ops.ce_up_ok(img.shape[0], model.num_classes, hs[0], hs[1], img.shape[2], img.shape[3],
+                                           model.align_corners):
+            return (int(img.shape[2]), int(img.shape[3]), bool(model.align_corners))
+    return None
+
+
+def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux):
+    ohem = supervised_criterion(cfg)                     # supervised.py:222-231 (raises on what the kernels cannot do)
+    img_x, mask_x = batch["img_x"], batch["mask_x"]
+    B, dev = img_x.shape[0], img_x.device
+    if "wgrad_stream" in cfg:
+        ops.WGRAD_STREAM = bool(cfg["wgrad_stream"])
+    elif not cfg.get("overlap_streams", True):
+        ops.WGRAD_STREAM = False
+    head = getattr(model, "decode_head", None)
+    if head is not None:    # one grad-carrying decode of B samples, every sample live
+        head._bwd_ranges = None
+        head._live_class_images = B * head.num_classes
+        head._remat_step = {}
+        if "head_remat" in cfg:
+            head.remat = cfg["head_remat"]
+        if cfg.get("head_chunk_class_images"):
+            head.chunk_class_images = int(cfg["head_chunk_class_images"])
+        frac = cfg.get("act_mem_fraction", 0.70)
+        head.act_limit_bytes = (None if frac is None or not img_x.is_cuda else
+                                int(frac * torch.cuda.get_device_properties(dev).total_memory))
+    # (the cross-entropy kernels index the label map by the logits' geometry: a map of another shape is refused here)
+    if mask_x.dtype != torch.int64 or tuple(mask_x.shape) != (B,) + tuple(img_x.shape[2:]):
+        raise ValueError(f"supervised_train_step: mask_x {tuple(mask_x.shape)} {mask_x.dtype} does not match img_x "
+                         f"{tuple(img_x.shape)} (expected int64 [B, S, S])")
+    mask_x = mask_x.contiguous()
+    if reducer is not None:
+        reducer.begin()
+    up = _head_res(model, img_x, cfg)
+    model.train()                                        # supervised.py:268
+    pred = model(img_x, **(dict(head_res=True) if up is not None else {}))     # :277
+    count = ops.zeros(1, dtype=torch.int64, device=dev)
+    mask_x_ohem = None
+    if ohem is not None:    # criterion = OHEM: the plain CE on the relabelled map, its count as normaliser
+        mask_x = mask_x_ohem = ohem.relabel(pred, mask_x, up=up, counts_out=count)
+    else:
+        ops.count_valid(mask_x, count)
+    gscale = ops.zeros(2, device=dev)                    # {g_t, g_m}: g_m stays 0
+    ops.inv_count(count, gscale)
+    dlogits = torch.empty_like(pred)
+    # sums[0] = {sum ce, 0, 0, #kept}; svl_semivl_loss's `loss_x` slot is sums[0][0] / sums[0][3] -- the mean, weight 1 (:279).
+    # The other three branches do not exist here: their rows are zero and their slots of `out` are never read.
+    sums = ops.zeros(4, 4, dtype=torch.float64, device=dev)
+    if up is not None:
+        ops.ce_up_fused(pred.detach(), up[0], up[1], up[2], mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0])
+    else:
+        ops.ce_fused(pred.detach(), mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0])
+    out = ops.empty(8, device=dev)
+    ops.semivl_loss(sums, float(mask_x.numel()), 0.0, out)
+    loss = out[1:2]
+    if optimizer is not None:
+        optimizer.zero_grad()                            # :285
+    torch.autograd.backward([pred], [dlogits])           # :286
+    if reducer is not None:
+        reducer.finish()
+    if optimizer is not None:
+        optimizer.step()                                 # :287
+        optimizer.poly_lr(iters, total_iters)            # :294-300: lr * (1 - iters / total_iters) ** 0.9, nothing else
+    if return_aux:
+        pred_x = pred.detach()
+        if up is not None:
+            pred_x = pred_x.contiguous()
+            pred_x = ops.bilinear_planes_fwd(pred_x, pred_x.shape[2], pred_x.shape[3], up[2], up[0], up[1])
+        return loss, dict(pred_x=pred_x, dlogits=dlogits, mask_x_ohem=mask_x_ohem, upsample_in_loss=up is not None)
+    return loss
 
 
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
@@ -207,6 +316,16 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         lam = lam_cfg[0] * (1 - prog) + lam_cfg[1] * prog
     else:
         lam = lam_cfg
+    # semivl.py:158: the reference builds the guidance criterion, runs the frozen encoder (:234) and adds the three guidance
+    # terms (:283,296,309) only `if cfg['maskclip_consistency_lambda'] != 0` -- a scalar 0 switches all of it off, a list
+    # (even [0, 0]) or a missing key keeps it on
+    guided = lam_cfg != 0
+    if not guided:
+        lam = 0.0
+    elif getattr(model, "clip_encoder", None) is None:
+        raise ValueError(f"semivl_train_step: maskclip_consistency_lambda={lam_cfg!r} asks for the MaskCLIP guidance but the "
+                         f"model was built with clip_encoder=None; set maskclip_consistency_lambda=0 (experiment 41's rows) "
+                         f"or build the model with a clip_encoder")
     b = batch
     img_x, mask_x = b["img_x"], b["mask_x"]
     img_w, img_s1, img_s2 = b["img_w"], b["img_s1"], b["img_s2"]
@@ -242,6 +361,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     # (the same holds for a decode head with BatchNorm -- the DeepLabV3+ head: `has_batchnorm`)
     head_bn = bool(getattr(getattr(model, "decode_head", None), "has_batchnorm", False))
     pl_side = side if (getattr(model, "conv_encoder", None) is None and not head_bn) else None
+    if not guided and pl_side is None:
+        side = None         # nothing would run there: no fork, no join
     # The logits stay at the head's resolution (round 5): the bilinear resize to the crop (vlg_head.py:247, builder.py:93-97)
     # is evaluated inside the softmax-max / cross-entropy kernels and the gradient comes back at the head's resolution --
     # the [B, N, H, W] tensors and the two resize passes do not exist.  `up` = (H, W, align_corners) or None (models without
@@ -272,10 +393,12 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         conf_w_other, mask_w_other = smax(pred_w_other)
         if not return_aux:
             del pred_w_other
-    with torch.no_grad(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-        mclip_all = model.forward_maskclip(_cat2(img_w, b["img_w_other"]), cfg.get("mcc_conf_thresh", 0.9),
-                                           ignore_mask=_cat2i(ign, ign_o))
-        mclip, mclip_other = mclip_all[:B], mclip_all[B:]
+    mclip_all = mclip = mclip_other = None
+    if guided:
+        with torch.no_grad(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            mclip_all = model.forward_maskclip(_cat2(img_w, b["img_w_other"]), cfg.get("mcc_conf_thresh", 0.9),
+                                               ignore_mask=_cat2i(ign, ign_o))
+            mclip, mclip_other = mclip_all[:B], mclip_all[B:]
     model.train()          # semivl.py:246: unconditionally back to train mode
     # predictions
     # the feature-perturbed copy of the labeled half (pred_x_fp) is never read by the step (semivl.py:247): only the
@@ -335,13 +458,15 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     conf_w, mask_w = smax(pred_w.detach())
     if side is not None:        # join: the label maps of the side stream are consumed from here on
         main.wait_stream(side)
-        for t_ in ((conf_w_other, mask_w_other, mclip_all) if pl_side is not None else (mclip_all,)):
+        for t_ in ((conf_w_other, mask_w_other) if pl_side is not None else ()) + ((mclip_all,) if guided else ()):
             t_.record_stream(main)
     # CutMix labels
     mw1, mw2 = cutmix_mask(mask_w, mask_w_other, mix1), cutmix_mask(mask_w, mask_w_other, mix2)
     cw1, cw2 = cutmix_mask(conf_w, conf_w_other, mix1), cutmix_mask(conf_w, conf_w_other, mix2)
     ig1, ig2 = cutmix_mask(ign, ign_o, mix1), cutmix_mask(ign, ign_o, mix2)
-    mc1, mc2 = cutmix_mask(mclip, mclip_other, mix1), cutmix_mask(mclip, mclip_other, mix2)
+    mc1 = mc2 = None        # (not guided: the cross-entropy kernels take mc == NULL, their guidance sums stay 0)
+    if guided:
+        mc1, mc2 = cutmix_mask(mclip, mclip_other, mix1), cutmix_mask(mclip, mclip_other, mix2)
     # normalisers -> per-branch gradient scales, on the device
     counts = ops.zeros(4, dtype=torch.int64, device=dev)
     mask_x_ohem = None
@@ -361,7 +486,9 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     if conf_mode == "pixelratio":   # train_utils.py:39-42: image b's CE map times its share of confident valid pixels
         ratios = tuple(ops.conf_ratio(c_, g_, cfg["conf_thresh"]) for c_, g_ in ((cw1, ig1), (cw2, ig2), (conf_w, ign)))
     mc_counts = None                # semivl.py:52-58: the guidance loss's normaliser
-    if mcc_reduce == "mean_valid":
+    if not guided:
+        pass                        # no guidance term: no normaliser either ('mean' would count 0 labelled pixels -> 0 * x / 0)
+    elif mcc_reduce == "mean_valid":
         mc_counts = counts[1:]
     elif mcc_reduce == "mean":      # nn.CrossEntropyLoss(ignore_index=255): mean over the labelled guidance pixels
         mc_counts = ops.zeros(3, dtype=torch.int64, device=dev)
