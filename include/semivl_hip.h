@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 605: + svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32, svl_ce_up_lsw_num_blocks, svl_class_weight_sum_f64, svl_class_weight_sum_ws_doubles, svl_scale_from_sum_f32 (label_smoothing / class weights of the labelled cross entropy); 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -318,6 +318,13 @@ int svl_cutmix_i64(int64_t* out, const int64_t* a, const int64_t* b, const float
  * svl_ce_finalize() reduces the partials in double, in a fixed order, to sums[4].
  * If dlogits != NULL: dlogits = gscale_t * w_t * (softmax - onehot(target)) + gscale_m * [mc valid] * (softmax - onehot(mc))
  * where gscale_* are read from DEVICE memory (gscale[0], gscale[1]) so no host sync is needed.
+ *
+ * svl_ce_fused_lsw_f32 / svl_ce_up_fused_lsw_f32 (the labelled criterion with label_smoothing eps and class weights w,
+ * below) fill the same four slots with another meaning: partials[blk] = {
+ *   sum_p [t != 255] ( (1 - eps) w_t ce_t(p) + (eps / N) sum_c w_c (-log_softmax(logits)[c]) ),
+ *   0, 0,
+ *   sum_p [t != 255] w_t }       (integer-valued without weights: the count of labelled pixels)
+ * so that sums[0] / sums[3] is torch's weighted, smoothed mean and svl_semivl_loss reads it unchanged.
  */
 typedef struct svl_ce_desc {
   const float* logits;   /* [B, N, HW] */
@@ -339,6 +346,16 @@ typedef struct svl_ce_desc {
 int64_t svl_ce_num_blocks(int B, int N, int64_t HW); /* -1 if N is unsupported (N > 256) */
 int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t stream);
 int svl_ce_finalize(const float* partials, int64_t nblocks, double* sums /* [4] device */, svl_stream_t stream);
+/* The labelled criterion as nn.CrossEntropyLoss(ignore_index=255, label_smoothing=eps, weight=w) (semivl.py:142-143: the
+ * reference passes cfg['criterion']['kwargs'] to torch).  With W = sum_c w_c, p = softmax(logits), lse = logsumexp(logits):
+ *   numerator(pixel) = (1 - eps) w_t (lse - x_t) + (eps / N) sum_c w_c (lse - x_c)                  (t != 255, else 0)
+ *   dlogits_c = g [t != 255] ( (1 - eps) w_t (p_c - [c == t]) + (eps / N) (W p_c - w_c) ),   g = gscale[0] (device)
+ * and the loss is sum numerator / sum [t != 255] w_t: partials as described above, reduced by svl_ce_finalize.
+ * label_smoothing in [0, 1]; class_weight: float[N] on the device, or NULL for all ones.  Labelled branch only: a
+ * descriptor with conf, ign, mc_target, img_weight or all_pixels set, or with use_ignore_t == 0, is refused (status -1,
+ * the message names the field).  Same workspace (svl_ce_num_blocks), tiling and determinism as svl_ce_fused_f32; an
+ * ignored pixel's gradient is exactly 0 and is never multiplied by g (g is 1 / 0 when every target is 255). */
+int svl_ce_fused_lsw_f32(const svl_ce_desc* d, float label_smoothing, const float* class_weight, svl_stream_t stream);
 
 /* Round 5: the same two pixel-loss entry points on logits that exist ONLY at the head's resolution.  The reference
  * resizes the head's [B, N, h, w] map to the crop (vlg_head.py:247, builder.py:93-97: bilinear, align_corners as
@@ -367,6 +384,12 @@ typedef struct svl_ce_up_desc {
 } svl_ce_up_desc;
 int64_t svl_ce_up_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners);
 int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t stream);
+/* svl_ce_fused_lsw_f32 on the resized logits (same formulas, refusals and partials; the gradient arrives at the head's
+ * resolution).  Its kernel stages the class weights in LDS beside the tile, so it has its own host-only geometry query:
+ * svl_ce_up_lsw_num_blocks is the size of `partials` in blocks, or -1 when the geometry is unsupported or does not fit the
+ * 160 KB of LDS (callers then resize with svl_bilinear_planes_fwd and use svl_ce_fused_lsw_f32). */
+int64_t svl_ce_up_lsw_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners);
+int svl_ce_up_fused_lsw_f32(const svl_ce_up_desc* d, float label_smoothing, const float* class_weight, svl_stream_t stream);
 /* conf / label [B, H, W] = softmax(dim 1).max(dim 1) of the resized logits (semivl.py:232,252); first maximum wins. */
 int svl_softmax_max_up_f32(const float* logits, int B, int N, int h, int w, int H, int W, int align_corners, float* conf,
                            int64_t* label, svl_stream_t stream);
@@ -386,6 +409,18 @@ int svl_semivl_gscale(const int64_t* counts, double numel_u, float lam, const do
  * synchronisation.  Only out[0] is written: callers that pass it as `gscale` [2] zero g_m themselves.  count[0] == 0
  * gives +inf, which no pixel then multiplies (every target is 255). */
 int svl_inv_count_f32(const int64_t* count, float* out, svl_stream_t stream);
+/* The normaliser of a class-weighted mean (nn.CrossEntropyLoss(weight=w), reduction 'mean'), without a host
+ * synchronisation: sum[0] (device double) = sum over the n pixels with target != 255 of class_weight[target], accumulated
+ * in double in two stages with a fixed order (deterministic); a label outside [0, N) adds nothing.  class_weight: float[N]
+ * on the device.  workspace: svl_class_weight_sum_ws_doubles(n) doubles of device memory, caller-owned, no initialisation. */
+int64_t svl_class_weight_sum_ws_doubles(int64_t n);
+int svl_class_weight_sum_f64(const int64_t* target, int64_t n, const float* class_weight, int N, double* sum,
+                             double* workspace, svl_stream_t stream);
+/* out[0] (device float) = (float)(factor / sum[0]) for the device double sum[0]: the weighted counterpart of
+ * svl_inv_count_f32 (factor 1 for the supervised step, 0.5 for the labelled branch of the semi-supervised one, where it
+ * overwrites gscale[0][0] after svl_semivl_gscale).  Only out[0] is written; sum[0] == 0 gives +inf, which no pixel
+ * then multiplies. */
+int svl_scale_from_sum_f32(const double* sum, double factor, float* out, svl_stream_t stream);
 /* conf_mode 'pixelavg' (train_utils.py:43-46): factor[0] = sum over images b of mean_{valid pixels}(conf_b).  The
  * unsupervised branch loss is (sum over ALL pixels of CE) * factor / #valid.  `factors` above/below: double[3] device
  * for the branches {s1, s2, fp}, or NULL for 'pixelwise'. */

@@ -106,6 +106,14 @@ struct CeP {
   int P;             // pixels per block
   long blocks_per_img;
 };
+// The labelled criterion's label_smoothing / class weights (nn.CrossEntropyLoss(**cfg['criterion']['kwargs']), semivl.py:142-143):
+// a separate instantiation of ce_fused_kernel, so that the plain one keeps its code, its LDS and its kernel arguments.
+struct CeLswP : CeP {
+  float eps;         // label_smoothing
+  const float* cw;   // [N] class weights or null (all ones)
+};
+template <bool LSW> struct ce_param { using type = CeP; };
+template <> struct ce_param<true> { using type = CeLswP; };
 
 // Round 4: the kernel moved 4.6 TB/s (0.58 of the 8 TB/s peak on its real PMC bytes).  It was latency-, not bandwidth-bound:
 // the tile loop issued ONE 16 B load per thread and waited for it before the LDS store (28 KB in flight per CU with seven
@@ -113,10 +121,26 @@ struct CeP {
 // rows of its column quad before the first LDS store (no index division in the loop: thread = (row r, quad q), rows r, r +
 // R, ...), the maps are requested before the tile, the exponentials are computed once (the tile holds exp(x - max) for the
 // gradient pass) and the four block sums share one barrier.
-__global__ __launch_bounds__(256) void ce_fused_kernel(const CeP p) {
+//
+// LSW (labelled branch only: conf / ign / mc / img_weight are refused on the host): with eps = label_smoothing, w = class
+// weights (ones when absent), W = sum_c w_c and g = gscale[0]
+//   numerator(pixel) = (1 - eps) w_t (lse - x_t) + (eps / N) (W lse - sum_c w_c x_c)         (target != 255, else 0)
+//   dlogits_c        = a p_c - b [c == t] - e w_c,   a = g ((1 - eps) w_t + (eps / N) W), b = g (1 - eps) w_t, e = g eps / N
+// partials[block] = { sum numerator, 0, 0, sum [t != 255] w_t }.  w is staged in LDS once per block; sum_c w_c x_c is formed in
+// the maximum's class loop (before the tile is overwritten with the exponentials) and meets in LDS in part order like m and s.
+template <bool LSW>
+__global__ __launch_bounds__(256) void ce_fused_kernel(const typename ce_param<LSW>::type p) {
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [N][P]
   __shared__ float red[4][4];
   __shared__ float part[2][256];          // per-(class part, pixel) partial max / partial sum when P < 256
+  float* wsh = nullptr;                   // LSW: the class weights [N <= 256] and the partial sum_c w_c x_c
+  float* part_wx = nullptr;
+  if constexpr (LSW) {
+    __shared__ float wsh_[256];
+    __shared__ float part_wx_[256];
+    wsh = wsh_;
+    part_wx = part_wx_;
+  }
   const int tid = threadIdx.x;
   const long blk = blockIdx.x;
   const long b = blk / p.blocks_per_img;
@@ -138,6 +162,9 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const CeP p) {
     t = p.target[o];
     if (p.conf) { ig = p.ign[o]; cf = p.conf[o]; }
     if (p.mc) mm = p.mc[o];
+  }
+  if constexpr (LSW) {
+    for (int c = tid; c < p.N; c += 256) wsh[c] = p.cw ? p.cw[c] : 1.f;
   }
   constexpr int LU = 8;
   const int q4 = np >> 2;
@@ -172,16 +199,34 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const CeP p) {
   const bool t_ok = !(p.use_ignore_t && t == 255);
   const int ti = (act && t_ok) ? (int)t : -1;
   const int mi = (act && p.mc && mm != 255) ? (int)mm : -1;
-  if (act) {
+  float swx = 0.f, wsum = 0.f, wt = 0.f;          // LSW: sum_c w_c x_c, W, w_t (0 for a label outside [0, N))
+  if constexpr (LSW) {
+    for (int c = 0; c < p.N; ++c) wsum += wsh[c];  // (class order: the same W in every thread and block)
+    if (act) {
+      for (int c = prt; c < p.N; c += K) {
+        const float x = tile[c * P + pix];
+        m = fmaxf(m, x);
+        swx = fmaf(wsh[c], x, swx);
+      }
+      const bool in = ti >= 0 && ti < p.N;
+      xt = in ? tile[ti * P + pix] : 0.f;
+      wt = in ? wsh[ti] : 0.f;
+    }
+  } else if (act) {
     for (int c = prt; c < p.N; c += K) m = fmaxf(m, tile[c * P + pix]);
     xt = ti >= 0 ? tile[ti * P + pix] : 0.f;      // (read before the exp pass overwrites the tile)
     xm = mi >= 0 ? tile[mi * P + pix] : 0.f;
   }
   if (K > 1) {                                    // (block-uniform)
     part[0][tid] = m;
+    if constexpr (LSW) part_wx[tid] = swx;
     __syncthreads();
     m = part[0][pix];
     for (int k = 1; k < K; ++k) m = fmaxf(m, part[0][k * P + pix]);
+    if constexpr (LSW) {
+      swx = part_wx[pix];
+      for (int k = 1; k < K; ++k) swx += part_wx[k * P + pix];
+    }
   }
   if (act) {
     for (int c = prt; c < p.N; c += K) {
@@ -196,7 +241,27 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const CeP p) {
     s = part[1][pix];
     for (int k = 1; k < K; ++k) s += part[1][k * P + pix];
   }
-  if (act) {
+  if constexpr (LSW) {
+    if (act) {
+      const float lse = m + logf(s);
+      const float en = p.eps / (float)p.N, om = 1.f - p.eps;
+      if (prt == 0 && t_ok) {                       // the pixel's scalars are counted once
+        n_v = wt;
+        s_t = om * wt * (lse - xt) + en * (wsum * lse - swx);
+      }
+      if (p.dlogits) {
+        // (an ignored pixel multiplies nothing: with every target 255 the scale is 1 / 0)
+        const float g = t_ok ? p.gscale[0] : 0.f;
+        const float ga = t_ok ? g * (om * wt + en * wsum) : 0.f, gb = t_ok ? g * om * wt : 0.f, ge = t_ok ? g * en : 0.f;
+        const float inv = 1.f / s;
+        for (int c = prt; c < p.N; c += K) {
+          float d = ga * (tile[c * P + pix] * inv) - ge * wsh[c];
+          if (c == ti) d -= gb;
+          tile[c * P + pix] = t_ok ? d : 0.f;
+        }
+      }
+    }
+  } else if (act) {
     const float lse = m + logf(s);
     float w = 1.f;
     bool valid = t_ok;
@@ -309,6 +374,37 @@ __global__ void semivl_gscale_kernel(const unsigned long long* counts, double nu
 __global__ void inv_count_kernel(const unsigned long long* count, float* out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   out[0] = (float)(1.0 / (double)count[0]);
+}
+// out[0] = factor / sum[0]: the gradient scale of a class-weighted mean, whose normaliser D = sum [t != 255] w_t is a double
+__global__ void scale_from_sum_kernel(const double* sum, double factor, float* out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  out[0] = (float)(factor / sum[0]);
+}
+// D = sum over the pixels with target != 255 of w[target], in double (a label outside [0, N) adds nothing).
+// stage 1: CW_CHUNKS blocks, one contiguous chunk each, fixed shuffle tree; stage 2: one thread, chunk order.
+constexpr int CW_CHUNKS = 128;
+__global__ __launch_bounds__(256) void class_weight_sum_partial_kernel(const int64_t* __restrict__ target, long n,
+                                                                       const float* __restrict__ cw, int N,
+                                                                       double* __restrict__ part) {
+  __shared__ double sh[4];
+  const long per = (n + CW_CHUNKS - 1) / CW_CHUNKS;
+  const long i0 = (long)blockIdx.x * per, i1 = min(n, i0 + per);
+  double s = 0.0;
+  for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const long t = target[i];
+    if (t != 255 && t >= 0 && t < N) s += (double)cw[t];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ void class_weight_sum_final_kernel(const double* __restrict__ part, double* __restrict__ sum) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double tot = 0.0;
+  for (int k = 0; k < CW_CHUNKS; ++k) tot += part[k];
+  sum[0] = tot;
 }
 // factor = sum over images of (sum_p conf*valid) / (sum_p valid)   (train_utils.py:43-46, conf_mode 'pixelavg')
 // stage 1: grid (CONF_CHUNKS, B), per-(image, chunk) partial sums in double; stage 2: one block, fixed order.
@@ -561,8 +657,61 @@ extern "C" int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t stream) {
   p.blocks_per_img = (d->HW + P - 1) / P;
   const long nblk = (long)d->B * p.blocks_per_img;
   const size_t lds = (size_t)d->N * P * sizeof(float);
-  hipLaunchKernelGGL(ce_fused_kernel, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(ce_fused_kernel<false>, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
   SVL_LAUNCH_CHECK("svl_ce_fused_f32");
+  return SVL_OK;
+}
+
+extern "C" int svl_ce_fused_lsw_f32(const svl_ce_desc* d, float label_smoothing, const float* class_weight,
+                                    svl_stream_t stream) {
+  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_fused_lsw_f32: null args");
+  SVL_CHECK_ARG(d->B > 0 && d->N > 0 && d->HW > 0, "svl_ce_fused_lsw_f32: bad sizes");
+  SVL_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "svl_ce_fused_lsw_f32: label_smoothing=%g outside [0, 1]",
+                (double)label_smoothing);
+  // labelled branch only
+  SVL_CHECK_ARG(d->conf == nullptr, "svl_ce_fused_lsw_f32: conf must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->ign == nullptr, "svl_ce_fused_lsw_f32: ign must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->mc_target == nullptr, "svl_ce_fused_lsw_f32: mc_target must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->img_weight == nullptr, "svl_ce_fused_lsw_f32: img_weight must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->all_pixels == 0, "svl_ce_fused_lsw_f32: all_pixels must be 0 (labelled branch only)");
+  SVL_CHECK_ARG(d->use_ignore_t != 0, "svl_ce_fused_lsw_f32: use_ignore_t must be 1 (labelled branch only)");
+  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_fused_lsw_f32: gscale required with dlogits");
+  const int P = ce_tile_pixels(d->N);
+  SVL_CHECK_ARG(P >= 64, "svl_ce_fused_lsw_f32: N=%d too large for the LDS tile", d->N);
+  CeLswP p;
+  p.logits = d->logits; p.B = d->B; p.N = d->N; p.HW = d->HW;
+  p.target = d->target; p.use_ignore_t = 1;
+  p.conf = nullptr; p.ign = nullptr; p.conf_thresh = 0.f; p.all_pixels = 0;
+  p.mc = nullptr; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
+  p.img_weight = nullptr;
+  p.P = P;
+  p.blocks_per_img = (d->HW + P - 1) / P;
+  p.eps = label_smoothing; p.cw = class_weight;
+  const long nblk = (long)d->B * p.blocks_per_img;
+  const size_t lds = (size_t)d->N * P * sizeof(float);
+  hipLaunchKernelGGL(ce_fused_kernel<true>, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
+  SVL_LAUNCH_CHECK("svl_ce_fused_lsw_f32");
+  return SVL_OK;
+}
+
+extern "C" int64_t svl_class_weight_sum_ws_doubles(int64_t n) { return n > 0 ? CW_CHUNKS : 0; }
+
+extern "C" int svl_class_weight_sum_f64(const int64_t* target, int64_t n, const float* class_weight, int N, double* sum,
+                                        double* workspace, svl_stream_t stream) {
+  SVL_CHECK_ARG(target && class_weight && sum && workspace && n > 0 && N > 0, "svl_class_weight_sum_f64: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(class_weight_sum_partial_kernel, dim3(CW_CHUNKS), dim3(256), 0, st, target, (long)n, class_weight, N,
+                     workspace);
+  SVL_LAUNCH_CHECK("svl_class_weight_sum_f64/partial");
+  hipLaunchKernelGGL(class_weight_sum_final_kernel, dim3(1), dim3(64), 0, st, workspace, sum);
+  SVL_LAUNCH_CHECK("svl_class_weight_sum_f64");
+  return SVL_OK;
+}
+
+extern "C" int svl_scale_from_sum_f32(const double* sum, double factor, float* out, svl_stream_t stream) {
+  SVL_CHECK_ARG(sum && out, "svl_scale_from_sum_f32: bad args");
+  hipLaunchKernelGGL(scale_from_sum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sum, factor, out);
+  SVL_LAUNCH_CHECK("svl_scale_from_sum_f32");
   return SVL_OK;
 }
 

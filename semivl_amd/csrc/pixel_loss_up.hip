@@ -47,6 +47,14 @@ struct UpP {
   int ncy, ncx;
   int pstr;             // stride of the per-pixel LDS arrays: >= the largest region (rows x columns) of any block
 };
+// label_smoothing / class weights of the labelled criterion (pixel_loss.hip's CeLswP): ce_up_kernel<true> only
+struct UpLswP : UpP {
+  float eps;
+  const float* cw;      // [N] or null (all ones)
+};
+template <bool LSW> struct up_param { using type = UpP; };
+template <> struct up_param<true> { using type = UpLswP; };
+constexpr int UP_MAX_N = 160;   // class counts the resize-fused kernels take (up_ok)
 
 __device__ __host__ inline float up_scale(int in, int out, bool align) {
   if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
@@ -224,13 +232,27 @@ __global__ __launch_bounds__(256) void target_prob_up_kernel(const UpP p, float*
 // ------------------------------------------------------------------------------------------------
 // Cross entropy (+ confidence weighting + guidance term) forward and backward on the resized logits; the gradient
 // arrives at the LOW resolution.  partials[block] = { sum w_t*ce_t, sum ce_m, sum conf*valid, #valid } like ce_fused_kernel.
+//
+// LSW (labelled branch only, a separate instantiation: the plain one keeps its code and its LDS): label_smoothing eps and
+// class weights w (staged in LDS once per block; ones when absent), W = sum_c w_c, g = gscale[0], everything in the staged
+// base 2 until the one LN2 per pixel:
+//   numerator(pixel) = LN2 [ (1 - eps) w_t (lse - x_t) + (eps / N) (W lse - sum_c w_c x_c) ]   (sum_c w_c x_c: phase A's class loop)
+//   d(loss)/d(resized logit c) = a p_c - b [c == t] - e w_c,  a = g ((1 - eps) w_t + (eps / N) W), b = g (1 - eps) w_t, e = g eps / N
+// The pixel arrays hold a and b where the plain kernel holds g_t and g_m; e is one number per launch and applies exactly where
+// the stored target index is >= 0, so no further per-pixel state is needed.  partials = { sum numerator, 0, 0, sum [t != 255] w_t }.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
+template <bool LSW>
+__global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>::type p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ int ry0[RMAX], ry1[RMAX], cx0[RMAX], cx1[RMAX];
   __shared__ float rl0[RMAX], rl1[RMAX], cl0[RMAX], cl1[RMAX];
   __shared__ int cr_lo[TC], cr_hi[TC], cc_lo[TC], cc_hi[TC];
   __shared__ float red[NT / 64][4];
+  float* wsh = nullptr;                     // LSW: the class weights
+  if constexpr (LSW) {
+    __shared__ float wsh_[UP_MAX_N];
+    wsh = wsh_;
+  }
   // (the pixel arrays are strided by the launch's largest region, not by RMAX^2: 72 KB in all at N = 21 and 128 -> 512, two
   //  blocks per CU -- the kernel waits on LDS round trips more than on anything else, profiles/r5_h_pmc_sq_ce_up.txt)
   const int PS = p.pstr;
@@ -261,6 +283,9 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
       for (int c = cl; c < p.N; c += NT / 128) d[c * CSTR] = g[c * hw] * LOG2E;
     }
   }
+  if constexpr (LSW) {
+    if (tid < p.N) wsh[tid] = p.cw ? p.cw[tid] : 1.f;     // (N <= UP_MAX_N < NT)
+  }
   __syncthreads();
   // footprint of each owned cell row / column inside the evaluated region (first and last index with a tap on it)
   if (tid < 2 * TC) {
@@ -287,6 +312,12 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
   const float g0 = p.dlogits ? p.gscale[0] : 0.f, g1 = p.dlogits ? p.gscale[1] : 0.f;
   const float iw = p.img_weight ? p.img_weight[b] : 1.f;
   float s_t = 0.f, s_m = 0.f, s_c = 0.f, n_v = 0.f;
+  float om = 1.f, en = 0.f, wsum = 0.f;             // LSW: 1 - eps, eps / N, W (class order: the same in every thread)
+  if constexpr (LSW) {
+    om = 1.f - p.eps;
+    en = p.eps / (float)p.N;
+    for (int c = 0; c < p.N; ++c) wsum += wsh[c];
+  }
   for (int px = tid; px < npx; px += NT) {
     const int r = px / nrx, q = px - r * nrx;
     const int y0 = ry0[r], x0 = cx0[q];
@@ -300,6 +331,28 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
     float cf = 0.f;
     if (p.conf) { ig = p.ign[o]; cf = p.conf[o]; }
     if (p.mc) mm = p.mc[o];
+    if constexpr (LSW) {
+      float m = -INFINITY, s = 0.f, swx = 0.f;
+      for (int c = 0; c < p.N; ++c) {
+        const float x = up_interp(tile + c * CSTR, k);
+        up_online(x, m, s);
+        swx = fmaf(wsh[c], x, swx);
+      }
+      const float lse = m + log2f(s);               // (base 2, like the staged logits and swx)
+      const bool t_ok = t != 255, in = t_ok && t >= 0 && t < p.N;
+      const float wt = in ? wsh[(int)t] : 0.f;      // (a label outside [0, N) reads no logit and no weight)
+      if (t_ok && y0 >= c0y && y0 < c1y && x0 >= c0x && x0 < c1x) {      // owned
+        const float xt = in ? up_interp(tile + (int)t * CSTR, k) : 0.f;
+        n_v += wt;
+        s_t += LN2 * (om * wt * (lse - xt) + en * (wsum * lse - swx));
+      }
+      // (selected, not multiplied: with every target 255 the scale g0 is 1 / 0)
+      st_lse[px] = lse;
+      st_gt[px] = t_ok ? g0 * (om * wt + en * wsum) : 0.f;
+      st_gm[px] = t_ok ? g0 * (om * wt) : 0.f;
+      st_ix[px] = (int)((unsigned)((t_ok ? (int)t : -1) & 0xffff) | 0xffff0000u);
+      continue;                                     // (the plain kernel's pixel body follows)
+    }
     float m = -INFINITY, s = 0.f;
     for (int c = 0; c < p.N; ++c) {
       up_online(up_interp(tile + c * CSTR, k), m, s);
@@ -372,6 +425,7 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
       wx[f] = (cell_ok && clo + f <= chi) ? ((cx0[cc] == xl ? cl0[cc] : 0.f) + (cx1[cc] == xl ? cl1[cc] : 0.f)) : 0.f;
     }
   }
+  const float ge = en > 0.f ? g0 * en : 0.f;        // LSW: e = g eps / N (0 in the plain kernel)
   float* dl = p.dlogits + (long)b * p.N * p.h * p.w + (long)yl * p.w + xl;
   for (int cg0 = 0; cg0 < p.N; cg0 += CG) {
     for (int px = tid; px < npx; px += NT) {
@@ -388,7 +442,12 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const UpP p) {
       for (int j = 0; j < CG; ++j) {
         const int c = cg0 + j;
         float d = 0.f;
-        if (c < p.N && gs != 0.f) {
+        if constexpr (LSW) {
+          if (c < p.N && ti >= 0) {                 // gt = a, gm = b of the pixel; e w_c on every labelled pixel
+            d = gt * __builtin_amdgcn_exp2f(up_interp(tile + c * CSTR, k) - lse) - ge * wsh[c];
+            if (c == ti) d -= gm;
+          }
+        } else if (c < p.N && gs != 0.f) {
           d = gs * __builtin_amdgcn_exp2f(up_interp(tile + c * CSTR, k) - lse);
           if (c == ti) d -= gt;
           if (c == mi) d -= gm;
@@ -431,7 +490,7 @@ inline bool up_axis_ok(int in, int out, bool align, int* max_region = nullptr) {
   return true;
 }
 inline bool up_ok(int N, int h, int w, int H, int W, int align) {
-  return N > 0 && N <= 160 && up_axis_ok(h, H, align != 0) && up_axis_ok(w, W, align != 0);
+  return N > 0 && N <= UP_MAX_N && up_axis_ok(h, H, align != 0) && up_axis_ok(w, W, align != 0);
 }
 inline size_t ce_up_lds(int N, int pstr) { return ((size_t)N * CSTR + (size_t)(4 + CG) * pstr) * sizeof(float); }
 
@@ -458,12 +517,16 @@ size_t device_lds_limit() {
   return 160 * 1024;
 }
 // the largest dynamic allocation a launch of this geometry asks for (pixel arrays strided by the launch's largest region)
-inline bool up_fits(int N, int h, int w, int H, int W, int align) {
+inline bool up_fits(int N, int h, int w, int H, int W, int align, size_t fixed = 1024) {
   int my = 0, mx = 0;
   if (!up_axis_ok(h, H, align != 0, &my) || !up_axis_ok(w, W, align != 0, &mx)) return false;
   static const size_t limit = device_lds_limit();
-  return ce_up_lds(N, ((my * mx + 31) / 32) * 32) + 1024 <= limit;     // (+ the kernels' static LDS)
+  return ce_up_lds(N, ((my * mx + 31) / 32) * 32) + fixed <= limit;     // (+ the kernels' static LDS)
 }
+// ce_up_kernel<true>: its static LDS is the index / footprint / reduction arrays (1536 B) and the staged class weights
+// (640 B); 3 KB keeps the dynamic part within the 157 KB its launch asks the runtime for
+constexpr size_t UP_LSW_FIXED = 3 * 1024;
+static_assert(1536 + UP_MAX_N * sizeof(float) <= UP_LSW_FIXED, "static LDS of ce_up_kernel<true>");
 
 }  // namespace
 
@@ -513,12 +576,56 @@ extern "C" int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t stream)
   p.pstr = ((my * mx + 31) / 32) * 32;
   static std::atomic<uint64_t> mask{0};
   {
-    const int rc = lds_attr_once(mask, ce_up_kernel, 158 * 1024);
+    const int rc = lds_attr_once(mask, ce_up_kernel<false>, 158 * 1024);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(ce_up_kernel, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
+  hipLaunchKernelGGL(ce_up_kernel<false>, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
                      (hipStream_t)stream, p);
   SVL_LAUNCH_CHECK("svl_ce_up_fused_f32");
+  return SVL_OK;
+}
+
+extern "C" int64_t svl_ce_up_lsw_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners) {
+  if (B <= 0 || !up_ok(N, h, w, H, W, align_corners) || !up_fits(N, h, w, H, W, align_corners, UP_LSW_FIXED)) return -1;
+  return (int64_t)B * ((h + TC - 1) / TC) * ((w + TC - 1) / TC);
+}
+
+extern "C" int svl_ce_up_fused_lsw_f32(const svl_ce_up_desc* d, float label_smoothing, const float* class_weight,
+                                       svl_stream_t stream) {
+  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_up_fused_lsw_f32: null args");
+  SVL_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "svl_ce_up_fused_lsw_f32: label_smoothing=%g outside [0, 1]",
+                (double)label_smoothing);
+  // labelled branch only
+  SVL_CHECK_ARG(d->conf == nullptr, "svl_ce_up_fused_lsw_f32: conf must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->ign == nullptr, "svl_ce_up_fused_lsw_f32: ign must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->mc_target == nullptr, "svl_ce_up_fused_lsw_f32: mc_target must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->img_weight == nullptr, "svl_ce_up_fused_lsw_f32: img_weight must be NULL (labelled branch only)");
+  SVL_CHECK_ARG(d->all_pixels == 0, "svl_ce_up_fused_lsw_f32: all_pixels must be 0 (labelled branch only)");
+  SVL_CHECK_ARG(d->use_ignore_t != 0, "svl_ce_up_fused_lsw_f32: use_ignore_t must be 1 (labelled branch only)");
+  SVL_CHECK_ARG(d->B > 0 && up_ok(d->N, d->h, d->w, d->H, d->W, d->align_corners) &&
+                    up_fits(d->N, d->h, d->w, d->H, d->W, d->align_corners, UP_LSW_FIXED),
+                "svl_ce_up_fused_lsw_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_lsw_num_blocks < 0)", d->N, d->h,
+                d->w, d->H, d->W);
+  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_up_fused_lsw_f32: gscale required with dlogits");
+  UpLswP p = {};
+  p.logits = d->logits; p.B = d->B; p.N = d->N; p.h = d->h; p.w = d->w; p.H = d->H; p.W = d->W;
+  p.align = d->align_corners != 0;
+  p.target = d->target; p.use_ignore_t = 1;
+  p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
+  p.ncy = (d->h + TC - 1) / TC; p.ncx = (d->w + TC - 1) / TC;
+  p.eps = label_smoothing; p.cw = class_weight;
+  int my = 0, mx = 0;
+  (void)up_axis_ok(d->h, d->H, p.align != 0, &my);
+  (void)up_axis_ok(d->w, d->W, p.align != 0, &mx);
+  p.pstr = ((my * mx + 31) / 32) * 32;
+  static std::atomic<uint64_t> mask{0};
+  {
+    const int rc = lds_attr_once(mask, ce_up_kernel<true>, 157 * 1024);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(ce_up_kernel<true>, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
+                     (hipStream_t)stream, p);
+  SVL_LAUNCH_CHECK("svl_ce_up_fused_lsw_f32");
   return SVL_OK;
 }
 

@@ -101,6 +101,12 @@ SIGNATURES = {
     "svl_ce_finalize": (_I, [_P, _L, _P, _P]),
     "svl_ce_up_num_blocks": (_L, [_I, _I, _I, _I, _I, _I, _I]),
     "svl_ce_up_fused_f32": (_I, [C.POINTER(CeUpDesc), _P]),
+    "svl_ce_fused_lsw_f32": (_I, [C.POINTER(CeDesc), _F, _P, _P]),
+    "svl_ce_up_lsw_num_blocks": (_L, [_I, _I, _I, _I, _I, _I, _I]),
+    "svl_ce_up_fused_lsw_f32": (_I, [C.POINTER(CeUpDesc), _F, _P, _P]),
+    "svl_class_weight_sum_ws_doubles": (_L, [_L]),
+    "svl_class_weight_sum_f64": (_I, [_P, _L, _P, _I, _P, _P, _P]),
+    "svl_scale_from_sum_f32": (_I, [_P, _D, _P, _P]),
     "svl_softmax_max_up_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "svl_semivl_gscale": (_I, [_P, _D, _F, _P, _P, _P, _P]),
     "svl_semivl_loss": (_I, [_P, _D, _F, _P, _P, _P, _P]),

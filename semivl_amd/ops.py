@@ -1585,9 +1585,26 @@ def count_valid(map_i64, out_count):
     L.check(L.load().svl_count_valid_i64(_p(map_i64), map_i64.numel(), _p(out_count), _st()), "svl_count_valid_i64")
 
 
+def _lsw_args(label_smoothing, class_weight, N, device):
+    """(eps, weight) of the label-smoothing / class-weight entry points, or None for the plain ones (0.0 and None)."""
+    eps = float(label_smoothing)
+    if eps == 0.0 and class_weight is None:
+        return None
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be between 0.0 and 1.0. Got: {eps}")
+    if class_weight is not None and not (class_weight.dtype == torch.float32 and class_weight.is_contiguous() and
+                                         class_weight.numel() == N and class_weight.device == device):
+        raise ValueError(f"class_weight must be a contiguous fp32 tensor of {N} elements on {device}, got "
+                         f"{tuple(class_weight.shape)} {class_weight.dtype} on {class_weight.device}")
+    return eps, class_weight
+
+
 def ce_fused(logits, target, use_ignore_t, conf=None, ign=None, conf_thresh=0.0, mc=None, dlogits=None, gscale=None,
-             sums_out=None, all_pixels=False, img_weight=None):
-    """Returns sums (double[4] device): {sum w*ce_t, sum ce_m, sum conf*valid, #valid}."""
+             sums_out=None, all_pixels=False, img_weight=None, label_smoothing=0.0, class_weight=None):
+    """Returns sums (double[4] device): {sum w*ce_t, sum ce_m, sum conf*valid, #valid}.
+    `label_smoothing` / `class_weight` (fp32 [N] on the device): the labelled criterion as torch's
+    CrossEntropyLoss(ignore_index=255, label_smoothing=, weight=) (svl_ce_fused_lsw_f32; labelled branch only) -- sums are
+    then {numerator, 0, 0, sum of w[target] over the labelled pixels}; 0.0 and None call the plain entry point."""
     Bn, N = logits.shape[:2]
     HW = logits[0, 0].numel()
     lib = L.load()
@@ -1598,7 +1615,11 @@ def ce_fused(logits, target, use_ignore_t, conf=None, ign=None, conf_thresh=0.0,
     d = L.CeDesc(_p(logits), Bn, N, HW, _p(target), 1 if use_ignore_t else 0, _p(conf), _p(ign), float(conf_thresh),
                  1 if all_pixels else 0, _p(mc), _p(partials), _p(dlogits), _p(gscale), _p(img_weight))
     e0 = _prof_begin()
-    L.check(lib.svl_ce_fused_f32(C.byref(d), _st()), "svl_ce_fused_f32")
+    lsw = _lsw_args(label_smoothing, class_weight, N, logits.device)
+    if lsw is None:
+        L.check(lib.svl_ce_fused_f32(C.byref(d), _st()), "svl_ce_fused_f32")
+    else:
+        L.check(lib.svl_ce_fused_lsw_f32(C.byref(d), lsw[0], _p(lsw[1]), _st()), "svl_ce_fused_lsw_f32")
     # algorithmic bytes: fwd (4N+20) + bwd (8N+20) B/px when dlogits is produced, else fwd only
     _prof_end("ce_fused", e0, float(Bn * HW) * ((12 * N + 40) if dlogits is not None else (4 * N + 20)), (Bn, N, HW))
     if sums_out is None:
@@ -1610,6 +1631,11 @@ def ce_fused(logits, target, use_ignore_t, conf=None, ign=None, conf_thresh=0.0,
 def ce_up_ok(Bn, N, h, w, H, W, align):
     """Whether the pixel-loss kernels can evaluate the resize [h, w] -> [H, W] themselves (svl_ce_up_num_blocks)."""
     return L.load().svl_ce_up_num_blocks(int(Bn), int(N), int(h), int(w), int(H), int(W), 1 if align else 0) > 0
+
+
+def ce_up_lsw_ok(Bn, N, h, w, H, W, align):
+    """ce_up_ok for the label-smoothing / class-weight variant (svl_ce_up_lsw_num_blocks: its kernel holds more in LDS)."""
+    return L.load().svl_ce_up_lsw_num_blocks(int(Bn), int(N), int(h), int(w), int(H), int(W), 1 if align else 0) > 0
 
 
 def softmax_max_up(logits, H, W, align):
@@ -1625,12 +1651,14 @@ def softmax_max_up(logits, H, W, align):
 
 
 def ce_up_fused(logits, H, W, align, target, use_ignore_t, conf=None, ign=None, conf_thresh=0.0, mc=None, dlogits=None,
-                gscale=None, sums_out=None, all_pixels=False, img_weight=None):
+                gscale=None, sums_out=None, all_pixels=False, img_weight=None, label_smoothing=0.0, class_weight=None):
     """ce_fused on bilinear(logits [B, N, h, w] -> [H, W]) with the resize evaluated inside the kernel; `dlogits`
-    [B, N, h, w] receives d(loss)/d(logits) at the LOW resolution.  Returns sums (double[4] device)."""
+    [B, N, h, w] receives d(loss)/d(logits) at the LOW resolution.  Returns sums (double[4] device).
+    `label_smoothing` / `class_weight` as in ce_fused (svl_ce_up_fused_lsw_f32; geometry: ce_up_lsw_ok)."""
     Bn, N, h, w = logits.shape
     lib = L.load()
-    nblk = lib.svl_ce_up_num_blocks(Bn, N, h, w, H, W, 1 if align else 0)
+    lsw = _lsw_args(label_smoothing, class_weight, N, logits.device)
+    nblk = (lib.svl_ce_up_num_blocks if lsw is None else lib.svl_ce_up_lsw_num_blocks)(Bn, N, h, w, H, W, 1 if align else 0)
     if nblk <= 0:
         raise RuntimeError(f"svl_ce_up_fused: unsupported geometry N={N} {h}x{w} -> {H}x{W}")
     partials = empty(nblk, 4, device=logits.device)
@@ -1638,7 +1666,10 @@ def ce_up_fused(logits, H, W, align, target, use_ignore_t, conf=None, ign=None, 
                    _p(ign), float(conf_thresh), 1 if all_pixels else 0, _p(mc), _p(partials), _p(dlogits), _p(gscale),
                    _p(img_weight))
     e0 = _prof_begin()
-    L.check(lib.svl_ce_up_fused_f32(C.byref(d), _st()), "svl_ce_up_fused_f32")
+    if lsw is None:
+        L.check(lib.svl_ce_up_fused_f32(C.byref(d), _st()), "svl_ce_up_fused_f32")
+    else:
+        L.check(lib.svl_ce_up_fused_lsw_f32(C.byref(d), lsw[0], _p(lsw[1]), _st()), "svl_ce_up_fused_lsw_f32")
     # bytes the kernel moves: low-resolution logits in (+ gradient out) and 28 B of maps per full-resolution pixel
     _prof_end("ce_up_fused", e0, float(Bn) * ((8.0 if dlogits is not None else 4.0) * N * h * w + 28.0 * H * W),
               (Bn, N, h * w, H * W))
@@ -1746,6 +1777,26 @@ def semivl_gscale(counts_i64, numel_u, lam, gscale_out, factors=None, mc_counts=
 def inv_count(count_i64, out):
     """out[0] (fp32 view) = 1 / count_i64[0] on the device (svl_inv_count_f32): the gradient scale of a plain mean."""
     L.check(L.load().svl_inv_count_f32(_p(count_i64), _p(out), _st()), "svl_inv_count_f32")
+
+
+def class_weight_sum(target, class_weight, out):
+    """out[0] (float64 view on the device) = sum of class_weight[target] over the pixels with target != 255
+    (svl_class_weight_sum_f64): the normaliser of torch's weighted mean, in a fixed order, no host sync."""
+    lib = L.load()
+    n = target.numel()
+    assert target.dtype == torch.int64 and target.is_contiguous() and out.dtype == torch.float64
+    assert class_weight.dtype == torch.float32 and class_weight.is_contiguous()
+    ws = torch.empty(int(lib.svl_class_weight_sum_ws_doubles(n)), dtype=torch.float64, device=target.device)
+    L.check(lib.svl_class_weight_sum_f64(_p(target), n, _p(class_weight), class_weight.numel(), _p(out), _p(ws), _st()),
+            "svl_class_weight_sum_f64")
+    return out
+
+
+def scale_from_sum(sum_f64, factor, out):
+    """out[0] (fp32 view) = factor / sum_f64[0] on the device (svl_scale_from_sum_f32): inv_count for a weighted mean."""
+    assert sum_f64.dtype == torch.float64 and out.dtype == torch.float32
+    L.check(L.load().svl_scale_from_sum_f32(_p(sum_f64), float(factor), _p(out), _st()), "svl_scale_from_sum_f32")
+    return out
 
 
 def semivl_loss(sums_f64, numel_u, lam, out8, factors=None, mc_counts=None):

@@ -10,9 +10,11 @@ Mirrors (same names / argument meaning):
 """
 
 import contextlib
+import numbers
 import os
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -104,11 +106,52 @@ class ProbOhemCrossEntropy2d(torch.nn.Module):
 def supervised_criterion(cfg):
     """cfg['criterion'] (semivl.py:142-149) -> None for the plain cross entropy (missing, 'CELoss', and -- unchanged --
     every other name) or a ProbOhemCrossEntropy2d for 'OHEM', built from cfg['criterion']['kwargs'] as given (ohem.py's
-    defaults fill the rest, like the reference)."""
+    defaults fill the rest, like the reference).  The `label_smoothing` / `weight` kwargs of 'CELoss' are read by
+    celoss_kwargs."""
     crit = cfg.get("criterion")
     if not isinstance(crit, dict) or crit.get("name") != "OHEM":
         return None
     return ProbOhemCrossEntropy2d(**(crit.get("kwargs") or {}))
+
+
+def celoss_kwargs(cfg, num_classes):
+    """(label_smoothing, weight) of cfg['criterion'] = dict(name='CELoss', kwargs=...): the two arguments of the reference's
+    nn.CrossEntropyLoss(**cfg['criterion']['kwargs']) (semivl.py:142-143, supervised.py:230-231) that change the labelled
+    loss's arithmetic.  `label_smoothing` must be a real number in [0, 1] (torch's own rule); `weight` a list, tuple, numpy
+    array or tensor of `num_classes` numbers, returned as a contiguous fp32 tensor (a tensor already on a GPU stays there),
+    or None.  Every other key (`ignore_index`, `reduction`, ...) is not read, as before.  A missing criterion, 'OHEM'
+    (ProbOhemCrossEntropy2d has no such arguments) and every other name give (0.0, None)."""
+    crit = cfg.get("criterion")
+    if not isinstance(crit, dict) or crit.get("name") != "CELoss":
+        return 0.0, None
+    kw = crit.get("kwargs") or {}
+    eps = kw.get("label_smoothing", 0.0)
+    if isinstance(eps, bool) or not isinstance(eps, numbers.Real) or not 0.0 <= float(eps) <= 1.0:
+        raise ValueError(f"criterion kwargs: label_smoothing must be a real number between 0.0 and 1.0. Got: {eps!r}")
+    weight = kw.get("weight")
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            weight = torch.as_tensor(np.asarray(weight, dtype=np.float64))
+        weight = weight.detach().to(torch.float32).contiguous()
+        # (num_classes None: a model that does not say; the kernels' wrappers then check the length against the logits)
+        if weight.dim() != 1 or (num_classes is not None and weight.numel() != num_classes):
+            raise ValueError(f"criterion kwargs: weight has {weight.numel()} entries (shape {tuple(weight.shape)}), expected "
+                             f"{num_classes}: one number for each class")
+    return float(eps), weight
+
+
+def _celoss_weight_on(model, weight, dev):
+    """The class weights of celoss_kwargs on `dev`: copied once and kept on the model (ops.StreamCached, like
+    renormalize_img_for_clip's statistics), so that a step makes no host-to-device copy and no sync."""
+    if weight is None or weight.device == dev:
+        return weight
+    cache = getattr(model, "_dev_cache", None)
+    if not isinstance(cache, dict):
+        cache = model.__dict__.setdefault("_celoss_dev_cache", {})
+    key = ("celoss_weight", str(dev), tuple(weight.tolist()))
+    if key not in cache:
+        cache[key] = ops.StreamCached(weight.to(dev))
+    return cache[key].get()
 
 
 def _cat2(a, b):
@@ -206,7 +249,9 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
     synthetic_batch).  model.train(), ONE forward on img_x, criterion from supervised_criterion(cfg) (cross entropy with
     ignore 255, or OHEM relabelling on the device followed by the same cross entropy), loss = the plain mean over the kept
     pixels (weight 1, not the 1/2 of semivl.py:319); its gradient scale 1 / count is formed on the device
-    (svl_inv_count_f32): no host sync.  Then optimizer.zero_grad(), backward (reducer.begin() / finish() around it),
+    (svl_inv_count_f32): no host sync.  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs) select the
+    cross-entropy kernels' label-smoothing / class-weight variant: torch's weighted, smoothed mean, its scale 1 / D with
+    D = the sum of weight[target] over the labelled pixels, also formed on the device.  Then optimizer.zero_grad(), backward (reducer.begin() / finish() around it),
     optimizer.step() and optimizer.poly_lr(iters, total_iters) -- supervised.py:294-300 has no warm-up and no
     scheduler_max_iters, so cfg's `warmup_iters` / `scheduler_max_iters` are ignored here.
     Returns the device tensor `loss` [1]; with `return_aux` also dict(pred_x [B, N, S, S], dlogits, mask_x_ohem (None
@@ -217,14 +262,15 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
         return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux)
 
 
-def _head_res(model, img, cfg):
+def _head_res(model, img, cfg, lsw=False):
     """`up` = (H, W, align_corners) when the logits can stay at the head's resolution (the bilinear resize to the crop is then
     evaluated inside the softmax-max / cross-entropy kernels), else None: models without the option, geometries the kernels
-    do not take, cfg['fuse_upsample_loss'] / SVL_NO_UP_LOSS."""
+    do not take, cfg['fuse_upsample_loss'] / SVL_NO_UP_LOSS.  `lsw`: the labelled cross entropy runs its label-smoothing /
+    class-weight variant, whose own geometry query (ops.ce_up_lsw_ok) must allow it too."""
     if img.is_cuda and cfg.get("fuse_upsample_loss", ops.UP_LOSS) and hasattr(model, "head_res_size"):
         hs = model.head_res_size(tuple(img.shape[2:]))
-        if hs is not None and ops.ce_up_ok(img.shape[0], model.num_classes, hs[0], hs[1], img.shape[2], img.shape[3],
-                                           model.align_corners):
+        geom = (img.shape[0], model.num_classes, hs[0], hs[1], img.shape[2], img.shape[3], model.align_corners) if hs else None
+        if hs is not None and ops.ce_up_ok(*geom) and (not lsw or ops.ce_up_lsw_ok(*geom)):
             return (int(img.shape[2]), int(img.shape[3]), bool(model.align_corners))
     return None
 
@@ -233,6 +279,10 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
     ohem = supervised_criterion(cfg)                     # supervised.py:222-231 (raises on what the kernels cannot do)
     img_x, mask_x = batch["img_x"], batch["mask_x"]
     B, dev = img_x.shape[0], img_x.device
+    # CELoss kwargs (supervised.py:230-231): label_smoothing / weight reach the cross-entropy kernels; (0.0, None) is the plain path
+    eps, cw = celoss_kwargs(cfg, getattr(model, "num_classes", None))
+    cw = _celoss_weight_on(model, cw, dev)
+    ce_kw = dict(label_smoothing=eps, class_weight=cw) if (eps != 0.0 or cw is not None) else {}
     if "wgrad_stream" in cfg:
         ops.WGRAD_STREAM = bool(cfg["wgrad_stream"])
     elif not cfg.get("overlap_streams", True):
@@ -256,7 +306,7 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
     mask_x = mask_x.contiguous()
     if reducer is not None:
         reducer.begin()
-    up = _head_res(model, img_x, cfg)
+    up = _head_res(model, img_x, cfg, lsw=bool(ce_kw))
     model.train()                                        # supervised.py:268
     pred = model(img_x, **(dict(head_res=True) if up is not None else {}))     # :277
     count = ops.zeros(1, dtype=torch.int64, device=dev)
@@ -266,15 +316,20 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
     else:
         ops.count_valid(mask_x, count)
     gscale = ops.zeros(2, device=dev)                    # {g_t, g_m}: g_m stays 0
-    ops.inv_count(count, gscale)
+    if cw is not None:      # torch's weighted mean: the normaliser is D = sum of w[target] over the labelled pixels
+        ops.scale_from_sum(ops.class_weight_sum(mask_x, cw, ops.empty(1, dtype=torch.float64, device=dev)), 1.0, gscale)
+    else:
+        ops.inv_count(count, gscale)
     dlogits = torch.empty_like(pred)
     # sums[0] = {sum ce, 0, 0, #kept}; svl_semivl_loss's `loss_x` slot is sums[0][0] / sums[0][3] -- the mean, weight 1 (:279).
+    # (with CELoss kwargs: {numerator, 0, 0, D}, the same quotient.)
     # The other three branches do not exist here: their rows are zero and their slots of `out` are never read.
     sums = ops.zeros(4, 4, dtype=torch.float64, device=dev)
     if up is not None:
-        ops.ce_up_fused(pred.detach(), up[0], up[1], up[2], mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0])
+        ops.ce_up_fused(pred.detach(), up[0], up[1], up[2], mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0],
+                        **ce_kw)
     else:
-        ops.ce_fused(pred.detach(), mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0])
+        ops.ce_fused(pred.detach(), mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0], **ce_kw)
     out = ops.empty(8, device=dev)
     ops.semivl_loss(sums, float(mask_x.numel()), 0.0, out)
     loss = out[1:2]
@@ -299,7 +354,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
                        return_aux=False):
     """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
-    returned `losses` is a device float[8] (LOSS_NAMES order).
+    returned `losses` is a device float[8] (LOSS_NAMES order).  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs)
+    change the labelled launch only: `losses[1]` is torch's smoothed / weighted loss_x and enters `losses[0]` as before.
     """
     conf_mode = cfg.get("conf_mode", "pixelwise")
     mcc_reduce = cfg.get("mcc_loss_reduce", "mean_all")
@@ -308,6 +364,10 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     if mcc_reduce not in ("mean_all", "mean_valid", "mean"):
         raise ValueError(mcc_reduce)                     # semivl.py:161-162
     ohem = supervised_criterion(cfg)                     # semivl.py:142-149 (raises on what the kernels cannot do)
+    # CELoss kwargs (semivl.py:142-143): label_smoothing / weight change the labelled launch only; (0.0, None) is the plain path
+    eps_x, cw_x = celoss_kwargs(cfg, getattr(model, "num_classes", None))
+    cw_x = _celoss_weight_on(model, cw_x, batch["img_x"].device)
+    ce_kw_x = dict(label_smoothing=eps_x, class_weight=cw_x) if (eps_x != 0.0 or cw_x is not None) else {}
     pixelavg = conf_mode == "pixelavg"
     whole_map = conf_mode in ("pixelavg", "pixelratio")  # both weight the WHOLE CE map, not the confident valid pixels
     lam_cfg = cfg.get("maskclip_consistency_lambda", [0.1, 0])
@@ -370,8 +430,10 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     up = None
     if img_x.is_cuda and cfg.get("fuse_upsample_loss", ops.UP_LOSS) and hasattr(model, "head_res_size"):
         hs = model.head_res_size(tuple(img_x.shape[2:]))
-        if hs is not None and ops.ce_up_ok(B, model.num_classes, hs[0], hs[1], img_x.shape[2], img_x.shape[3],
-                                           model.align_corners):
+        geom = (B, model.num_classes, hs[0], hs[1], img_x.shape[2], img_x.shape[3], model.align_corners) if hs else None
+        # (the labelled launch's label-smoothing / class-weight variant has its own geometry query: where it refuses, the
+        # whole step runs on the resized tensors)
+        if hs is not None and ops.ce_up_ok(*geom) and (not ce_kw_x or ops.ce_up_lsw_ok(*geom)):
             up = (int(img_x.shape[2]), int(img_x.shape[3]), bool(model.align_corners))
     fwd_kw = dict(head_res=True) if up is not None else {}
 
@@ -495,6 +557,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         for i, m_ in enumerate((mc1, mc2, mclip)):
             ops.count_valid(m_, mc_counts[i:i + 1])
     ops.semivl_gscale(counts, numel_u, lam, gscale, factors, mc_counts)
+    if cw_x is not None:    # torch's weighted mean: g_t of the labelled branch is 0.5 / D, D = sum of w[target] (counts[0] stays)
+        ops.scale_from_sum(ops.class_weight_sum(mask_x, cw_x, ops.empty(1, dtype=torch.float64, device=dev)), 0.5, gscale[0])
     # fused CE forward + backward per branch
     thr = cfg["conf_thresh"]
     dl4 = torch.empty_like(preds4)
@@ -508,7 +572,7 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
             return ops.ce_up_fused(pred, up[0], up[1], up[2], *a_, **kw)
         return ops.ce_fused(pred, *a_, **kw)
 
-    ce(pred_x.detach(), mask_x, True, dlogits=dl4[B:2 * B], gscale=gscale[0], sums_out=sums[0])
+    ce(pred_x.detach(), mask_x, True, dlogits=dl4[B:2 * B], gscale=gscale[0], sums_out=sums[0], **ce_kw_x)
     ce(pred_s1.detach(), mw1, False, conf=cw1, ign=ig1, conf_thresh=thr, mc=mc1, dlogits=dls[:B],
        gscale=gscale[1], sums_out=sums[1], all_pixels=whole_map, img_weight=ratios[0])
     ce(pred_s2.detach(), mw2, False, conf=cw2, ign=ig2, conf_thresh=thr, mc=mc2, dlogits=dls[B:],
