@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 605: + svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32, svl_ce_up_lsw_num_blocks, svl_class_weight_sum_f64, svl_class_weight_sum_ws_doubles, svl_scale_from_sum_f32 (label_smoothing / class weights of the labelled cross entropy); 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 606: + svl_grad_clip_f32, svl_grad_clip_ws_doubles, svl_adamw_step_dscale, svl_sgd_step_dscale (gradient-norm clipping on the arena, formed and applied on the device); 605: + svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32, svl_ce_up_lsw_num_blocks, svl_class_weight_sum_f64, svl_class_weight_sum_ws_doubles, svl_scale_from_sum_f32 (label_smoothing / class weights of the labelled cross entropy); 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -772,6 +772,40 @@ int svl_adamw_step(float* p, const float* g, float* m, float* v, const int64_t* 
 int svl_sgd_step(float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr, const float* seg_wd,
                  int nseg, int64_t total, float momentum, float dampening, int nesterov, int step, float gscale,
                  float* ema, float ema_decay, svl_stream_t stream);
+/* The same two steps with the gradient scale read from the DEVICE: gscale_dev points to one fp32 value (stats + 2 of
+ * svl_grad_clip_f32), read by the kernel when it runs -- nothing about it is known to the host.  Every other argument, check
+ * and rule as above; the kernels are further instantiations of the same templates and do the same arithmetic after the read:
+ * for the same scale value both forms produce the same bits in p, m, v and ema. */
+int svl_adamw_step_dscale(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const float* seg_lr,
+                          const float* seg_wd, int nseg, int64_t total, float beta1, float beta2, float eps, int step,
+                          const float* gscale_dev, float* ema, float ema_decay, svl_stream_t stream);
+int svl_sgd_step_dscale(float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr,
+                        const float* seg_wd, int nseg, int64_t total, float momentum, float dampening, int nesterov,
+                        int step, const float* gscale_dev, float* ema, float ema_decay, svl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping over the gradient arena: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type) over all
+ * tensors of the arena at once (its padding is zero, so the arena's norm is the norm over the tensors).  Replaces NOTHING of
+ * the reference: semivl.py does not clip; this is what mmcv's OptimizerHook(grad_clip=dict(max_norm, norm_type)) calls.
+ *   norm_kind 0: L2, norm = gscale * sqrt(sum_i g_i^2);   norm_kind 1: max norm, norm = gscale * max_i |g_i|
+ *   coef = min(max_norm / (norm + 1e-6), 1);   stats = {norm, coef, gscale * coef, 1.0 if norm is not finite else 0.0}
+ * stats[2] is the scale a step applies to g (svl_adamw_step_dscale / svl_sgd_step_dscale): the clip never rewrites g.
+ * Rounding and order: stage 1 is one launch that reads g once (16-byte loads when g is 16-byte aligned, 4-byte loads
+ * otherwise and for the last total % 4 elements); a lane adds its g_i^2 in double (fma, one chain per position in its group
+ * of four) or keeps its largest |g_i| and a NaN flag (fmax alone would lose a NaN); lanes fold by cross-lane shuffles, waves
+ * through LDS, and every block writes ONE double into ws.  Which lane and block reads which element depends on `total` alone:
+ * not on the alignment of g, not on its values.  Stage 2 is a second launch of one block that folds the partials in a fixed
+ * order and forms norm, coef and gscale * coef in double, each rounded to fp32 ONCE.  No atomics and no combination across
+ * workgroups inside a launch: two calls on the same g give the same bits.
+ * Non-finite gradients as in torch (error_if_nonfinite=False): the norm is inf or NaN, coef = max_norm / inf = 0 or NaN,
+ * stats[3] = 1 and nothing is skipped.  max_norm = +inf needs no special case: coef = 1, the call only reports the norm.
+ * gscale (the 1 / world_size of the data-parallel mean, applied to the norm as it is to the step) must be positive and
+ * finite, max_norm positive: anything else, a null pointer or total <= 0 is SVL_ERR_INVALID_ARG.
+ * ws: svl_grad_clip_ws_doubles(total) doubles of device memory (host-only query; at most 1024), caller-owned, no
+ * initialisation; exactly that many are written.  stats: 4 floats. */
+int64_t svl_grad_clip_ws_doubles(int64_t total);
+int svl_grad_clip_f32(const float* g, int64_t total, int norm_kind, float gscale, float max_norm, double* ws,
+                      float* stats /* [4] */, svl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * BatchNorm2d (batch statistics, SyncBN-ready) and MaxPool2d(3, 2, 1) on channels-last [rows, C] activations: the ops of

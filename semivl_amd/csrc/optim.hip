@@ -5,13 +5,21 @@
 
 namespace {
 
+// The gradient scale of a step kernel: a host float passed by value (svl_adamw_step, svl_sgd_step), or ONE device float the
+// kernel reads (the *_dscale entry points: stats[2] of svl_grad_clip_f32).  Same arithmetic after the read, so the same
+// scale value gives the same bits.
+__device__ __forceinline__ float scale_of(float s) { return s; }
+__device__ __forceinline__ float scale_of(const float* s) { return *s; }
+
+template <typename SCALE>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     const long long* __restrict__ seg_off,
                                                     const float* __restrict__ seg_lr, const float* __restrict__ seg_wd,
                                                     int nseg, long total, float beta1, float beta2, float eps,
-                                                    float bc1, float bc2_sqrt, float gscale, float* __restrict__ ema,
+                                                    float bc1, float bc2_sqrt, SCALE gscale_arg, float* __restrict__ ema,
                                                     float ema_decay) {
+  const float gscale = scale_of(gscale_arg);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     // segment lookup: largest s with seg_off[s] <= i
     int lo = 0, hi = nseg - 1;
@@ -64,13 +72,14 @@ __device__ __forceinline__ void sgd_elem(float& pw, float gr, float& mm, float l
   pw = pw - lr * d;
 }
 
-template <bool MOM, bool FIRST, bool NEST, bool EMA>
+template <bool MOM, bool FIRST, bool NEST, bool EMA, typename SCALE>
 __global__ __launch_bounds__(SGD_THREADS) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, const long long* __restrict__ seg_off,
                                                           const float* __restrict__ seg_lr,
                                                           const float* __restrict__ seg_wd, int nseg, long total,
-                                                          float momentum, float omd, float gscale,
+                                                          float momentum, float omd, SCALE gscale_arg,
                                                           float* __restrict__ ema, float ema_decay, float ema_omd) {
+  const float gscale = scale_of(gscale_arg);
   for (long base = (long)blockIdx.x * SGD_TRIP; base < total; base += (long)gridDim.x * SGD_TRIP) {
     const long last = (base + SGD_TRIP <= total ? base + SGD_TRIP : total) - 1;
     const int s_lo = seg_search(seg_off, 0, nseg - 1, base);
@@ -111,16 +120,64 @@ __global__ __launch_bounds__(SGD_THREADS) void sgd_kernel(float* __restrict__ p,
   }
 }
 
-template <bool MOM, bool FIRST, bool NEST>
+template <bool MOM, bool FIRST, bool NEST, typename SCALE>
 void sgd_launch(bool with_ema, unsigned grid, hipStream_t st, float* p, const float* g, float* m, const long long* seg_off,
-                const float* seg_lr, const float* seg_wd, int nseg, long total, float momentum, float omd, float gscale,
+                const float* seg_lr, const float* seg_wd, int nseg, long total, float momentum, float omd, SCALE gscale,
                 float* ema, float ema_decay, float ema_omd) {
   if (with_ema)
-    hipLaunchKernelGGL((sgd_kernel<MOM, FIRST, NEST, true>), dim3(grid), dim3(SGD_THREADS), 0, st, p, g, m, seg_off,
+    hipLaunchKernelGGL((sgd_kernel<MOM, FIRST, NEST, true, SCALE>), dim3(grid), dim3(SGD_THREADS), 0, st, p, g, m, seg_off,
                        seg_lr, seg_wd, nseg, total, momentum, omd, gscale, ema, ema_decay, ema_omd);
   else
-    hipLaunchKernelGGL((sgd_kernel<MOM, FIRST, NEST, false>), dim3(grid), dim3(SGD_THREADS), 0, st, p, g, m, seg_off,
+    hipLaunchKernelGGL((sgd_kernel<MOM, FIRST, NEST, false, SCALE>), dim3(grid), dim3(SGD_THREADS), 0, st, p, g, m, seg_off,
                        seg_lr, seg_wd, nseg, total, momentum, omd, gscale, ema, ema_decay, ema_omd);
+}
+
+template <typename SCALE>
+int adamw_step(const char* name, float* p, const float* g, float* m, float* v, const int64_t* seg_off, const float* seg_lr,
+               const float* seg_wd, int nseg, int64_t total, float beta1, float beta2, float eps, int step, SCALE gscale,
+               float* ema, float ema_decay, svl_stream_t stream) {
+  SVL_CHECK_ARG(p && g && m && v && seg_off && seg_lr && seg_wd && nseg > 0 && total > 0 && step >= 1, "%s: bad args",
+                name);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  long grid = (total + 1023) / 1024;
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(adamw_kernel<SCALE>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (const long long*)seg_off, seg_lr, seg_wd, nseg, (long)total, beta1, beta2, eps, (float)bc1,
+                     (float)sqrt(bc2), gscale, ema, ema_decay);
+  SVL_LAUNCH_CHECK(name);
+  return SVL_OK;
+}
+
+template <typename SCALE>
+int sgd_step(const char* name, float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr,
+             const float* seg_wd, int nseg, int64_t total, float momentum, float dampening, int nesterov, int step,
+             SCALE gscale, float* ema, float ema_decay, svl_stream_t stream) {
+  SVL_CHECK_ARG(p && g && seg_off && seg_lr && seg_wd && nseg > 0 && total > 0 && step >= 1, "%s: bad args", name);
+  SVL_CHECK_ARG(m || momentum == 0.f, "%s: momentum %g needs a momentum buffer (m is null)", name, (double)momentum);
+  SVL_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f),
+                "%s: nesterov momentum requires a momentum and zero dampening (momentum %g, dampening %g)", name,
+                (double)momentum, (double)dampening);
+  SVL_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)ema) & 15) == 0,
+                "%s: p, g, m and ema must be 16-byte aligned", name);
+  const float omd = (float)(1.0 - (double)dampening), ema_omd = (float)(1.0 - (double)ema_decay);
+  long grid = (total + SGD_TRIP - 1) / SGD_TRIP;
+  if (grid > SGD_GRID_CAP) grid = SGD_GRID_CAP;
+  const bool mom = momentum != 0.f, first = step == 1, with_ema = ema != nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  const long long* so = (const long long*)seg_off;
+#define SVL_SGD_GO(MOM, FIRST, NEST)                                                                                     \
+  sgd_launch<MOM, FIRST, NEST, SCALE>(with_ema, (unsigned)grid, st, p, g, m, so, seg_lr, seg_wd, nseg, (long)total, momentum, \
+                                      omd, gscale, ema, ema_decay, ema_omd)
+  if (!mom) SVL_SGD_GO(false, false, false);
+  else if (first && nesterov) SVL_SGD_GO(true, true, true);
+  else if (first) SVL_SGD_GO(true, true, false);
+  else if (nesterov) SVL_SGD_GO(true, false, true);
+  else SVL_SGD_GO(true, false, false);
+#undef SVL_SGD_GO
+  SVL_LAUNCH_CHECK(name);
+  return SVL_OK;
 }
 
 }  // namespace
@@ -128,45 +185,31 @@ void sgd_launch(bool with_ema, unsigned grid, hipStream_t st, float* p, const fl
 extern "C" int svl_adamw_step(float* p, const float* g, float* m, float* v, const int64_t* seg_off, const float* seg_lr,
                               const float* seg_wd, int nseg, int64_t total, float beta1, float beta2, float eps, int step,
                               float gscale, float* ema, float ema_decay, svl_stream_t stream) {
-  SVL_CHECK_ARG(p && g && m && v && seg_off && seg_lr && seg_wd && nseg > 0 && total > 0 && step >= 1,
-                "svl_adamw_step: bad args");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  long grid = (total + 1023) / 1024;
-  if (grid > 4096) grid = 4096;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                     (const long long*)seg_off, seg_lr, seg_wd, nseg, (long)total, beta1, beta2, eps, (float)bc1,
-                     (float)sqrt(bc2), gscale, ema, ema_decay);
-  SVL_LAUNCH_CHECK("svl_adamw_step");
-  return SVL_OK;
+  return adamw_step<float>("svl_adamw_step", p, g, m, v, seg_off, seg_lr, seg_wd, nseg, total, beta1, beta2, eps, step,
+                           gscale, ema, ema_decay, stream);
+}
+
+extern "C" int svl_adamw_step_dscale(float* p, const float* g, float* m, float* v, const int64_t* seg_off,
+                                     const float* seg_lr, const float* seg_wd, int nseg, int64_t total, float beta1,
+                                     float beta2, float eps, int step, const float* gscale_dev, float* ema,
+                                     float ema_decay, svl_stream_t stream) {
+  SVL_CHECK_ARG(gscale_dev, "svl_adamw_step_dscale: gscale_dev is null");
+  return adamw_step<const float*>("svl_adamw_step_dscale", p, g, m, v, seg_off, seg_lr, seg_wd, nseg, total, beta1, beta2,
+                                  eps, step, gscale_dev, ema, ema_decay, stream);
 }
 
 extern "C" int svl_sgd_step(float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr,
                             const float* seg_wd, int nseg, int64_t total, float momentum, float dampening, int nesterov,
                             int step, float gscale, float* ema, float ema_decay, svl_stream_t stream) {
-  SVL_CHECK_ARG(p && g && seg_off && seg_lr && seg_wd && nseg > 0 && total > 0 && step >= 1, "svl_sgd_step: bad args");
-  SVL_CHECK_ARG(m || momentum == 0.f, "svl_sgd_step: momentum %g needs a momentum buffer (m is null)", (double)momentum);
-  SVL_CHECK_ARG(!nesterov || (momentum > 0.f && dampening == 0.f),
-                "svl_sgd_step: nesterov momentum requires a momentum and zero dampening (momentum %g, dampening %g)",
-                (double)momentum, (double)dampening);
-  SVL_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)ema) & 15) == 0,
-                "svl_sgd_step: p, g, m and ema must be 16-byte aligned");
-  const float omd = (float)(1.0 - (double)dampening), ema_omd = (float)(1.0 - (double)ema_decay);
-  long grid = (total + SGD_TRIP - 1) / SGD_TRIP;
-  if (grid > SGD_GRID_CAP) grid = SGD_GRID_CAP;
-  const bool mom = momentum != 0.f, first = step == 1, with_ema = ema != nullptr;
-  const hipStream_t st = (hipStream_t)stream;
-  const long long* so = (const long long*)seg_off;
-#define SVL_SGD_GO(MOM, FIRST, NEST)                                                                              \
-  sgd_launch<MOM, FIRST, NEST>(with_ema, (unsigned)grid, st, p, g, m, so, seg_lr, seg_wd, nseg, (long)total, momentum, \
-                               omd, gscale, ema, ema_decay, ema_omd)
-  if (!mom) SVL_SGD_GO(false, false, false);
-  else if (first && nesterov) SVL_SGD_GO(true, true, true);
-  else if (first) SVL_SGD_GO(true, true, false);
-  else if (nesterov) SVL_SGD_GO(true, false, true);
-  else SVL_SGD_GO(true, false, false);
-#undef SVL_SGD_GO
-  SVL_LAUNCH_CHECK("svl_sgd_step");
-  return SVL_OK;
+  return sgd_step<float>("svl_sgd_step", p, g, m, seg_off, seg_lr, seg_wd, nseg, total, momentum, dampening, nesterov, step,
+                         gscale, ema, ema_decay, stream);
+}
+
+extern "C" int svl_sgd_step_dscale(float* p, const float* g, float* m, const int64_t* seg_off, const float* seg_lr,
+                                   const float* seg_wd, int nseg, int64_t total, float momentum, float dampening,
+                                   int nesterov, int step, const float* gscale_dev, float* ema, float ema_decay,
+                                   svl_stream_t stream) {
+  SVL_CHECK_ARG(gscale_dev, "svl_sgd_step_dscale: gscale_dev is null");
+  return sgd_step<const float*>("svl_sgd_step_dscale", p, g, m, seg_off, seg_lr, seg_wd, nseg, total, momentum, dampening,
+                                nesterov, step, gscale_dev, ema, ema_decay, stream);
 }

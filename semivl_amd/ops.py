@@ -1755,18 +1755,74 @@ def concept_max(pred, offsets_i32, N):
     return out
 
 
-def adamw_step(p, g, m, v, seg_off, seg_lr, seg_wd, nseg, beta1, beta2, eps, step, gscale=1.0, ema=None, ema_decay=0.0):
-    L.check(L.load().svl_adamw_step(_p(p), _p(g), _p(m), _p(v), _p(seg_off), _p(seg_lr), _p(seg_wd), nseg, p.numel(),
-                                    float(beta1), float(beta2), float(eps), int(step), float(gscale), _p(ema),
-                                    float(ema_decay), _st()), "svl_adamw_step")
+def adamw_step(p, g, m, v, seg_off, seg_lr, seg_wd, nseg, beta1, beta2, eps, step, gscale=1.0, ema=None, ema_decay=0.0,
+               gscale_dev=None):
+    """torch.optim.AdamW over the flat arena.  `gscale_dev`: ONE fp32 value on the device that the kernel reads in place of
+    the host float `gscale` (svl_adamw_step_dscale: stats[2:3] of grad_clip)."""
+    lib = L.load()
+    head = (_p(p), _p(g), _p(m), _p(v), _p(seg_off), _p(seg_lr), _p(seg_wd), nseg, p.numel(), float(beta1), float(beta2),
+            float(eps), int(step))
+    if gscale_dev is None:
+        L.check(lib.svl_adamw_step(*head, float(gscale), _p(ema), float(ema_decay), _st()), "svl_adamw_step")
+    else:
+        L.check(lib.svl_adamw_step_dscale(*head, _p(_dscale(gscale_dev, p)), _p(ema), float(ema_decay), _st()),
+                "svl_adamw_step_dscale")
 
 
 def sgd_step(p, g, m, seg_off, seg_lr, seg_wd, nseg, momentum, dampening, nesterov, step, gscale=1.0, ema=None,
-             ema_decay=0.0):
-    """torch.optim.SGD over the flat arena (svl_sgd_step); m is None without momentum."""
-    L.check(L.load().svl_sgd_step(_p(p), _p(g), _p(m), _p(seg_off), _p(seg_lr), _p(seg_wd), nseg, p.numel(),
-                                  float(momentum), float(dampening), int(bool(nesterov)), int(step), float(gscale),
-                                  _p(ema), float(ema_decay), _st()), "svl_sgd_step")
+             ema_decay=0.0, gscale_dev=None):
+    """torch.optim.SGD over the flat arena (svl_sgd_step); m is None without momentum.  `gscale_dev`: as in adamw_step
+    (svl_sgd_step_dscale)."""
+    lib = L.load()
+    head = (_p(p), _p(g), _p(m), _p(seg_off), _p(seg_lr), _p(seg_wd), nseg, p.numel(), float(momentum), float(dampening),
+            int(bool(nesterov)), int(step))
+    if gscale_dev is None:
+        L.check(lib.svl_sgd_step(*head, float(gscale), _p(ema), float(ema_decay), _st()), "svl_sgd_step")
+    else:
+        L.check(lib.svl_sgd_step_dscale(*head, _p(_dscale(gscale_dev, p)), _p(ema), float(ema_decay), _st()),
+                "svl_sgd_step_dscale")
+
+
+def _dscale(t, like):
+    assert t.dtype == torch.float32 and t.numel() == 1 and t.device == like.device, (t.dtype, tuple(t.shape), t.device)
+    return t
+
+
+def grad_clip_kind(norm_type):
+    """svl_grad_clip_f32's norm_kind of clip_grad_norm_'s norm_type: 0 for 2 / 2.0, 1 for float('inf') / 'inf'."""
+    if norm_type == "inf" or (isinstance(norm_type, (int, float)) and not isinstance(norm_type, bool)
+                              and norm_type == float("inf")):
+        return 1
+    if isinstance(norm_type, (int, float)) and not isinstance(norm_type, bool) and norm_type == 2:
+        return 0
+    raise NotImplementedError("grad_clip: norm_type %r is not supported (2 or inf)" % (norm_type,))
+
+
+def grad_clip_ws(g):
+    """The float64 scratch grad_clip needs for the arena `g` (svl_grad_clip_ws_doubles): allocate once, pass as ws=."""
+    return torch.empty(int(L.load().svl_grad_clip_ws_doubles(g.numel())), dtype=torch.float64, device=g.device)
+
+
+def grad_clip(g, max_norm, norm_type=2.0, gscale=1.0, stats=None, ws=None):
+    """torch.nn.utils.clip_grad_norm_ over the flat gradient arena `g`, formed on the device (svl_grad_clip_f32: two
+    launches, no atomics, no host sync): returns `stats` (fp32 [4]) = {norm of gscale * g, coef = min(max_norm / (norm + 1e-6),
+    1), gscale * coef, 1.0 if the norm is not finite}.  g itself is not rewritten: stats[2:3] is what a step applies
+    (`gscale_dev=` of adamw_step / sgd_step).  `ws`: float64 scratch of svl_grad_clip_ws_doubles(g.numel()) elements."""
+    lib = L.load()
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1, (g.dtype, tuple(g.shape))
+    kind = grad_clip_kind(norm_type)
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=g.device)
+    if ws is None:
+        ws = grad_clip_ws(g)
+    assert stats.dtype == torch.float32 and stats.numel() == 4 and stats.is_contiguous() and stats.device == g.device
+    assert ws.dtype == torch.float64 and ws.is_contiguous() and ws.device == g.device
+    assert ws.numel() >= lib.svl_grad_clip_ws_doubles(g.numel()), (ws.numel(), g.numel())
+    e0 = _prof_begin()
+    L.check(lib.svl_grad_clip_f32(_p(g), g.numel(), kind, float(gscale), float(max_norm), _p(ws), _p(stats), _st()),
+            "svl_grad_clip_f32")
+    _prof_end("grad_clip", e0, 4 * g.numel())
+    return stats
 
 
 def semivl_gscale(counts_i64, numel_u, lam, gscale_out, factors=None, mc_counts=None):

@@ -3,7 +3,12 @@
   semivl.py:123-125,339-345    mmcv param-wise AdamW + poly LR          -> FusedAdamW
   semivl.py:118-121,330-337    two-group SGD when cfg has no optimizer  -> FusedSGD.original
   mmseg build_optimizer        cfg['optimizer'] type AdamW / SGD        -> build_optimizer, optimizer_from_cfg
+  mmcv OptimizerHook           optimizer_config = dict(grad_clip=...)   -> grad_clip_from_cfg, ArenaOptimizer.set_grad_clip
+                               (not in semivl.py, which never clips)
 """
+import math
+import numbers
+
 import torch
 
 from . import ops
@@ -43,17 +48,76 @@ def arena_layout(sizes):
     return offs, o
 
 
+def _real(v):
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def _check_grad_clip(max_norm, norm_type):
+    """(max_norm as a float, norm_type as 2.0 or inf); ValueError for a max_norm that is no real number > 0,
+    NotImplementedError for a norm_type other than 2 / 2.0 / float('inf') / 'inf'."""
+    if not _real(max_norm) or not float(max_norm) > 0:
+        raise ValueError("grad_clip: max_norm must be a real number > 0 (inf allowed), got %r" % (max_norm,))
+    if norm_type == "inf":
+        norm_type = math.inf
+    if not _real(norm_type) or float(norm_type) not in (2.0, math.inf):
+        raise NotImplementedError("grad_clip: norm_type %r is not supported: the arena's norm kernel forms the L2 norm (2) "
+                                  "and the max norm (inf, 'inf')" % (norm_type,))
+    return float(max_norm), float(norm_type)
+
+
+def grad_clip_from_cfg(cfg):
+    """mmcv's `optimizer_config = dict(grad_clip=dict(max_norm=..., norm_type=2))` (OptimizerHook, which calls
+    torch.nn.utils.clip_grad_norm_(params, **grad_clip)) -> dict(max_norm, norm_type) for ArenaOptimizer, or None: no
+    'optimizer_config' key, optimizer_config None, or grad_clip None.  norm_type: 2 / 2.0 / float('inf') / 'inf' (default 2).
+    ValueError for values clip_grad_norm_ has no meaning for; NotImplementedError, naming the offender, for what torch / mmcv
+    would do and this package does not: another norm_type, error_if_nonfinite=True (it needs the norm on the host: a sync
+    every step), and any key of optimizer_config besides 'grad_clip' and 'type' (cumulative_iters, loss_scale, ... must not
+    be ignored silently).  error_if_nonfinite=False and `foreach` are accepted: neither changes the result."""
+    oc = cfg.get("optimizer_config")
+    if oc is None:
+        return None
+    if not isinstance(oc, dict):
+        raise ValueError("optimizer_config must be a dict or None, got %r" % (oc,))
+    other = sorted(k for k in oc if k not in ("grad_clip", "type"))
+    if other:
+        raise NotImplementedError("optimizer_config keys %s are not supported (grad_clip only)" % other)
+    gc = oc.get("grad_clip")
+    if gc is None:
+        return None
+    if not isinstance(gc, dict):
+        raise ValueError("optimizer_config['grad_clip'] must be a dict or None, got %r" % (gc,))
+    stray = sorted(k for k in gc if k not in ("max_norm", "norm_type", "error_if_nonfinite", "foreach"))
+    if stray:
+        raise ValueError("grad_clip: unknown keys %s (clip_grad_norm_ takes max_norm, norm_type, error_if_nonfinite, "
+                         "foreach)" % stray)
+    if "max_norm" not in gc:
+        raise ValueError("grad_clip needs max_norm")
+    if gc.get("error_if_nonfinite", False):
+        raise NotImplementedError("grad_clip: error_if_nonfinite=True is not supported: it needs the norm on the host, a "
+                                  "sync every step (optimizer.grad_stats[3] is the flag, on the device)")
+    max_norm, norm_type = _check_grad_clip(gc["max_norm"], gc.get("norm_type", 2))
+    return dict(max_norm=max_norm, norm_type=norm_type)
+
+
 class ArenaOptimizer:
     """ONE flat fp32 arena: parameters `p`, gradients `g` (`main_grad` views the model's backward writes into), the
     subclass's state buffers and optionally the EMA teacher, all laid out by arena_layout over `groups` (one dict per
     arena tensor: name, param, lr, weight_decay).  GradAllReducer and semivl_train_step rely on these attributes.
 
     A subclass validates its hyper-parameters, calls __init__ with its groups and the names of its state buffers, and
-    supplies `_launch()` (the step's one kernel), `_hyper()` (the hyper-parameters every param group of state_dict()
+    supplies `_launch(gscale_dev)` (the step's one kernel; gscale_dev None: the host float grad_scale), `_hyper()` (the hyper-parameters every param group of state_dict()
     carries), `_state_entry(ai)` (state_dict()'s entry of arena tensor ai, or None) and `_load_state(sd, index)` (copies
-    the entries in, returns the step count)."""
+    the entries in, returns the step count).
 
-    def __init__(self, model, groups, lr, wd, ema_decay, state):
+    `grad_clip` (None, or dict(max_norm, norm_type=2.0); set_grad_clip): torch.nn.utils.clip_grad_norm_ over all tensors of
+    the arena before every step, as mmcv's OptimizerHook(grad_clip=...) does -- formed and applied on the device.  The norm
+    is that of grad_scale * g (under GradAllReducer: of the averaged gradient, after the all-reduce, the same on every
+    rank); `grad_stats` (fp32 [4] on the device, None without clipping) = {norm, coef, grad_scale * coef, non-finite flag}
+    of the last step is what a training loop logs from.  g is not rewritten: the step kernel reads grad_stats[2] as its
+    gradient scale.  Non-finite gradients: as in torch with error_if_nonfinite=False, nothing is skipped.  Configuration,
+    not state: state_dict() does not carry it."""
+
+    def __init__(self, model, groups, lr, wd, ema_decay, state, grad_clip=None):
         self.lr, self.wd, self.groups = lr, wd, groups
         arena_index = {id(g_["param"]): i for i, g_ in enumerate(groups)}
         self.all_params = [(n, arena_index.get(id(p))) for n, p in model.named_parameters()]   # (name, arena slot | None)
@@ -83,6 +147,21 @@ class ArenaOptimizer:
         self.step_count = 0
         self.grad_scale = 1.0
         self._lr_factor = 1.0     # the schedule's current factor (poly_lr): lr of the groups outside the arena
+        self.grad_clip, self.grad_stats, self._clip_ws = None, None, None
+        if grad_clip is not None:
+            self.set_grad_clip(**grad_clip)
+
+    def set_grad_clip(self, max_norm, norm_type=2.0):
+        """Clip the arena's gradient norm to max_norm before every step (max_norm=inf: only report it); None: off."""
+        if max_norm is None:
+            self.grad_clip, self.grad_stats = None, None
+            return
+        max_norm, norm_type = _check_grad_clip(max_norm, norm_type)
+        self.grad_clip = dict(max_norm=max_norm, norm_type=norm_type)
+        if self.grad_stats is None:
+            self.grad_stats = ops.zeros(4, device=self.g.device)
+        if self._clip_ws is None:
+            self._clip_ws = ops.grad_clip_ws(self.g)
 
     @property
     def param_groups(self):
@@ -103,7 +182,12 @@ class ArenaOptimizer:
     def step(self):
         self._fold_autograd_grads()
         self.step_count += 1
-        self._launch()
+        if self.grad_clip is None:
+            self._launch(None)
+        else:
+            ops.grad_clip(self.g, self.grad_clip["max_norm"], self.grad_clip["norm_type"], gscale=self.grad_scale,
+                          stats=self.grad_stats, ws=self._clip_ws)
+            self._launch(self.grad_stats[2:3])
         ops.weights_changed()    # cached bf16 planes of the trainable weights are stale now (ops.weight_planes)
 
     def _seg(self, buf, ai):
@@ -193,18 +277,18 @@ class FusedAdamW(ArenaOptimizer):
     """torch.optim.AdamW semantics over the arena: parameters, gradients, exp_avg `m`, exp_avg_sq `v`; one svl_adamw_step
     launch per step (28 B/param of HBM traffic)."""
 
-    def __init__(self, model, optimizer_cfg, ema_decay=None):
+    def __init__(self, model, optimizer_cfg, ema_decay=None, grad_clip=None):
         assert optimizer_cfg.get("type", "AdamW") == "AdamW"
         lr, wd = optimizer_cfg["lr"], optimizer_cfg.get("weight_decay", 0.01)
         self.betas, self.eps = optimizer_cfg.get("betas", (0.9, 0.999)), optimizer_cfg.get("eps", 1e-8)
         ck = optimizer_cfg.get("paramwise_cfg", {}).get("custom_keys", {})
         named = [(n, p) for n, p in model.named_parameters() if _trainable(n, p)]
-        super().__init__(model, mmcv_param_groups(named, lr, wd, ck), lr, wd, ema_decay, ("m", "v"))
+        super().__init__(model, mmcv_param_groups(named, lr, wd, ck), lr, wd, ema_decay, ("m", "v"), grad_clip)
 
-    def _launch(self):
+    def _launch(self, gscale_dev):
         ops.adamw_step(self.p, self.g, self.m, self.v, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups),
                        self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale, self.ema,
-                       self.ema_decay)
+                       self.ema_decay, gscale_dev=gscale_dev)
 
     def _hyper(self):
         return dict(betas=tuple(self.betas), eps=self.eps, amsgrad=False)
@@ -282,7 +366,7 @@ class FusedSGD(ArenaOptimizer):
     reference builds when cfg has no 'optimizer' key (semivl.py:118-121), re-scheduled by semivl.py:330-337; its
     param_groups, state_dict() and poly_lr follow the reference's two groups (`lr_multi` set), everything else is shared."""
 
-    def __init__(self, model, optimizer_cfg, ema_decay=None, *, lr_multi=None):
+    def __init__(self, model, optimizer_cfg, ema_decay=None, *, lr_multi=None, grad_clip=None):
         if optimizer_cfg.get("type", "SGD") != "SGD":
             raise ValueError("FusedSGD got optimizer type %r" % (optimizer_cfg.get("type"),))
         momentum, dampening = optimizer_cfg.get("momentum", 0.0), optimizer_cfg.get("dampening", 0.0)
@@ -299,21 +383,22 @@ class FusedSGD(ArenaOptimizer):
             self._members, self._index, groups = sgd_original_groups(model, lr, lr_multi, wd)
             self._pg = [dict(lr=lr), dict(lr=lr * lr_multi)]
         self.m = None
-        super().__init__(model, groups, lr, wd, ema_decay, ("m",) if momentum != 0 else ())
+        super().__init__(model, groups, lr, wd, ema_decay, ("m",) if momentum != 0 else (), grad_clip)
 
     @classmethod
-    def original(cls, model, lr, lr_multi, momentum=0.9, weight_decay=1e-4, ema_decay=None):
+    def original(cls, model, lr, lr_multi, momentum=0.9, weight_decay=1e-4, ema_decay=None, grad_clip=None):
         return cls(model, dict(type="SGD", lr=lr, momentum=momentum, weight_decay=weight_decay), ema_decay,
-                   lr_multi=lr_multi)
+                   lr_multi=lr_multi, grad_clip=grad_clip)
 
     @property
     def param_groups(self):
         """Per-tensor groups (mmcv layout), or the reference's two groups for the `original` recipe."""
         return self.groups if self._members is None else self._pg
 
-    def _launch(self):
+    def _launch(self, gscale_dev):
         ops.sgd_step(self.p, self.g, self.m, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups), self.momentum,
-                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema, self.ema_decay)
+                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema, self.ema_decay,
+                     gscale_dev=gscale_dev)
 
     def _hyper(self):
         return dict(momentum=self.momentum, dampening=self.dampening, nesterov=self.nesterov, maximize=False, foreach=None,
@@ -387,19 +472,24 @@ class FusedSGD(ArenaOptimizer):
         self._stage_lr([g_["lr"] for g_ in self.groups])
 
 
-def build_optimizer(model, optimizer_cfg, ema_decay=None):
-    """mmseg's build_optimizer for the types this package runs fused: AdamW (exp 40-44) and SGD."""
+def build_optimizer(model, optimizer_cfg, ema_decay=None, grad_clip=None):
+    """mmseg's build_optimizer for the types this package runs fused: AdamW (exp 40-44) and SGD.  `grad_clip`: None or
+    dict(max_norm, norm_type) (ArenaOptimizer); passed on only when set."""
     kind = optimizer_cfg.get("type", "AdamW")
+    clip = {} if grad_clip is None else dict(grad_clip=grad_clip)
     if kind == "AdamW":
-        return FusedAdamW(model, optimizer_cfg, ema_decay=ema_decay)
+        return FusedAdamW(model, optimizer_cfg, ema_decay=ema_decay, **clip)
     if kind == "SGD":
-        return FusedSGD(model, optimizer_cfg, ema_decay=ema_decay)
+        return FusedSGD(model, optimizer_cfg, ema_decay=ema_decay, **clip)
     raise ValueError("optimizer type %r is not supported (AdamW, SGD)" % (kind,))
 
 
 def optimizer_from_cfg(model, cfg, ema_decay=None):
     """semivl.py:118-125: without an 'optimizer' key the reference's two-group SGD (cfg['lr'], cfg['lr_multi']), with it
-    whatever the key builds."""
+    whatever the key builds.  cfg['optimizer_config'] in mmcv's spelling (grad_clip_from_cfg) switches gradient-norm clipping
+    on for either; without the key, or with grad_clip=None, the optimizer launches what it always did."""
+    grad_clip = grad_clip_from_cfg(cfg)
+    clip = {} if grad_clip is None else dict(grad_clip=grad_clip)
     if "optimizer" not in cfg:
-        return FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay)
-    return build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay)
+        return FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay, **clip)
+    return build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay, **clip)

@@ -19,8 +19,8 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import (FusedAdamW, FusedSGD, build_optimizer, mmcv_param_groups, optimizer_from_cfg,  # noqa: F401
-                    sgd_original_groups, sgd_original_lr)
+from .optim import (FusedAdamW, FusedSGD, build_optimizer, grad_clip_from_cfg, mmcv_param_groups,  # noqa: F401
+                    optimizer_from_cfg, sgd_original_groups, sgd_original_lr)
 
 
 # ------------------------------------------------------------------------------------------------ reference-named helpers
@@ -255,7 +255,7 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
     optimizer.step() and optimizer.poly_lr(iters, total_iters) -- supervised.py:294-300 has no warm-up and no
     scheduler_max_iters, so cfg's `warmup_iters` / `scheduler_max_iters` are ignored here.
     Returns the device tensor `loss` [1]; with `return_aux` also dict(pred_x [B, N, S, S], dlogits, mask_x_ohem (None
-    without OHEM), upsample_in_loss).  Per-step overrides taken from `cfg` (`wgrad_stream`, `overlap_streams`,
+    without OHEM), upsample_in_loss; `grad_stats` too when the optimizer clips the gradient norm).  Per-step overrides taken from `cfg` (`wgrad_stream`, `overlap_streams`,
     `head_remat`, `head_chunk_class_images`, `act_mem_fraction`) are set up for one decode of B samples and undone when
     the step ends -- also when it raises -- as in semivl_train_step."""
     with _step_scope(model, ("remat", "chunk_class_images", "act_limit_bytes")):
@@ -346,7 +346,8 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
         if up is not None:
             pred_x = pred_x.contiguous()
             pred_x = ops.bilinear_planes_fwd(pred_x, pred_x.shape[2], pred_x.shape[3], up[2], up[0], up[1])
-        return loss, dict(pred_x=pred_x, dlogits=dlogits, mask_x_ohem=mask_x_ohem, upsample_in_loss=up is not None)
+        aux = dict(pred_x=pred_x, dlogits=dlogits, mask_x_ohem=mask_x_ohem, upsample_in_loss=up is not None)
+        return loss, _with_grad_stats(aux, optimizer)
     return loss
 
 
@@ -605,8 +606,16 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
                    pred_x=full_res(pred_x.detach()), pred_s1=full_res(pred_s1.detach()), pred_w=full_res(pred_w.detach()),
                    pred_w_other=full_res(pred_w_other), dl4=dl4, dls=dls, upsample_in_loss=up is not None,
                    mask_x_ohem=mask_x_ohem)
-        return losses, aux
+        return losses, _with_grad_stats(aux, optimizer)
     return losses
+
+
+def _with_grad_stats(aux, optimizer):
+    """aux['grad_stats'] = the optimizer's device tensor {norm, coef, scale, non-finite flag} when it clips the gradient
+    norm (ArenaOptimizer.grad_clip); without clipping aux keeps exactly its keys."""
+    if getattr(optimizer, "grad_clip", None) is not None:
+        aux["grad_stats"] = optimizer.grad_stats
+    return aux
 
 
 def _cat2i(a, b):
@@ -636,6 +645,9 @@ class GradAllReducer:
     every rank) and makes the compute stream wait for all collectives before the optimizer.  xGMI is point-to-point (~153 GB/s per
     link): a 25 MB bucket is ~0.3 ms on the ring, so few, large buckets; the 1/W of the mean is folded into the optimizer's
     kernel (grad_scale).  Loss normalisers stay per-rank as in the reference.
+    Gradient-norm clipping (ArenaOptimizer.grad_clip) needs nothing from the reducer: optimizer.step() runs after finish(),
+    on the reduced arena every rank holds alike, and forms the norm of grad_scale * g -- the norm of the averaged gradient,
+    identical on every rank, as under the reference's DDP.
     With `overlap=False`, or on backends that cannot run stream-ordered collectives on GPU tensors (gloo: it stages
     through the host and stalls the launching thread), the same buckets are reduced back to back in finish()."""
 
