@@ -748,6 +748,26 @@ int svl_avgpool_cat_bwd(const float* dy, int imgs, int H, int W, int C, int PH, 
 int svl_avgpool_cat_bwd_text(const float* dy, int imgs, int64_t HWp, int C, int Ct, int nclass, float* part, float* dtext,
                              svl_stream_t stream);
 
+/* Test-time augmentation of the evaluator (mmseg 0.x MultiScaleFlipAug + EncoderDecoder.aug_test; csrc/tta.hip).
+ * A view of the image: src [planes, h, w] -> dst [planes, oh, ow], bilinear with ATen's upsample_bilinear2d arithmetic,
+ * align_corners = False (one fp32 scale per axis, area_pixel_compute_source_index, guard_index_and_lambda, as
+ * svl_bilinear_planes_fwd); flip != 0 mirrors the columns: dst[p, y, x] = resized[p, y, ow - 1 - x], the unflipped
+ * formula evaluated at column ow - 1 - x.  oh == h && ow == w moves the elements: a bit-exact copy, with flip a bit-exact
+ * mirror. */
+int svl_tta_view_f32(const float* src, int64_t planes, int h, int w, int oh, int ow, int flip, float* dst,
+                     svl_stream_t stream);
+/* The class scores of one view, formed at the target resolution and added to the running mean in one pass:
+ * src [B, N, h, w], dst [B, N, H, W].  For every destination pixel (b, y, x): xs = flip ? W - 1 - x : x, u_c = the bilinear
+ * value (arithmetic as above, align_corners as given) of plane c of src at destination index (y, xs);
+ *   kind 0 (logits):                       s_c = softmax_c(u)  (the maximum is subtracted first)
+ *   kind 1 (summed window probabilities):  s_c = u_c / sum_k u_k, and s_c = 0 for every c where that total is 0
+ *   dst[b, c, y, x] = (accumulate ? dst[b, c, y, x] : 0) + scale * s_c.
+ * One owner per destination element, no atomics: two runs agree bit for bit.  dst is read at most once (not at all
+ * with accumulate == 0) and written once per element; consecutive lanes own consecutive x (16-byte stores when W % 4 == 0
+ * and dst is 16-byte aligned, scalar stores otherwise).  Any N >= 1.  kind outside {0, 1}: status -1. */
+int svl_tta_accum_f32(const float* src, int B, int N, int h, int w, float* dst, int H, int W, int kind,
+                      int align_corners, int flip, float scale, int accumulate, svl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Optimiser (semivl.py:123-125,328,339-345: torch AdamW, one param group per tensor, poly LR).
  * Flat arena of `nseg` segments; seg_* arrays are DEVICE arrays of length nseg.

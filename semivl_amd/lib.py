@@ -200,6 +200,8 @@ SIGNATURES = {
     "svl_avgpool_cat_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     "svl_avgpool_cat_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "svl_avgpool_cat_bwd_text": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _P]),
+    "svl_tta_view_f32": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _P]),
+    "svl_tta_accum_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
     "svl_gap_tokens_fwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _P]),
     "svl_gap_tokens_bwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _I, _P]),
     "svl_bcast_rows_fwd": (_I, [_P, _L, _I, _L, _I, _P, _L, _I, _P]),

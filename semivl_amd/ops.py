@@ -1519,6 +1519,31 @@ def bilinear_planes_bwd(dy, h, w, align, H, W, out=None):
     return dx
 
 
+def tta_view(img, oh, ow, flip, out=None):
+    """A test-time-augmentation view of `img` [..., h, w] (svl_tta_view_f32): bilinear to [..., oh, ow], align_corners = False,
+    columns mirrored when `flip`; the same size moves the elements (bit-exact copy / mirror)."""
+    _chk(img)
+    assert img.is_contiguous()
+    h, w = img.shape[-2:]
+    planes = img.numel() // (h * w)
+    y = empty(*img.shape[:-2], oh, ow, device=img.device) if out is None else out
+    assert _chk(y).is_contiguous() and y.numel() == planes * oh * ow
+    L.check(L.load().svl_tta_view_f32(_p(img), planes, h, w, oh, ow, 1 if flip else 0, _p(y), _st()), "svl_tta_view_f32")
+    return y
+
+
+def tta_accum(src, dst, kind, align, flip, scale, accumulate):
+    """dst [B, N, H, W] (=|+=) scale * class scores of the view's `src` [B, N, h, w] resized to (H, W) and un-flipped
+    (svl_tta_accum_f32): kind 0 softmax of logits, kind 1 probability sums over their total."""
+    _chk(src), _chk(dst)
+    assert src.is_contiguous() and dst.is_contiguous() and src.dim() == 4 and dst.shape[:2] == src.shape[:2]
+    Bn, N, h, w = src.shape
+    L.check(L.load().svl_tta_accum_f32(_p(src), Bn, N, h, w, _p(dst), dst.shape[2], dst.shape[3], int(kind),
+                                       1 if align else 0, 1 if flip else 0, float(scale), 1 if accumulate else 0, _st()),
+            "svl_tta_accum_f32")
+    return dst
+
+
 def avgpool_cat_fwd(x, imgs, H, W, Cc, P, text, nclass, out=None):
     """P: int (square window) or (PH, PW).  `out`: a contiguous fp32 tensor of the result's size to write instead."""
     PH, PW = (P, P) if isinstance(P, int) else P
