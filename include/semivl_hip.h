@@ -828,6 +828,24 @@ int svl_grad_clip_f32(const float* g, int64_t total, int norm_kind, float gscale
                       float* stats /* [4] */, svl_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Moving average over a table of independent segments: the mean teacher's BatchNorm running statistics against the
+ * student's (semivl_amd/ema.py; the parameters' average is the `ema` arena of the step entries above, not this).
+ *   dst[s][i] = decay * dst[s][i] + (1 - decay) * src[s][i]     for i < seg_off[s + 1] - seg_off[s],  s < nseg
+ * dst, src: DEVICE arrays of nseg pointers; seg_off: DEVICE array of nseg + 1 offsets (only the differences are used).
+ * decay in [0, 1]; 1 - decay is formed on the host as (float)(1.0 - (double)decay), like the SGD step's ema factor, and
+ * the expression is evaluated in fp32 as fma(decay, dst, fl((1 - decay) * src)): two roundings, the same on every path.
+ * ONE launch: one block per segment, the grid capped at 256 blocks (further segments take further trips); one owner per
+ * element, no atomics, no host sync: two calls on the same data give the same bits.  A segment whose two pointers are
+ * 16-byte aligned moves 16 bytes per lane (its last length % 4 elements singly), any other segment 4 bytes per lane; the
+ * arithmetic per element is the same, so both give the same bits.  decay == 0 copies src.
+ * The tables live on the device, so the entry cannot compare the pointers they hold: segments must not overlap, and
+ * dst[s] != src[s] for every s is the business of whoever builds the tables (ops.ema_segment_tables refuses it by this
+ * entry's name); passing the SAME table as dst and src is refused here.  nseg == 0 returns SVL_OK without a launch; a
+ * negative nseg, a null table or a decay outside [0, 1] is SVL_ERR_INVALID_ARG. */
+int svl_ema_segments_f32(float* const* dst, const float* const* src, const int64_t* seg_off /* [nseg + 1] */, int nseg,
+                         float decay, svl_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * BatchNorm2d (batch statistics, SyncBN-ready) and MaxPool2d(3, 2, 1) on channels-last [rows, C] activations: the ops of
  * the Cityscapes recipe's convolutional side encoder (`conv_encoder` = mmseg ResNetV1c deep stem + layer1 with
  * norm_cfg SyncBN; reference model/vlm.py:50-53,120-121, configs/_base_/models/vlm-vlg-aspp-s2p4-skr04-ftap-mcvitb.py:50-60).

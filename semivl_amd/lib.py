@@ -212,6 +212,7 @@ SIGNATURES = {
     "svl_sgd_step_dscale": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _I, _I, _P, _P, _F, _P]),
     "svl_grad_clip_ws_doubles": (_L, [_L]),
     "svl_grad_clip_f32": (_I, [_P, _L, _I, _F, _F, _P, _P, _P]),
+    "svl_ema_segments_f32": (_I, [_P, _P, _P, _I, _F, _P]),
     "svl_lora_merge_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _F, _P, _P, _L, _P]),
     "svl_lora_wgrad_ws_floats": (_L, [_I, _I, _I]),
     "svl_lora_wgrad_f32": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _F, _P, _I, _P, _I, _P, _P]),

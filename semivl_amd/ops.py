@@ -454,6 +454,13 @@ def weights_changed():
     WEIGHT_EPOCH += 1
 
 
+def _weight_epoch(base):
+    """The epoch part of a weight cache's version: WEIGHT_EPOCH for tensors a step kernel rewrites behind torch's version
+    counter -- trainable parameters, and the mean teacher's views of the EMA arena (ema.py marks them `_svl_rewritten`:
+    they do not require a gradient) -- and 0 for frozen ones."""
+    return WEIGHT_EPOCH if (base.requires_grad or getattr(base, "_svl_rewritten", False)) else 0
+
+
 def weight_planes(W, transpose=False, fmt=None):
     """Planes of a weight matrix (or of a row slice of one), split ONCE and cached: frozen weights for the life of the
     process (keyed on storage + torch version counter), trainable ones until the next optimizer step.  h2 planes carry the
@@ -467,7 +474,7 @@ def weight_planes(W, transpose=False, fmt=None):
     if not isinstance(base, torch.nn.Parameter):      # not a parameter: no identity to key a cache on
         return build()
     key = (W.data_ptr(), tuple(W.shape), W.stride(0), transpose, fmt)
-    ver = (base._version, WEIGHT_EPOCH if base.requires_grad else 0)
+    ver = (base._version, _weight_epoch(base))
     hit = _WPLANES.get(key)
     if hit is not None and hit[0] == ver and hit[2]() is base:    # (a freed parameter's address may be handed out again)
         return hit[1].get()
@@ -481,7 +488,7 @@ def weight_planes(W, transpose=False, fmt=None):
 def _out_bound(B, bias):
     """Device float[2] = {max row norm of B, max |bias|} for svl_pgemm_desc::b_bound (one single-block launch,
     svl_bound2_f32), cached on the weight planes per (bias tensor version, stream)."""
-    key = (None if bias is None else (bias.data_ptr(), bias._version, WEIGHT_EPOCH if bias.requires_grad else 0),
+    key = (None if bias is None else (bias.data_ptr(), bias._version, _weight_epoch(bias)),
            torch.cuda.current_stream().cuda_stream)
     if B._bd is None:
         B._bd = {}
@@ -1258,7 +1265,7 @@ def cached_pack(W, tag, fn):
     if not isinstance(base, torch.nn.Parameter):
         return fn(W.detach())
     key = (W.data_ptr(), tuple(W.shape), tag)
-    ver = (base._version, WEIGHT_EPOCH if base.requires_grad else 0)
+    ver = (base._version, _weight_epoch(base))
     hit = _PACKS.get(key)
     if hit is not None and hit[0] == ver and hit[2]() is base:    # weak reference: the address of a freed parameter of an
         return hit[1].get()                                        # earlier model may be handed out again by the allocator
@@ -1806,6 +1813,41 @@ def sgd_step(p, g, m, seg_off, seg_lr, seg_wd, nseg, momentum, dampening, nester
     else:
         L.check(lib.svl_sgd_step_dscale(*head, _p(_dscale(gscale_dev, p)), _p(ema), float(ema_decay), _st()),
                 "svl_sgd_step_dscale")
+
+
+def ema_segment_tables(dst, src):
+    """(dst table, src table, seg_off, nseg) on the device for ema_segments: `dst` / `src` are lists of contiguous fp32
+    tensors of pairwise equal sizes.  Built once by the caller (one host-to-device copy each) and valid while the tensors
+    live.  The tables sit on the device, where svl_ema_segments_f32 cannot compare what they hold, so the refusal of
+    dst[s] == src[s] -- and of overlapping segments -- is made here."""
+    assert len(dst) == len(src)
+    spans = []
+    for i, (d, s) in enumerate(zip(dst, src)):
+        for t in (d, s):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (i, t.device, t.dtype)
+        assert d.numel() == s.numel() and d.device == s.device, (i, tuple(d.shape), tuple(s.shape))
+        if d.data_ptr() == s.data_ptr():
+            raise ValueError("svl_ema_segments_f32: dst == src for segment %d: a segment must not be averaged with itself" % i)
+        spans.append((d.data_ptr(), d.data_ptr() + 4 * d.numel(), True))
+        spans.append((s.data_ptr(), s.data_ptr() + 4 * s.numel(), False))
+    spans.sort()
+    for (a0, a1, aw), (b0, b1, bw) in zip(spans, spans[1:]):
+        if b0 < a1 and (aw or bw):
+            raise ValueError("svl_ema_segments_f32: a written segment overlaps another segment")
+    dev = dst[0].device if dst else torch.device("cuda", torch.cuda.current_device())
+    off = [0]
+    for d in dst:
+        off.append(off[-1] + d.numel())
+    mk = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+    return mk([d.data_ptr() for d in dst]), mk([s.data_ptr() for s in src]), mk(off), len(dst)
+
+
+def ema_segments(dst_tab, src_tab, seg_off, nseg, decay):
+    """dst[s] = decay * dst[s] + (1 - decay) * src[s] for every segment of the tables (ema_segment_tables): ONE launch
+    (svl_ema_segments_f32), none for nseg == 0."""
+    assert seg_off.dtype == torch.int64 and seg_off.numel() == nseg + 1 and dst_tab.numel() == nseg == src_tab.numel()
+    L.check(L.load().svl_ema_segments_f32(_p(dst_tab), _p(src_tab), _p(seg_off), int(nseg), float(decay), _st()),
+            "svl_ema_segments_f32")
 
 
 def _dscale(t, like):

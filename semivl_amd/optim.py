@@ -5,6 +5,8 @@
   mmseg build_optimizer        cfg['optimizer'] type AdamW / SGD        -> build_optimizer, optimizer_from_cfg
   mmcv OptimizerHook           optimizer_config = dict(grad_clip=...)   -> grad_clip_from_cfg, ArenaOptimizer.set_grad_clip
                                (not in semivl.py, which never clips)
+  third_party/unimatch/eval.py:29,132-133  `--ema` reads checkpoint['ema_model'] -> ema_from_cfg, ArenaOptimizer.ema /
+                               ema_decay_at: the average the mean teacher (ema.py) is built on
 """
 import math
 import numbers
@@ -99,6 +101,46 @@ def grad_clip_from_cfg(cfg):
     return dict(max_norm=max_norm, norm_type=norm_type)
 
 
+def ema_from_cfg(cfg):
+    """cfg['ema'] = dict(decay=0.996, warmup=True, teacher=True, buffers='ema') -> a dict with all four keys, or None
+    without the key.  `decay` (required): a real number in [0, 1), no bool.  `warmup` (bool, default True): the decay of
+    step t is min(decay, 1 - 1 / t) (ArenaOptimizer.ema_decay_at).  `teacher` (bool, default True): whether pseudo-labels
+    come from the averaged weights or the average is only maintained.  `buffers`: 'ema' (default) or 'copy', the rule of
+    the teacher's BatchNorm statistics (ema.EmaTeacher).  A non-dict, an unknown key or a value out of range raises
+    ValueError naming it."""
+    if "ema" not in cfg:
+        return None
+    e = cfg["ema"]
+    if not isinstance(e, dict):
+        raise ValueError("ema must be a dict(decay=..., warmup=True, teacher=True, buffers='ema'), got %r" % (e,))
+    stray = sorted(k for k in e if k not in ("decay", "warmup", "teacher", "buffers"))
+    if stray:
+        raise ValueError("ema: unknown keys %s (decay, warmup, teacher, buffers)" % stray)
+    if "decay" not in e:
+        raise ValueError("ema needs decay")
+    decay = e["decay"]
+    if not _real(decay) or not 0.0 <= float(decay) < 1.0:
+        raise ValueError("ema: decay must be a real number in [0, 1), got %r" % (decay,))
+    out = dict(decay=float(decay))
+    for k in ("warmup", "teacher"):
+        v = e.get(k, True)
+        if not isinstance(v, bool):
+            raise ValueError("ema: %s must be a bool, got %r" % (k, v))
+        out[k] = v
+    out["buffers"] = e.get("buffers", "ema")
+    if out["buffers"] not in ("ema", "copy"):
+        raise ValueError("ema: buffers must be 'ema' or 'copy', got %r" % (out["buffers"],))
+    return out
+
+
+def ema_decay_schedule(decay, warmup, t):
+    """The EMA decay of step t (1-based), in double: `decay`, or with warm-up min(decay, 1 - 1 / t) -- 0 at step 1 (the
+    average starts as the first updated weights) and, while 1 - 1 / t < decay, the plain arithmetic mean of p_1 .. p_t."""
+    if t < 1:
+        raise ValueError("ema_decay_at: step %r (steps count from 1)" % (t,))
+    return min(decay, 1.0 - 1.0 / t) if warmup else decay
+
+
 class ArenaOptimizer:
     """ONE flat fp32 arena: parameters `p`, gradients `g` (`main_grad` views the model's backward writes into), the
     subclass's state buffers and optionally the EMA teacher, all laid out by arena_layout over `groups` (one dict per
@@ -137,6 +179,7 @@ class ArenaOptimizer:
             g_["initial_lr"] = g_["lr"]
         self.ema = self.p.clone() if ema_decay is not None else None
         self.ema_decay = ema_decay or 0.0
+        self.ema_warmup = False   # (set_ema_warmup / cfg['ema']: the decay of step t is min(ema_decay, 1 - 1 / t))
         self.seg_off = torch.tensor(self._offs + [self.total], dtype=torch.int64, device=dev)
         self.seg_wd = torch.tensor([g_["weight_decay"] for g_ in groups], dtype=torch.float32, device=dev)
         self._lr_host = torch.tensor([g_["lr"] for g_ in groups], dtype=torch.float32)
@@ -162,6 +205,19 @@ class ArenaOptimizer:
             self.grad_stats = ops.zeros(4, device=self.g.device)
         if self._clip_ws is None:
             self._clip_ws = ops.grad_clip_ws(self.g)
+
+    def set_ema_warmup(self, warmup=True):
+        """Warm the EMA up (cfg['ema']['warmup']): see ema_decay_at.  Configuration, not state, like grad_clip."""
+        if not isinstance(warmup, bool):
+            raise ValueError("ema: warmup must be a bool, got %r" % (warmup,))
+        if warmup and self.ema is None:
+            raise ValueError("ema: warmup without an EMA arena (build the optimizer with ema_decay= or cfg['ema'])")
+        self.ema_warmup = warmup
+
+    def ema_decay_at(self, t):
+        """d_t, the EMA decay the step kernel is handed at step t (1-based: step_count after its increment), formed on the
+        host in double: ema_decay, or with warm-up min(ema_decay, 1 - 1 / t)."""
+        return ema_decay_schedule(self.ema_decay, self.ema_warmup, t)
 
     @property
     def param_groups(self):
@@ -288,7 +344,7 @@ class FusedAdamW(ArenaOptimizer):
     def _launch(self, gscale_dev):
         ops.adamw_step(self.p, self.g, self.m, self.v, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups),
                        self.betas[0], self.betas[1], self.eps, self.step_count, self.grad_scale, self.ema,
-                       self.ema_decay, gscale_dev=gscale_dev)
+                       self.ema_decay_at(self.step_count), gscale_dev=gscale_dev)
 
     def _hyper(self):
         return dict(betas=tuple(self.betas), eps=self.eps, amsgrad=False)
@@ -397,8 +453,8 @@ class FusedSGD(ArenaOptimizer):
 
     def _launch(self, gscale_dev):
         ops.sgd_step(self.p, self.g, self.m, self.seg_off, self.seg_lr, self.seg_wd, len(self.groups), self.momentum,
-                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema, self.ema_decay,
-                     gscale_dev=gscale_dev)
+                     self.dampening, self.nesterov, self.step_count, self.grad_scale, self.ema,
+                     self.ema_decay_at(self.step_count), gscale_dev=gscale_dev)
 
     def _hyper(self):
         return dict(momentum=self.momentum, dampening=self.dampening, nesterov=self.nesterov, maximize=False, foreach=None,
@@ -487,9 +543,22 @@ def build_optimizer(model, optimizer_cfg, ema_decay=None, grad_clip=None):
 def optimizer_from_cfg(model, cfg, ema_decay=None):
     """semivl.py:118-125: without an 'optimizer' key the reference's two-group SGD (cfg['lr'], cfg['lr_multi']), with it
     whatever the key builds.  cfg['optimizer_config'] in mmcv's spelling (grad_clip_from_cfg) switches gradient-norm clipping
-    on for either; without the key, or with grad_clip=None, the optimizer launches what it always did."""
+    on for either; without the key, or with grad_clip=None, the optimizer launches what it always did.
+    cfg['ema'] (ema_from_cfg) builds either with the EMA arena: decay and warm-up from the key (`ema_cfg` on the optimizer
+    keeps the whole dict for ema.EmaTeacher.from_cfg).  An explicit `ema_decay=` together with the key is a ValueError;
+    `ema_decay=` alone is a constant decay without warm-up, as before."""
     grad_clip = grad_clip_from_cfg(cfg)
+    ema = ema_from_cfg(cfg)
+    if ema is not None and ema_decay is not None:
+        raise ValueError("optimizer_from_cfg: ema_decay=%r and cfg['ema'] both set the EMA decay; give one" % (ema_decay,))
+    if ema is not None:
+        ema_decay = ema["decay"]
     clip = {} if grad_clip is None else dict(grad_clip=grad_clip)
     if "optimizer" not in cfg:
-        return FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay, **clip)
-    return build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay, **clip)
+        opt = FusedSGD.original(model, cfg["lr"], cfg["lr_multi"], ema_decay=ema_decay, **clip)
+    else:
+        opt = build_optimizer(model, cfg["optimizer"], ema_decay=ema_decay, **clip)
+    if ema is not None:
+        opt.set_ema_warmup(ema["warmup"])
+        opt.ema_cfg = ema
+    return opt

@@ -19,8 +19,8 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .optim import (FusedAdamW, FusedSGD, build_optimizer, grad_clip_from_cfg, mmcv_param_groups,  # noqa: F401
-                    optimizer_from_cfg, sgd_original_groups, sgd_original_lr)
+from .optim import (FusedAdamW, FusedSGD, build_optimizer, ema_from_cfg, grad_clip_from_cfg,  # noqa: F401
+                    mmcv_param_groups, optimizer_from_cfg, sgd_original_groups, sgd_original_lr)
 
 
 # ------------------------------------------------------------------------------------------------ reference-named helpers
@@ -228,7 +228,7 @@ def _step_scope(model, head_attrs=("remat", "chunk_class_images")):
 
 
 def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                      return_aux=False):
+                      return_aux=False, teacher=None):
     """One iteration of semivl.py:223-328 (see _semivl_train_step for the body).  Per-step overrides taken from `cfg`
     (`wgrad_stream`, `overlap_streams`, `head_remat`, `head_chunk_class_images`) and the decode head's per-step memory
     plan are undone when the step ends -- also when it raises -- so that a later grad-enabled decode outside a training
@@ -238,12 +238,25 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
     283,296,309): a scalar 0 / 0.0 switches it off -- no frozen-encoder forward, no guidance maps, `mc = NULL` in the three
     unlabelled cross entropies, `losses[5:8]` exactly 0, `aux['mclip']` / `aux['mclip_other']` None -- whether or not the
     model has a `clip_encoder`; a list or tuple (also [0, 0]) or a missing key keeps it on, and then a model built with
-    `clip_encoder=None` is refused with a ValueError before the step touches anything."""
+    `clip_encoder=None` is refused with a ValueError before the step touches anything.
+
+    `teacher` (an ema.EmaTeacher over `model` and `optimizer`, or None: the step as it always was): the mean teacher.  With
+    teacher.labels the pseudo-labels of both weak views come from ONE gradient-free pass of teacher.model over
+    cat(img_w, img_w_other) -- on the step's second stream for every model, a conv_encoder or a BatchNorm head included:
+    the teacher reads its own running statistics, not the ones the train-mode forwards write.  The student's forwards are
+    launched exactly as without a teacher; its pred_w is simply no longer the source of labels.  forward_maskclip stays on
+    the student, whose encoder is frozen and shared.  After optimizer.step() the teacher's BatchNorm statistics follow
+    (teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count)), one launch); its weights are the optimizer's EMA
+    arena and need nothing.  With return_aux, mask_w / conf_w / mask_w_other are the teacher's, pred_w_other is the
+    teacher's logits for img_w_other, pred_w stays the student's and pred_w_teacher is added.  With teacher.labels False the
+    step only maintains the teacher."""
     with _step_scope(model):
-        return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux)
+        return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux,
+                                  teacher)
 
 
-def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, return_aux=False):
+def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, return_aux=False,
+                          teacher=None):
     """One iteration of the labelled-only baseline, third_party/unimatch/supervised.py:268-301 (method 'supervised').
     `batch`: dict with `img_x` [B, 3, S, S] fp32 and `mask_x` [B, S, S] int64 on the GPU (data.LabeledLoader,
     synthetic_batch).  model.train(), ONE forward on img_x, criterion from supervised_criterion(cfg) (cross entropy with
@@ -257,9 +270,10 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
     Returns the device tensor `loss` [1]; with `return_aux` also dict(pred_x [B, N, S, S], dlogits, mask_x_ohem (None
     without OHEM), upsample_in_loss; `grad_stats` too when the optimizer clips the gradient norm).  Per-step overrides taken from `cfg` (`wgrad_stream`, `overlap_streams`,
     `head_remat`, `head_chunk_class_images`, `act_mem_fraction`) are set up for one decode of B samples and undone when
-    the step ends -- also when it raises -- as in semivl_train_step."""
+    the step ends -- also when it raises -- as in semivl_train_step.  `teacher` (ema.EmaTeacher or None): there are no
+    pseudo-labels here, the step only maintains it -- teacher.update_buffers after optimizer.step()."""
     with _step_scope(model, ("remat", "chunk_class_images", "act_limit_bytes")):
-        return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux)
+        return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux, teacher)
 
 
 def _head_res(model, img, cfg, lsw=False):
@@ -275,7 +289,7 @@ def _head_res(model, img, cfg, lsw=False):
     return None
 
 
-def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux):
+def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux, teacher=None):
     ohem = supervised_criterion(cfg)                     # supervised.py:222-231 (raises on what the kernels cannot do)
     img_x, mask_x = batch["img_x"], batch["mask_x"]
     B, dev = img_x.shape[0], img_x.device
@@ -341,6 +355,8 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
     if optimizer is not None:
         optimizer.step()                                 # :287
         optimizer.poly_lr(iters, total_iters)            # :294-300: lr * (1 - iters / total_iters) ** 0.9, nothing else
+        if teacher is not None:
+            teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count))
     if return_aux:
         pred_x = pred.detach()
         if up is not None:
@@ -352,7 +368,7 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
 
 
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                       return_aux=False):
+                       return_aux=False, teacher=None):
     """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
     returned `losses` is a device float[8] (LOSS_NAMES order).  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs)
@@ -421,7 +437,10 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     main = torch.cuda.current_stream(dev) if img_x.is_cuda else None
     # (the same holds for a decode head with BatchNorm -- the DeepLabV3+ head: `has_batchnorm`)
     head_bn = bool(getattr(getattr(model, "decode_head", None), "has_batchnorm", False))
-    pl_side = side if (getattr(model, "conv_encoder", None) is None and not head_bn) else None
+    # (a mean teacher that supplies the labels reads its OWN running statistics: its pass goes to the second stream for
+    # every model)
+    use_t = teacher is not None and teacher.labels
+    pl_side = side if (use_t or (getattr(model, "conv_encoder", None) is None and not head_bn)) else None
     if not guided and pl_side is None:
         side = None         # nothing would run there: no fork, no join
     # The logits stay at the head's resolution (round 5): the bilinear resize to the crop (vlg_head.py:247, builder.py:93-97)
@@ -451,15 +470,26 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     model.eval()
     if side is not None:
         side.wait_stream(main)
+    img_ww = pred_t = None
     with torch.no_grad(), (torch.cuda.stream(pl_side) if pl_side is not None else contextlib.nullcontext()):
-        pred_w_other = model(b["img_w_other"], **fwd_kw)
-        conf_w_other, mask_w_other = smax(pred_w_other)
-        if not return_aux:
-            del pred_w_other
+        if use_t:       # ONE pass of the averaged weights over both weak views: [w, w_other]
+            img_ww = _cat2(img_w, b["img_w_other"])
+            pred_t = teacher.model(img_ww, **fwd_kw)
+            conf_t, mask_t = smax(pred_t)
+            conf_w, mask_w, conf_w_other, mask_w_other = conf_t[:B], mask_t[:B], conf_t[B:], mask_t[B:]
+            if not return_aux:
+                del pred_t
+        else:
+            pred_w_other = model(b["img_w_other"], **fwd_kw)
+            conf_w_other, mask_w_other = smax(pred_w_other)
+            if not return_aux:
+                del pred_w_other
     mclip_all = mclip = mclip_other = None
     if guided:
         with torch.no_grad(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            mclip_all = model.forward_maskclip(_cat2(img_w, b["img_w_other"]), cfg.get("mcc_conf_thresh", 0.9),
+            if img_ww is None or side is not pl_side:
+                img_ww = _cat2(img_w, b["img_w_other"])
+            mclip_all = model.forward_maskclip(img_ww, cfg.get("mcc_conf_thresh", 0.9),
                                                ignore_mask=_cat2i(ign, ign_o))
             mclip, mclip_other = mclip_all[:B], mclip_all[B:]
     model.train()          # semivl.py:246: unconditionally back to train mode
@@ -518,10 +548,12 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     preds_s = model(_cat2(img_s1, img_s2), **fwd_kw)                                       # [s1, s2]
     pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:3 * B]
     pred_s1, pred_s2 = preds_s[:B], preds_s[B:]
-    conf_w, mask_w = smax(pred_w.detach())
+    if not use_t:
+        conf_w, mask_w = smax(pred_w.detach())
     if side is not None:        # join: the label maps of the side stream are consumed from here on
         main.wait_stream(side)
-        for t_ in ((conf_w_other, mask_w_other) if pl_side is not None else ()) + ((mclip_all,) if guided else ()):
+        side_maps = ((conf_t, mask_t) if use_t else (conf_w_other, mask_w_other)) if pl_side is not None else ()
+        for t_ in side_maps + ((mclip_all,) if guided else ()):
             t_.record_stream(main)
     # CutMix labels
     mw1, mw2 = cutmix_mask(mask_w, mask_w_other, mix1), cutmix_mask(mask_w, mask_w_other, mix2)
@@ -601,11 +633,17 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         optimizer.step()
         optimizer.poly_lr(iters, cfg.get("scheduler_max_iters", total_iters), warmup_iters=cfg.get("warmup_iters", 0),
                           warmup_ratio=cfg.get("warmup_ratio", 1e-6))
+        if teacher is not None:
+            teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count))
     if return_aux:
         aux = dict(mask_w=mask_w, mask_w_other=mask_w_other, mclip=mclip, mclip_other=mclip_other, conf_w=conf_w,
                    pred_x=full_res(pred_x.detach()), pred_s1=full_res(pred_s1.detach()), pred_w=full_res(pred_w.detach()),
-                   pred_w_other=full_res(pred_w_other), dl4=dl4, dls=dls, upsample_in_loss=up is not None,
-                   mask_x_ohem=mask_x_ohem)
+                   pred_w_other=full_res(pred_t[B:] if use_t else pred_w_other), dl4=dl4, dls=dls,
+                   upsample_in_loss=up is not None, mask_x_ohem=mask_x_ohem)
+        if use_t:
+            aux["pred_w_teacher"] = full_res(pred_t[:B])
+            if pl_side is not None:
+                pred_t.record_stream(main)
         return losses, _with_grad_stats(aux, optimizer)
     return losses
 
