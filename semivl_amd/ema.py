@@ -151,7 +151,7 @@ class EmaTeacher:
         self._copy_nbt()
 
     def _copy_nbt(self):
-        # int64 counters: copied as pairs of fp32 words with the fp32 copy kernel (train._cat2i does the same for label maps)
+        # int64 counters: copied as pairs of fp32 words with the fp32 copy kernel (train._cat2 does the same for label maps)
         ops.eltwise(4, self._nbt_s.view(torch.float32).view(-1), None, out=self._nbt_t.view(torch.float32).view(-1))
 
     def _copy_buffers(self):

@@ -1,10 +1,12 @@
-"""The SemiVL training step on MI355X: loss helpers, the two-branch step and the gradient all-reduce; the fused optimizers
-live in optim.py and are re-exported here.
+"""The SemiVL training steps on MI355X: the reference-named loss helpers, the step's streams, what both steps share (CELoss
+setup, stream override, head resolution, the head's memory plan, CE dispatch, the backward + update tail), the labelled-only
+step, the semi-supervised step as a sequence of phases and the gradient all-reduce; the optimizers are re-exported from optim.py.
 
 Mirrors (same names / argument meaning):
   utils/train_utils.py:19-49   cutmix_img_, cutmix_mask, confidence_weighted_loss
   semivl.py:52-58              compute_mc_loss
   semivl.py:223-345            the loop body  -> semivl_train_step()
+  supervised.py:268-301        the labelled-only loop body -> supervised_train_step()
   semivl.py:118-125,330-345    the optimizers + poly LR -> optim.py (FusedAdamW, FusedSGD)
   semivl.py:139-140            DistributedDataParallel -> GradAllReducer (RCCL all-reduce of the flat grad arena)
 """
@@ -13,6 +15,7 @@ import contextlib
 import numbers
 import os
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -154,16 +157,14 @@ def _celoss_weight_on(model, weight, dev):
     return cache[key].get()
 
 
-def _cat2(a, b):
-    """torch.cat((a, b)) along dim 0 with the library's copy kernel."""
-    out = ops.empty(a.shape[0] + b.shape[0], *a.shape[1:], device=a.device)
-    flat = out.view(-1)
-    ops.eltwise(4, a.contiguous().view(-1), None, out=flat[:a.numel()])
-    ops.eltwise(4, b.contiguous().view(-1), None, out=flat[a.numel():])
-    return out
-
-
+# ------------------------------------------------------------------------------------------------ the step's streams
 _SIDE = {}     # device -> second stream for the gradient-free passes of the step
+
+
+def _side_stream(dev):      # created by whoever asks first, create_step_streams or a step
+    if dev not in _SIDE:
+        _SIDE[dev] = torch.cuda.Stream(dev)
+    return _SIDE[dev]
 
 
 def create_step_streams(dev):
@@ -176,10 +177,7 @@ def create_step_streams(dev):
     if dev.type != "cuda":
         return []
     from . import lib as L
-    out = [torch.cuda.current_stream(dev)]
-    if dev not in _SIDE:
-        _SIDE[dev] = torch.cuda.Stream(dev)
-    out.append(_SIDE[dev])
+    out = [torch.cuda.current_stream(dev), _side_stream(dev)]
     if ops.WGRAD_STREAM:
         out.append(ops._wg_stream(dev))
     with torch.cuda.device(dev):
@@ -202,11 +200,21 @@ def step_helper_streams(streams):
             out.append(torch.cuda.ExternalStream(h_.value, device=s_.device))
     return out
 
+
+# ------------------------------------------------------------------------------------------------ the two public steps
 LOSS_NAMES = ("loss", "loss_x", "loss_s1", "loss_s2", "loss_fp", "loss_mc_s1", "loss_mc_s2", "loss_mc_fp")
+
+# The decode head's attributes a step overrides from cfg and _step_scope puts back when the step ends.  The two steps differ
+# in ONE attribute: `act_limit_bytes` (set by _plan_head in both) is restored after the supervised step and stays on the head
+# after the semivl step, where a later grad-enabled decode reads it.  Inherited behaviour, recorded here and kept exactly:
+# the semivl step always left it (every such decode then works under the limit of the last step's `act_mem_fraction`), the
+# supervised step was written with the restore.  Making them alike changes what such a decode does and is not done here.
+_HEAD_RESTORE_SEMIVL = ("remat", "chunk_class_images")
+_HEAD_RESTORE_SUPERVISED = _HEAD_RESTORE_SEMIVL + ("act_limit_bytes",)
 
 
 @contextlib.contextmanager
-def _step_scope(model, head_attrs=("remat", "chunk_class_images")):
+def _step_scope(model, head_attrs):
     """The per-step overrides of a training step (ops.WGRAD_STREAM, the decode head's `head_attrs` and its per-step memory
     plan) are undone when the block ends -- also when it raises."""
     head = getattr(model, "decode_head", None)
@@ -250,7 +258,7 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
     arena and need nothing.  With return_aux, mask_w / conf_w / mask_w_other are the teacher's, pred_w_other is the
     teacher's logits for img_w_other, pred_w stays the student's and pred_w_teacher is added.  With teacher.labels False the
     step only maintains the teacher."""
-    with _step_scope(model):
+    with _step_scope(model, _HEAD_RESTORE_SEMIVL):
         return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux,
                                   teacher)
 
@@ -272,8 +280,25 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
     `head_remat`, `head_chunk_class_images`, `act_mem_fraction`) are set up for one decode of B samples and undone when
     the step ends -- also when it raises -- as in semivl_train_step.  `teacher` (ema.EmaTeacher or None): there are no
     pseudo-labels here, the step only maintains it -- teacher.update_buffers after optimizer.step()."""
-    with _step_scope(model, ("remat", "chunk_class_images", "act_limit_bytes")):
+    with _step_scope(model, _HEAD_RESTORE_SUPERVISED):
         return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux, teacher)
+
+
+# ------------------------------------------------------------------------------------------------ what both steps do
+def _celoss_setup(model, eps_weight, dev):
+    """celoss_kwargs' (label_smoothing, weight) -> (weight on `dev` or None, the labelled CE launch's kwargs: {} = plain path)."""
+    eps, cw = eps_weight
+    cw = _celoss_weight_on(model, cw, dev)
+    return cw, (dict(label_smoothing=eps, class_weight=cw) if (eps != 0.0 or cw is not None) else {})
+
+
+# The weight-gradient stream is a process-wide switch (ops.WGRAD_STREAM: environment, multi_rank_defaults() or the caller);
+# a step only overrides it when its cfg says so explicitly (_step_scope puts it back)
+def _stream_override(cfg):
+    if "wgrad_stream" in cfg:
+        ops.WGRAD_STREAM = bool(cfg["wgrad_stream"])
+    elif not cfg.get("overlap_streams", True):
+        ops.WGRAD_STREAM = False
 
 
 def _head_res(model, img, cfg, lsw=False):
@@ -289,30 +314,82 @@ def _head_res(model, img, cfg, lsw=False):
     return None
 
 
+# The grad-carrying decodes of a step keep `live_samples` samples' activations until backward: the head decides ONCE per step
+# whether they fit or are re-materialised (model/vlg_head.py::_remat_decision) -- activations are kept while the allocation
+# stays under cfg's `act_mem_fraction` of the device, the others are recomputed in backward.
+def _plan_head(head, cfg, live_samples, bwd_ranges, img):
+    """The decode head's per-step memory plan.  `bwd_ranges`: {decoded batch: [(first, last) samples with a gradient]} or None."""
+    if head is None:
+        return
+    head._bwd_ranges = bwd_ranges
+    head._live_class_images = live_samples * head.num_classes
+    head._remat_step = {}
+    if "head_remat" in cfg:
+        head.remat = cfg["head_remat"]
+    if cfg.get("head_chunk_class_images"):
+        head.chunk_class_images = int(cfg["head_chunk_class_images"])
+    frac = cfg.get("act_mem_fraction", 0.70)
+    head.act_limit_bytes = (None if frac is None or not img.is_cuda else
+                            int(frac * torch.cuda.get_device_properties(img.device).total_memory))
+
+
+def _cat2(a, b):
+    """torch.cat((a, b)) along dim 0 with the library's copy kernel; int64 maps are copied as pairs of fp32 words."""
+    out = ops.empty(a.shape[0] + b.shape[0], *a.shape[1:], dtype=a.dtype, device=a.device)
+    fa, fb, fo = (t_.view(torch.float32).view(-1) for t_ in (a.contiguous(), b.contiguous(), out))
+    ops.eltwise(4, fa, None, out=fo[:fa.numel()])
+    ops.eltwise(4, fb, None, out=fo[fa.numel():])
+    return out
+
+
+def _smax(pred, up):
+    return ops.softmax_max_up(pred, *up) if up is not None else ops.softmax_max(pred)
+
+
+def _ce(up, pred, *a_, **kw):       # the fused cross entropy on logits at the head's resolution (`up`) or on resized ones
+    if up is not None:
+        return ops.ce_up_fused(pred, up[0], up[1], up[2], *a_, **kw)
+    return ops.ce_fused(pred, *a_, **kw)
+
+
+def _full_res(pred, up):    # (return_aux only) the resized logits the fused kernels never write
+    if up is None:
+        return pred
+    pred = pred.contiguous()
+    return ops.bilinear_planes_fwd(pred, pred.shape[2], pred.shape[3], up[2], up[0], up[1])
+
+
+def _backward_and_update(outputs, grads, optimizer, reducer, teacher, iters, max_iters, **warmup):
+    """The tail of both steps: backward, all-reduce, optimizer.step, poly_lr(iters, max_iters, **warmup), teacher statistics."""
+    if optimizer is not None:
+        optimizer.zero_grad()
+    torch.autograd.backward(outputs, grads)
+    if reducer is not None:
+        reducer.finish()    # folds autograd-delivered grads, flushes / waits for the overlapped all-reduce buckets
+    if optimizer is not None:
+        optimizer.step()
+        optimizer.poly_lr(iters, max_iters, **warmup)
+        if teacher is not None:
+            teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count))
+
+
+def _with_grad_stats(aux, optimizer):
+    """aux['grad_stats'] = the optimizer's device tensor {norm, coef, scale, non-finite flag} when it clips the gradient
+    norm (ArenaOptimizer.grad_clip); without clipping aux keeps exactly its keys."""
+    if getattr(optimizer, "grad_clip", None) is not None:
+        aux["grad_stats"] = optimizer.grad_stats
+    return aux
+
+
+# ------------------------------------------------------------------------------------------------ the labelled-only step
 def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux, teacher=None):
     ohem = supervised_criterion(cfg)                     # supervised.py:222-231 (raises on what the kernels cannot do)
     img_x, mask_x = batch["img_x"], batch["mask_x"]
     B, dev = img_x.shape[0], img_x.device
-    # CELoss kwargs (supervised.py:230-231): label_smoothing / weight reach the cross-entropy kernels; (0.0, None) is the plain path
-    eps, cw = celoss_kwargs(cfg, getattr(model, "num_classes", None))
-    cw = _celoss_weight_on(model, cw, dev)
-    ce_kw = dict(label_smoothing=eps, class_weight=cw) if (eps != 0.0 or cw is not None) else {}
-    if "wgrad_stream" in cfg:
-        ops.WGRAD_STREAM = bool(cfg["wgrad_stream"])
-    elif not cfg.get("overlap_streams", True):
-        ops.WGRAD_STREAM = False
-    head = getattr(model, "decode_head", None)
-    if head is not None:    # one grad-carrying decode of B samples, every sample live
-        head._bwd_ranges = None
-        head._live_class_images = B * head.num_classes
-        head._remat_step = {}
-        if "head_remat" in cfg:
-            head.remat = cfg["head_remat"]
-        if cfg.get("head_chunk_class_images"):
-            head.chunk_class_images = int(cfg["head_chunk_class_images"])
-        frac = cfg.get("act_mem_fraction", 0.70)
-        head.act_limit_bytes = (None if frac is None or not img_x.is_cuda else
-                                int(frac * torch.cuda.get_device_properties(dev).total_memory))
+    # CELoss kwargs (supervised.py:230-231): label_smoothing / weight reach the cross-entropy kernels; {} is the plain path
+    cw, ce_kw = _celoss_setup(model, celoss_kwargs(cfg, getattr(model, "num_classes", None)), dev)
+    _stream_override(cfg)
+    _plan_head(getattr(model, "decode_head", None), cfg, B, None, img_x)   # one grad-carrying decode, every sample live
     # (the cross-entropy kernels index the label map by the logits' geometry: a map of another shape is refused here)
     if mask_x.dtype != torch.int64 or tuple(mask_x.shape) != (B,) + tuple(img_x.shape[2:]):
         raise ValueError(f"supervised_train_step: mask_x {tuple(mask_x.shape)} {mask_x.dtype} does not match img_x "
@@ -339,41 +416,78 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
     # (with CELoss kwargs: {numerator, 0, 0, D}, the same quotient.)
     # The other three branches do not exist here: their rows are zero and their slots of `out` are never read.
     sums = ops.zeros(4, 4, dtype=torch.float64, device=dev)
-    if up is not None:
-        ops.ce_up_fused(pred.detach(), up[0], up[1], up[2], mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0],
-                        **ce_kw)
-    else:
-        ops.ce_fused(pred.detach(), mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0], **ce_kw)
+    _ce(up, pred.detach(), mask_x, True, dlogits=dlogits, gscale=gscale, sums_out=sums[0], **ce_kw)
     out = ops.empty(8, device=dev)
     ops.semivl_loss(sums, float(mask_x.numel()), 0.0, out)
     loss = out[1:2]
-    if optimizer is not None:
-        optimizer.zero_grad()                            # :285
-    torch.autograd.backward([pred], [dlogits])           # :286
-    if reducer is not None:
-        reducer.finish()
-    if optimizer is not None:
-        optimizer.step()                                 # :287
-        optimizer.poly_lr(iters, total_iters)            # :294-300: lr * (1 - iters / total_iters) ** 0.9, nothing else
-        if teacher is not None:
-            teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count))
+    # supervised.py:285-287, then :294-300: lr * (1 - iters / total_iters) ** 0.9, nothing else
+    _backward_and_update([pred], [dlogits], optimizer, reducer, teacher, iters, total_iters)
     if return_aux:
-        pred_x = pred.detach()
-        if up is not None:
-            pred_x = pred_x.contiguous()
-            pred_x = ops.bilinear_planes_fwd(pred_x, pred_x.shape[2], pred_x.shape[3], up[2], up[0], up[1])
-        aux = dict(pred_x=pred_x, dlogits=dlogits, mask_x_ohem=mask_x_ohem, upsample_in_loss=up is not None)
+        aux = dict(pred_x=_full_res(pred.detach(), up), dlogits=dlogits, mask_x_ohem=mask_x_ohem,
+                   upsample_in_loss=up is not None)
         return loss, _with_grad_stats(aux, optimizer)
     return loss
 
 
+# ------------------------------------------------------------------------------------------------ the semivl step
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
                        return_aux=False, teacher=None):
     """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
     returned `losses` is a device float[8] (LOSS_NAMES order).  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs)
     change the labelled launch only: `losses[1]` is torch's smoothed / weighted loss_x and enters `losses[0]` as before.
+    The phases below pass tensors as arguments and results; `s` holds the step's decisions (no tensors).
     """
+    # 1. everything that can refuse the cfg comes first: nothing has been touched when it raises
+    s = _semivl_cfg(cfg, iters, total_iters, getattr(model, "num_classes", None),
+                    getattr(model, "clip_encoder", None) is not None)
+    b, img_x = batch, batch["img_x"]
+    cw_x, ce_kw_x = _celoss_setup(model, s.celoss, img_x.device)
+    # CutMix images (in place, like the reference)
+    cutmix_img_(b["img_s1"], b["img_s1_other"], b["mix1"])
+    cutmix_img_(b["img_s2"], b["img_s2_other"], b["mix2"])
+    head = getattr(model, "decode_head", None)
+    if head is not None:
+        head._bwd_ranges = None
+    if reducer is not None:
+        reducer.begin()
+    _stream_override(cfg)
+    s.B, s.return_aux, s.use_t = img_x.shape[0], return_aux, teacher is not None and teacher.labels
+    # (a decode head with BatchNorm -- the DeepLabV3+ head: `has_batchnorm`)
+    s.head_bn = bool(getattr(head, "has_batchnorm", False))
+    # The logits stay at the head's resolution (round 5): the bilinear resize to the crop (vlg_head.py:247, builder.py:93-97)
+    # is evaluated inside the softmax-max / cross-entropy kernels and the gradient comes back at the head's resolution --
+    # the [B, N, H, W] tensors and the two resize passes do not exist.  `up` = (H, W, align_corners) or None (the resized
+    # tensors as before).  (The labelled launch's label-smoothing / class-weight variant has its own geometry query: where it
+    # refuses, the whole step runs on the resized tensors.)
+    s.up = _head_res(model, img_x, cfg, lsw=bool(ce_kw_x))
+    s.fwd_kw = dict(head_res=True) if s.up is not None else {}
+    lab = _label_pass(model, teacher, b, cfg, s)                                             # 2. (forks to the second stream)
+    preds4, preds_s = _student_forwards(model, b, cfg, fp_masks, s)                          # 3.
+    _join_labels(lab, preds4[:s.B], s)                                                       # 4. (joins it)
+    mix = _cutmix_labels(lab, b, s.guided)                                                   # 5.
+    # 6. / 7.: normalisers -> per-branch gradient scales, then the four fused cross entropies and the loss vector
+    norm = _normalisers(preds4[s.B:2 * s.B], b["mask_x"], lab, b["ignore_mask"], mix, cw_x, cfg, s)
+    losses, dl4, dls = _branch_losses(preds4, preds_s, lab, b["ignore_mask"], mix, norm, ce_kw_x, cfg, s)
+    if cfg.get("step_barrier", False) and dist.is_initialized() and dist.get_world_size() > 1:
+        # semivl.py:325: the reference synchronises all ranks before every backward.  It orders nothing the gradient
+        # all-reduce does not order already (SURVEY §2.2), so it is off by default; the flag restores the reference's
+        # lock-step pacing (useful when per-rank logging / timing is compared against the reference's).
+        dist.barrier()
+    try:    # 8. backward (+ all-reduce) + optimizer
+        _backward_and_update([preds4, preds_s], [dl4, dls], optimizer, reducer, teacher, iters,
+                             cfg.get("scheduler_max_iters", total_iters), warmup_iters=cfg.get("warmup_iters", 0),
+                             warmup_ratio=cfg.get("warmup_ratio", 1e-6))
+    finally:
+        if head is not None:
+            head._bwd_ranges = None
+    if return_aux:      # 9.
+        return losses, _with_grad_stats(_semivl_aux(lab, preds4, preds_s, dl4, dls, norm.mask_x_ohem, s), optimizer)
+    return losses
+
+
+def _semivl_cfg(cfg, iters, total_iters, num_classes, has_clip_encoder):
+    """Phase 1, host code only, all that can refuse the cfg: conf_mode, mcc_reduce, ohem, celoss, lam (at `iters`), guided."""
     conf_mode = cfg.get("conf_mode", "pixelwise")
     mcc_reduce = cfg.get("mcc_loss_reduce", "mean_all")
     if conf_mode not in ("pixelwise", "pixelavg", "pixelratio"):
@@ -382,11 +496,7 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
         raise ValueError(mcc_reduce)                     # semivl.py:161-162
     ohem = supervised_criterion(cfg)                     # semivl.py:142-149 (raises on what the kernels cannot do)
     # CELoss kwargs (semivl.py:142-143): label_smoothing / weight change the labelled launch only; (0.0, None) is the plain path
-    eps_x, cw_x = celoss_kwargs(cfg, getattr(model, "num_classes", None))
-    cw_x = _celoss_weight_on(model, cw_x, batch["img_x"].device)
-    ce_kw_x = dict(label_smoothing=eps_x, class_weight=cw_x) if (eps_x != 0.0 or cw_x is not None) else {}
-    pixelavg = conf_mode == "pixelavg"
-    whole_map = conf_mode in ("pixelavg", "pixelratio")  # both weight the WHOLE CE map, not the confident valid pixels
+    celoss = celoss_kwargs(cfg, num_classes)
     lam_cfg = cfg.get("maskclip_consistency_lambda", [0.1, 0])
     if isinstance(lam_cfg, (list, tuple)):
         prog = iters / total_iters
@@ -399,271 +509,200 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     guided = lam_cfg != 0
     if not guided:
         lam = 0.0
-    elif getattr(model, "clip_encoder", None) is None:
+    elif not has_clip_encoder:
         raise ValueError(f"semivl_train_step: maskclip_consistency_lambda={lam_cfg!r} asks for the MaskCLIP guidance but the "
                          f"model was built with clip_encoder=None; set maskclip_consistency_lambda=0 (experiment 41's rows) "
                          f"or build the model with a clip_encoder")
-    b = batch
-    img_x, mask_x = b["img_x"], b["mask_x"]
-    img_w, img_s1, img_s2 = b["img_w"], b["img_s1"], b["img_s2"]
-    ign, mix1, mix2 = b["ignore_mask"], b["mix1"], b["mix2"]
-    ign_o = b["ignore_mask_other"]
-    B = img_x.shape[0]
-    dev = img_x.device
-    # CutMix images (in place, like the reference)
-    cutmix_img_(img_s1, b["img_s1_other"], mix1)
-    cutmix_img_(img_s2, b["img_s2_other"], mix2)
-    if getattr(model, "decode_head", None) is not None:
-        model.decode_head._bwd_ranges = None
-    if reducer is not None:
-        reducer.begin()
-    # the weight-gradient stream is a process-wide switch (ops.WGRAD_STREAM: environment, multi_rank_defaults() or the
-    # caller); the step only overrides it when its cfg says so explicitly
-    if "wgrad_stream" in cfg:
-        ops.WGRAD_STREAM = bool(cfg["wgrad_stream"])
-    elif not cfg.get("overlap_streams", True):
-        ops.WGRAD_STREAM = False
+    return SimpleNamespace(conf_mode=conf_mode, mcc_reduce=mcc_reduce, ohem=ohem, celoss=celoss, lam=lam, guided=guided)
+
+
+def _label_pass(model, teacher, b, cfg, s):
+    """Phase 2, gradient-free: pseudo-labels of img_w_other (student) or of both weak views (teacher) and the guidance maps.
+    Sets s.main / s.side / s.pl_side: the caller's stream, the guidance's and the pseudo-label pass's (None = the caller's)."""
+    B, dev, on_gpu = s.B, b["img_x"].device, b["img_x"].is_cuda
     # pseudo labels + MaskCLIP guidance (model.eval(): the side encoder's BatchNorm uses its running statistics here,
     # semivl.py:228-244; nothing else on the path depends on the mode).  Both passes are gradient-free and independent of
     # the two student forwards below: they are enqueued on a second stream (event-forked from / joined back into the
     # caller's stream), so their kernels fill the partial last rounds of the student's grids instead of queueing behind
     # them.  With a conv_encoder only the frozen-CLIP guidance moves over: the pseudo-label pass reads, in eval mode, the
     # BatchNorm running statistics that the train-mode forwards update, so it stays in program order on the main stream.
-    side = None
-    if img_x.is_cuda and cfg.get("overlap_streams", True) and not os.environ.get("SVL_NO_SIDE_STREAM"):
-        side = _SIDE.get(dev)
-        if side is None:
-            side = _SIDE[dev] = torch.cuda.Stream(dev)
-    main = torch.cuda.current_stream(dev) if img_x.is_cuda else None
-    # (the same holds for a decode head with BatchNorm -- the DeepLabV3+ head: `has_batchnorm`)
-    head_bn = bool(getattr(getattr(model, "decode_head", None), "has_batchnorm", False))
+    # (the same holds for a decode head with BatchNorm: s.head_bn)
+    side = (_side_stream(dev) if on_gpu and cfg.get("overlap_streams", True) and not os.environ.get("SVL_NO_SIDE_STREAM")
+            else None)
+    s.main = torch.cuda.current_stream(dev) if on_gpu else None
     # (a mean teacher that supplies the labels reads its OWN running statistics: its pass goes to the second stream for
     # every model)
-    use_t = teacher is not None and teacher.labels
-    pl_side = side if (use_t or (getattr(model, "conv_encoder", None) is None and not head_bn)) else None
-    if not guided and pl_side is None:
+    pl_side = side if (s.use_t or (getattr(model, "conv_encoder", None) is None and not s.head_bn)) else None
+    if not s.guided and pl_side is None:
         side = None         # nothing would run there: no fork, no join
-    # The logits stay at the head's resolution (round 5): the bilinear resize to the crop (vlg_head.py:247, builder.py:93-97)
-    # is evaluated inside the softmax-max / cross-entropy kernels and the gradient comes back at the head's resolution --
-    # the [B, N, H, W] tensors and the two resize passes do not exist.  `up` = (H, W, align_corners) or None (models without
-    # the option, geometries the kernels do not take, cfg / SVL_NO_UP_LOSS: the resized tensors as before).
-    up = None
-    if img_x.is_cuda and cfg.get("fuse_upsample_loss", ops.UP_LOSS) and hasattr(model, "head_res_size"):
-        hs = model.head_res_size(tuple(img_x.shape[2:]))
-        geom = (B, model.num_classes, hs[0], hs[1], img_x.shape[2], img_x.shape[3], model.align_corners) if hs else None
-        # (the labelled launch's label-smoothing / class-weight variant has its own geometry query: where it refuses, the
-        # whole step runs on the resized tensors)
-        if hs is not None and ops.ce_up_ok(*geom) and (not ce_kw_x or ops.ce_up_lsw_ok(*geom)):
-            up = (int(img_x.shape[2]), int(img_x.shape[3]), bool(model.align_corners))
-    fwd_kw = dict(head_res=True) if up is not None else {}
-
-    def smax(pred):
-        return ops.softmax_max_up(pred, *up) if up is not None else ops.softmax_max(pred)
-
-    def full_res(pred):
-        """(return_aux only) the resized logits the fused kernels never write"""
-        if up is None:
-            return pred
-        pred = pred.contiguous()
-        return ops.bilinear_planes_fwd(pred, pred.shape[2], pred.shape[3], up[2], up[0], up[1])
-
+    s.side, s.pl_side = side, pl_side
+    lab = SimpleNamespace(mclip_all=None, mclip=None, mclip_other=None)
     model.eval()
     if side is not None:
-        side.wait_stream(main)
-    img_ww = pred_t = None
-    with torch.no_grad(), (torch.cuda.stream(pl_side) if pl_side is not None else contextlib.nullcontext()):
-        if use_t:       # ONE pass of the averaged weights over both weak views: [w, w_other]
-            img_ww = _cat2(img_w, b["img_w_other"])
-            pred_t = teacher.model(img_ww, **fwd_kw)
-            conf_t, mask_t = smax(pred_t)
-            conf_w, mask_w, conf_w_other, mask_w_other = conf_t[:B], mask_t[:B], conf_t[B:], mask_t[B:]
-            if not return_aux:
-                del pred_t
+        side.wait_stream(s.main)
+    img_ww = None
+    # (torch.cuda.stream(None) changes nothing: the pass stays on the caller's stream.  lab.pred: the pass's logits, kept for
+    # aux only; lab.side_maps: what _join_labels hands over to the main stream)
+    with torch.no_grad(), torch.cuda.stream(pl_side):
+        if s.use_t:     # ONE pass of the averaged weights over both weak views: [w, w_other]
+            img_ww = _cat2(b["img_w"], b["img_w_other"])
+            lab.pred = teacher.model(img_ww, **s.fwd_kw)
+            conf_t, mask_t = lab.side_maps = tuple(_smax(lab.pred, s.up))
+            lab.conf_w, lab.mask_w, lab.conf_w_other, lab.mask_w_other = conf_t[:B], mask_t[:B], conf_t[B:], mask_t[B:]
         else:
-            pred_w_other = model(b["img_w_other"], **fwd_kw)
-            conf_w_other, mask_w_other = smax(pred_w_other)
-            if not return_aux:
-                del pred_w_other
-    mclip_all = mclip = mclip_other = None
-    if guided:
-        with torch.no_grad(), (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            if img_ww is None or side is not pl_side:
-                img_ww = _cat2(img_w, b["img_w_other"])
-            mclip_all = model.forward_maskclip(img_ww, cfg.get("mcc_conf_thresh", 0.9),
-                                               ignore_mask=_cat2i(ign, ign_o))
-            mclip, mclip_other = mclip_all[:B], mclip_all[B:]
+            lab.pred = model(b["img_w_other"], **s.fwd_kw)
+            lab.conf_w_other, lab.mask_w_other = lab.side_maps = tuple(_smax(lab.pred, s.up))
+        if not s.return_aux:
+            lab.pred = None
+    if s.guided:
+        with torch.no_grad(), torch.cuda.stream(side):
+            if img_ww is None or side is not pl_side:    # (reused only when both passes share a stream)
+                img_ww = _cat2(b["img_w"], b["img_w_other"])
+            lab.mclip_all = model.forward_maskclip(img_ww, cfg.get("mcc_conf_thresh", 0.9),
+                                                   ignore_mask=_cat2(b["ignore_mask"], b["ignore_mask_other"]))
+            lab.mclip, lab.mclip_other = lab.mclip_all[:B], lab.mclip_all[B:]
     model.train()          # semivl.py:246: unconditionally back to train mode
-    # predictions
+    return lab
+
+
+def _wx(m_, B):     # rows in the reference's [x, w] order -> the step's [w, x]
+    return torch.cat((m_[B:2 * B], m_[:B]))
+
+
+@contextlib.contextmanager
+def _hooks_wx(backbone, B):
+    """Injected prompt-dropout / stochastic-depth masks of the backbone come in the reference's [x, w] row order too: inside
+    the block both hooks hand them over as [w, x]; the hooks are put back when it ends, also when the forward raises."""
+    keep = {n_: getattr(backbone, n_) for n_ in ("prompt_mask_hook", "drop_path_hook") if getattr(backbone, n_, None) is not None}
+    for n_, h_ in keep.items():
+        def swapped(*a_, hook=h_):
+            m_ = hook(*a_)
+            return None if m_ is None else _wx(m_, B)
+        setattr(backbone, n_, swapped)
+    try:
+        yield
+    finally:
+        for n_, h_ in keep.items():
+            setattr(backbone, n_, h_)
+
+
+def _student_forwards(model, b, cfg, fp_masks, s):
+    """Phase 3: the grad-carrying forwards -> preds4 over [w, x, w_fp] (BatchNorm head: + x_fp), preds_s over [s1, s2]."""
+    B = s.B
     # the feature-perturbed copy of the labeled half (pred_x_fp) is never read by the step (semivl.py:247): only the
     # unlabeled half is perturbed and decoded.  The batch is ordered [w, x] (the reference: [x, w]; every op is
     # per-sample or a permutation-invariant batch statistic) so that the decoded batch is [w, x, w_fp]: the two
     # gradient-carrying thirds are CONTIGUOUS and the head's backward runs once on 2B samples (full grid rounds)
     # instead of twice on B.
     if fp_masks is not None:   # injected masks come in the reference's [x, w] row order
-        fp_masks = [torch.cat((m_[B:2 * B], m_[:B])) for m_ in fp_masks]
+        fp_masks = [_wx(m_, B) for m_ in fp_masks]
     # pred_w is detached (semivl.py:251) -> exactly-zero dlogits: the head decodes those samples without keeping
-    # activations and its backward skips them (results identical).  Memory plan: activations of the remaining chunks are
-    # kept while the allocation stays under `act_mem_fraction` of the device, the others are recomputed in backward.
-    head = getattr(model, "decode_head", None)
-    if head is not None:
-        head._bwd_ranges = {3 * B: [(B, 3 * B)]}
-        # both grad-carrying decodes of the step ([x, w_fp] here, [s1, s2] below) keep activations until backward: the
-        # head decides ONCE per step whether they fit or are re-materialised (model/vlg_head.py::_remat_decision)
-        head._live_class_images = 4 * B * head.num_classes
-        head._remat_step = {}
-        if "head_remat" in cfg:
-            head.remat = cfg["head_remat"]
-        if cfg.get("head_chunk_class_images"):
-            head.chunk_class_images = int(cfg["head_chunk_class_images"])
-        frac = cfg.get("act_mem_fraction", 0.70)
-        head.act_limit_bytes = (None if frac is None or not img_x.is_cuda else
-                                int(frac * torch.cuda.get_device_properties(dev).total_memory))
+    # activations and its backward skips them (results identical).  Both grad-carrying decodes of the step ([x, w_fp] here,
+    # [s1, s2] below) keep activations until backward: 4 B live samples.
+    _plan_head(getattr(model, "decode_head", None), cfg, 4 * B, {3 * B: [(B, 3 * B)]}, b["img_x"])
     # A head with BatchNorm decodes all 4 B samples, [w, x, w_fp, x_fp]: with batch statistics x_fp enters every mean and
     # variance of the reference's need_fp forward (cat((f, dropout2d(f))) over [x, w], builder.py:78-89), so it cannot be
     # left out; its dlogits are zero like pred_w's, and backward runs on the whole batch (the statistics terms carry
     # gradient into those rows).
-    fp_kw = {} if head_bn else dict(fp_range=(0, B))
-    # (injected prompt-dropout masks of the backbone come in the reference's [x, w] row order too)
-    bb = getattr(model, "backbone", None)
-    phook = getattr(bb, "prompt_mask_hook", None)
-    if phook is not None:
-        def _wx(layer, n, hook=phook):
-            m_ = hook(layer, n)
-            return None if m_ is None else torch.cat((m_[B:2 * B], m_[:B]))
-        bb.prompt_mask_hook = _wx
-    # (and so do injected stochastic-depth masks, one value per sample)
-    dhook = getattr(bb, "drop_path_hook", None)
-    if dhook is not None:
-        def _wx_dp(layer, site, n, hook=dhook):
-            m_ = hook(layer, site, n)
-            return None if m_ is None else torch.cat((m_[B:2 * B], m_[:B]))
-        bb.drop_path_hook = _wx_dp
-    try:
-        preds4 = model(_cat2(img_w, img_x), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **fwd_kw)
-    finally:
-        if phook is not None:
-            bb.prompt_mask_hook = phook
-        if dhook is not None:
-            bb.drop_path_hook = dhook
-    preds_s = model(_cat2(img_s1, img_s2), **fwd_kw)                                       # [s1, s2]
-    pred_w, pred_x, pred_w_fp = preds4[:B], preds4[B:2 * B], preds4[2 * B:3 * B]
-    pred_s1, pred_s2 = preds_s[:B], preds_s[B:]
-    if not use_t:
-        conf_w, mask_w = smax(pred_w.detach())
-    if side is not None:        # join: the label maps of the side stream are consumed from here on
-        main.wait_stream(side)
-        side_maps = ((conf_t, mask_t) if use_t else (conf_w_other, mask_w_other)) if pl_side is not None else ()
-        for t_ in side_maps + ((mclip_all,) if guided else ()):
-            t_.record_stream(main)
-    # CutMix labels
-    mw1, mw2 = cutmix_mask(mask_w, mask_w_other, mix1), cutmix_mask(mask_w, mask_w_other, mix2)
-    cw1, cw2 = cutmix_mask(conf_w, conf_w_other, mix1), cutmix_mask(conf_w, conf_w_other, mix2)
-    ig1, ig2 = cutmix_mask(ign, ign_o, mix1), cutmix_mask(ign, ign_o, mix2)
-    mc1 = mc2 = None        # (not guided: the cross-entropy kernels take mc == NULL, their guidance sums stay 0)
-    if guided:
-        mc1, mc2 = cutmix_mask(mclip, mclip_other, mix1), cutmix_mask(mclip, mclip_other, mix2)
-    # normalisers -> per-branch gradient scales, on the device
+    fp_kw = {} if s.head_bn else dict(fp_range=(0, B))
+    with _hooks_wx(getattr(model, "backbone", None), B):
+        preds4 = model(_cat2(b["img_w"], b["img_x"]), need_fp=True, fp_masks=fp_masks, split_fp=False, **fp_kw, **s.fwd_kw)
+    preds_s = model(_cat2(b["img_s1"], b["img_s2"]), **s.fwd_kw)                             # [s1, s2]
+    return preds4, preds_s
+
+
+def _join_labels(lab, pred_w, s):
+    """Phase 4: the student's own pseudo-labels; then the join: the second stream's label maps are consumed from here on."""
+    if not s.use_t:
+        lab.conf_w, lab.mask_w = _smax(pred_w.detach(), s.up)
+    if s.side is not None:
+        s.main.wait_stream(s.side)
+        for t_ in (lab.side_maps if s.pl_side is not None else ()) + ((lab.mclip_all,) if s.guided else ()):
+            t_.record_stream(s.main)
+
+
+def _cutmix_labels(lab, b, guided):
+    """Phase 5: CutMix of the label maps -> (mask, conf, ignore, guidance) pairs for the branches (s1, s2)."""
+    def both(t_, other):
+        return cutmix_mask(t_, other, b["mix1"]), cutmix_mask(t_, other, b["mix2"])
+    # (not guided: the cross-entropy kernels take mc == NULL, their guidance sums stay 0)
+    return SimpleNamespace(mw=both(lab.mask_w, lab.mask_w_other), cw=both(lab.conf_w, lab.conf_w_other),
+                           ig=both(b["ignore_mask"], b["ignore_mask_other"]),
+                           mc=both(lab.mclip, lab.mclip_other) if guided else (None, None))
+
+
+def _normalisers(pred_x, mask_x, lab, ign, mix, cw_x, cfg, s):
+    """Phase 6: the normalisers of the branches (x, s1, s2, fp) -> their gradient scales, on the device; mask_x as CE reads it."""
+    dev, ohem = ign.device, s.ohem
+    branches = ((mix.cw[0], mix.ig[0]), (mix.cw[1], mix.ig[1]), (lab.conf_w, ign))      # (conf, ignore) of s1, s2, fp
     counts = ops.zeros(4, dtype=torch.int64, device=dev)
     mask_x_ohem = None
     if ohem is not None:   # semivl.py:267 with criterion_l = OHEM: the plain CE on the relabelled map, its count as normaliser
-        mask_x = mask_x_ohem = ohem.relabel(pred_x, mask_x, up=up, counts_out=counts[0:1])
-    for i, m_ in enumerate((mask_x, ig1, ig2, ign)):
+        mask_x = mask_x_ohem = ohem.relabel(pred_x, mask_x, up=s.up, counts_out=counts[0:1])
+    for i, m_ in enumerate((mask_x, mix.ig[0], mix.ig[1], ign)):
         if i > 0 or ohem is None:
             ops.count_valid(m_, counts[i:i + 1])
     numel_u = float(ign.numel())
     gscale = ops.empty(4, 2, device=dev)
     factors = None
-    if pixelavg:  # train_utils.py:43-46: (sum of the WHOLE CE map) * sum_b mean_valid(conf_b) / #valid
+    if s.conf_mode == "pixelavg":  # train_utils.py:43-46: (sum of the WHOLE CE map) * sum_b mean_valid(conf_b) / #valid
         factors = ops.empty(3, dtype=torch.float64, device=dev)
-        for i, (c_, g_) in enumerate(((cw1, ig1), (cw2, ig2), (conf_w, ign))):
+        for i, (c_, g_) in enumerate(branches):
             ops.conf_avg_factor(c_, g_, factors[i:i + 1])
     ratios = (None, None, None)
-    if conf_mode == "pixelratio":   # train_utils.py:39-42: image b's CE map times its share of confident valid pixels
-        ratios = tuple(ops.conf_ratio(c_, g_, cfg["conf_thresh"]) for c_, g_ in ((cw1, ig1), (cw2, ig2), (conf_w, ign)))
+    if s.conf_mode == "pixelratio":   # train_utils.py:39-42: image b's CE map times its share of confident valid pixels
+        ratios = tuple(ops.conf_ratio(c_, g_, cfg["conf_thresh"]) for c_, g_ in branches)
     mc_counts = None                # semivl.py:52-58: the guidance loss's normaliser
-    if not guided:
+    if not s.guided:
         pass                        # no guidance term: no normaliser either ('mean' would count 0 labelled pixels -> 0 * x / 0)
-    elif mcc_reduce == "mean_valid":
+    elif s.mcc_reduce == "mean_valid":
         mc_counts = counts[1:]
-    elif mcc_reduce == "mean":      # nn.CrossEntropyLoss(ignore_index=255): mean over the labelled guidance pixels
+    elif s.mcc_reduce == "mean":    # nn.CrossEntropyLoss(ignore_index=255): mean over the labelled guidance pixels
         mc_counts = ops.zeros(3, dtype=torch.int64, device=dev)
-        for i, m_ in enumerate((mc1, mc2, mclip)):
+        for i, m_ in enumerate(mix.mc + (lab.mclip,)):
             ops.count_valid(m_, mc_counts[i:i + 1])
-    ops.semivl_gscale(counts, numel_u, lam, gscale, factors, mc_counts)
+    ops.semivl_gscale(counts, numel_u, s.lam, gscale, factors, mc_counts)
     if cw_x is not None:    # torch's weighted mean: g_t of the labelled branch is 0.5 / D, D = sum of w[target] (counts[0] stays)
         ops.scale_from_sum(ops.class_weight_sum(mask_x, cw_x, ops.empty(1, dtype=torch.float64, device=dev)), 0.5, gscale[0])
-    # fused CE forward + backward per branch
-    thr = cfg["conf_thresh"]
-    dl4 = torch.empty_like(preds4)
-    dls = torch.empty_like(preds_s)
+    return SimpleNamespace(mask_x=mask_x, mask_x_ohem=mask_x_ohem, numel_u=numel_u, gscale=gscale, factors=factors,
+                           ratios=ratios, mc_counts=mc_counts)
+
+
+def _branch_losses(preds4, preds_s, lab, ign, mix, norm, ce_kw_x, cfg, s):
+    """Phase 7: the four fused cross entropies and svl_semivl_loss -> (losses [8], dl4, dls = the gradients of preds4, preds_s)."""
+    B, up = s.B, s.up
+    dl4, dls = torch.empty_like(preds4), torch.empty_like(preds_s)
     ops.fill(dl4[:B], 0.0)  # pred_w is detached (semivl.py:251)
-    if head_bn:
+    if s.head_bn:
         ops.fill(dl4[3 * B:], 0.0)   # pred_x_fp is never read (semivl.py:247)
-    sums = ops.empty(4, 4, dtype=torch.float64, device=dev)
-    def ce(pred, *a_, **kw):
-        if up is not None:
-            return ops.ce_up_fused(pred, up[0], up[1], up[2], *a_, **kw)
-        return ops.ce_fused(pred, *a_, **kw)
-
-    ce(pred_x.detach(), mask_x, True, dlogits=dl4[B:2 * B], gscale=gscale[0], sums_out=sums[0], **ce_kw_x)
-    ce(pred_s1.detach(), mw1, False, conf=cw1, ign=ig1, conf_thresh=thr, mc=mc1, dlogits=dls[:B],
-       gscale=gscale[1], sums_out=sums[1], all_pixels=whole_map, img_weight=ratios[0])
-    ce(pred_s2.detach(), mw2, False, conf=cw2, ign=ig2, conf_thresh=thr, mc=mc2, dlogits=dls[B:],
-       gscale=gscale[2], sums_out=sums[2], all_pixels=whole_map, img_weight=ratios[1])
-    ce(pred_w_fp.detach(), mask_w, False, conf=conf_w, ign=ign, conf_thresh=thr, mc=mclip,
-       dlogits=dl4[2 * B:3 * B], gscale=gscale[3], sums_out=sums[3], all_pixels=whole_map, img_weight=ratios[2])
-    losses = ops.empty(8, device=dev)
-    ops.semivl_loss(sums, numel_u, lam, losses, factors, mc_counts)
-    # backward (+ all-reduce) + optimizer
-    if cfg.get("step_barrier", False) and dist.is_initialized() and dist.get_world_size() > 1:
-        # semivl.py:325: the reference synchronises all ranks before every backward.  It orders nothing the gradient
-        # all-reduce does not order already (SURVEY §2.2), so it is off by default; the flag restores the reference's
-        # lock-step pacing (useful when per-rank logging / timing is compared against the reference's).
-        dist.barrier()
-    if optimizer is not None:
-        optimizer.zero_grad()
-    try:
-        torch.autograd.backward([preds4, preds_s], [dl4, dls])
-    finally:
-        if head is not None:
-            head._bwd_ranges = None
-    if reducer is not None:
-        reducer.finish()    # folds autograd-delivered grads, flushes / waits for the overlapped all-reduce buckets
-    if optimizer is not None:
-        optimizer.step()
-        optimizer.poly_lr(iters, cfg.get("scheduler_max_iters", total_iters), warmup_iters=cfg.get("warmup_iters", 0),
-                          warmup_ratio=cfg.get("warmup_ratio", 1e-6))
-        if teacher is not None:
-            teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count))
-    if return_aux:
-        aux = dict(mask_w=mask_w, mask_w_other=mask_w_other, mclip=mclip, mclip_other=mclip_other, conf_w=conf_w,
-                   pred_x=full_res(pred_x.detach()), pred_s1=full_res(pred_s1.detach()), pred_w=full_res(pred_w.detach()),
-                   pred_w_other=full_res(pred_t[B:] if use_t else pred_w_other), dl4=dl4, dls=dls,
-                   upsample_in_loss=up is not None, mask_x_ohem=mask_x_ohem)
-        if use_t:
-            aux["pred_w_teacher"] = full_res(pred_t[:B])
-            if pl_side is not None:
-                pred_t.record_stream(main)
-        return losses, _with_grad_stats(aux, optimizer)
-    return losses
+    sums = ops.empty(4, 4, dtype=torch.float64, device=ign.device)
+    # pixelavg and pixelratio weight the WHOLE CE map, not the confident valid pixels
+    u_kw = dict(conf_thresh=cfg["conf_thresh"], all_pixels=s.conf_mode in ("pixelavg", "pixelratio"))
+    _ce(up, preds4[B:2 * B].detach(), norm.mask_x, True, dlogits=dl4[B:2 * B], gscale=norm.gscale[0], sums_out=sums[0],
+        **ce_kw_x)
+    for i in (0, 1):        # s1, s2
+        _ce(up, preds_s[i * B:(i + 1) * B].detach(), mix.mw[i], False, conf=mix.cw[i], ign=mix.ig[i], mc=mix.mc[i],
+            dlogits=dls[i * B:(i + 1) * B], gscale=norm.gscale[1 + i], sums_out=sums[1 + i], img_weight=norm.ratios[i], **u_kw)
+    _ce(up, preds4[2 * B:3 * B].detach(), lab.mask_w, False, conf=lab.conf_w, ign=ign, mc=lab.mclip,
+        dlogits=dl4[2 * B:3 * B], gscale=norm.gscale[3], sums_out=sums[3], img_weight=norm.ratios[2], **u_kw)
+    losses = ops.empty(8, device=ign.device)
+    ops.semivl_loss(sums, norm.numel_u, s.lam, losses, norm.factors, norm.mc_counts)
+    return losses, dl4, dls
 
 
-def _with_grad_stats(aux, optimizer):
-    """aux['grad_stats'] = the optimizer's device tensor {norm, coef, scale, non-finite flag} when it clips the gradient
-    norm (ArenaOptimizer.grad_clip); without clipping aux keeps exactly its keys."""
-    if getattr(optimizer, "grad_clip", None) is not None:
-        aux["grad_stats"] = optimizer.grad_stats
+def _semivl_aux(lab, preds4, preds_s, dl4, dls, mask_x_ohem, s):
+    """Phase 9 (return_aux): label maps, full-resolution logits and the loss gradients."""
+    B, up = s.B, s.up
+    aux = dict(mask_w=lab.mask_w, mask_w_other=lab.mask_w_other, mclip=lab.mclip, mclip_other=lab.mclip_other,
+               conf_w=lab.conf_w, pred_x=_full_res(preds4[B:2 * B].detach(), up), pred_s1=_full_res(preds_s[:B].detach(), up),
+               pred_w=_full_res(preds4[:B].detach(), up),
+               pred_w_other=_full_res(lab.pred[B:] if s.use_t else lab.pred, up), dl4=dl4, dls=dls,
+               upsample_in_loss=up is not None, mask_x_ohem=mask_x_ohem)
+    if s.use_t:
+        aux["pred_w_teacher"] = _full_res(lab.pred[:B], up)
+        if s.pl_side is not None:
+            lab.pred.record_stream(s.main)
     return aux
-
-
-def _cat2i(a, b):
-    out = ops.empty(a.shape[0] + b.shape[0], *a.shape[1:], dtype=torch.int64, device=a.device)
-    # int64 maps: copy as pairs of fp32 words with the fp32 copy kernel
-    fa, fb = a.contiguous().view(torch.float32), b.contiguous().view(torch.float32)
-    fo = out.view(torch.float32).view(-1)
-    ops.eltwise(4, fa.view(-1), None, out=fo[:fa.numel()])
-    ops.eltwise(4, fb.view(-1), None, out=fo[fa.numel():])
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ data parallel
@@ -703,7 +742,6 @@ class GradAllReducer:
         per = max(1, int(bucket_mb * 1024 * 1024 // 4))
         groups = getattr(optimizer, "groups", None)
         self._slot = {}          # id(param) -> bucket index
-        self._expected, self._done = {}, {}
         if groups:               # cut at parameter boundaries (arena order = model.named_parameters() order)
             offs = optimizer.seg_off.tolist()
             self.buckets, start, members = [], 0, []
@@ -773,11 +811,17 @@ class GradAllReducer:
                                    comm_stream="dedicated" if self._async else "none (blocking backend; probed a stand-in)")
         elif self._async and on_gpu:
             self._comm = torch.cuda.Stream(optimizer.g.device)
-        self._works, self._fired, self._complete = [], set(), [0] * len(self.buckets)
+        self._reset()
         self.early_fires = 0
         if self.world > 1 and groups:
             for g_ in groups:
                 g_["param"]._svl_reducer = self
+
+    def _reset(self):
+        """The per-step state: works in flight, buckets fired, complete parameters per bucket, contributions per parameter."""
+        self._works, self._fired = [], set()
+        self._complete = [0] * len(self.buckets)
+        self._expected, self._done = {}, {}
 
     # ---- region hooks (gradsync.expect / gradsync.ready) ---------------------------------------------------------
     def _expect(self, prm):
@@ -842,9 +886,7 @@ class GradAllReducer:
             # collectives of an aborted step may still be in flight on arena slices: the next zero_grad / gradient
             # writes on the compute stream must not overtake them
             torch.cuda.current_stream().wait_stream(self._comm)
-        self._works, self._fired = [], set()
-        self._complete = [0] * len(self.buckets)
-        self._expected, self._done = {}, {}
+        self._reset()
 
     def finish(self):
         """After backward: every gradient in the arena, every bucket reduced, compute stream ordered after them."""
@@ -868,9 +910,7 @@ class GradAllReducer:
             elif self.profile:
                 self.timing = dict(events=self._ev, join=None, early_fires=self.early_fires)
                 self._ev = []
-        self._works, self._fired = [], set()
-        self._complete = [0] * len(self.buckets)
-        self._expected, self._done = {}, {}
+        self._reset()
 
     reduce = finish
 

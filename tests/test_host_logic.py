@@ -176,6 +176,59 @@ def test_warmup_then_poly_lr():
     assert torch.allclose(o.seg_lr, torch.tensor([g["lr"] for g in o.groups]))
 
 
+def test_semivl_cfg_phase():
+    """The semivl step's first phase (train._semivl_cfg, host code only): the guidance switch is the reference's own test,
+    `cfg['maskclip_consistency_lambda'] != 0` (semivl.py:158); a list is interpolated by iters / total_iters."""
+    from semivl_amd.train import _semivl_cfg
+    for zero in (0, 0.0):                                        # a scalar 0 switches the guidance off, encoder or not
+        for enc in (True, False):
+            s = _semivl_cfg(dict(maskclip_consistency_lambda=zero), 3, 10, 21, enc)
+            assert s.guided is False and s.lam == 0.0 and isinstance(s.lam, float)
+    s = _semivl_cfg(dict(maskclip_consistency_lambda=[0, 0]), 3, 10, 21, True)
+    assert s.guided is True and s.lam == 0.0                     # a list keeps it on, whatever it holds
+    s = _semivl_cfg({}, 3, 10, 21, True)                             # missing key: today's default [0.1, 0]
+    assert s.guided is True and math.isclose(s.lam, 0.1 * 0.7)
+    assert (s.conf_mode, s.mcc_reduce) == ("pixelwise", "mean_all")
+    s = _semivl_cfg(dict(maskclip_consistency_lambda=(0.5, 0.1), conf_mode="pixelratio", mcc_loss_reduce="mean"), 25, 100, None, True)
+    assert s.guided is True and math.isclose(s.lam, 0.5 * 0.75 + 0.1 * 0.25)
+    assert (s.conf_mode, s.mcc_reduce) == ("pixelratio", "mean")
+    assert _semivl_cfg(dict(maskclip_consistency_lambda=0.25), 25, 100, None, True).lam == 0.25    # a scalar is taken as it is
+    with pytest.raises(ValueError, match="pixelmax"):
+        _semivl_cfg(dict(conf_mode="pixelmax"), 3, 10, 21, True)
+    with pytest.raises(ValueError, match="median"):
+        _semivl_cfg(dict(mcc_loss_reduce="median", maskclip_consistency_lambda=0), 3, 10, 21, True)
+    for lam in ([0, 0], 0.1, None):                              # guided on a model built with clip_encoder=None
+        cfg = {} if lam is None else dict(maskclip_consistency_lambda=lam)
+        with pytest.raises(ValueError, match="maskclip_consistency_lambda.*clip_encoder"):
+            _semivl_cfg(cfg, 3, 10, 21, False)
+
+
+def test_head_memory_plan():
+    """train._plan_head sets the decode head's per-step plan for both callers: the semivl step (4 B live samples, the ranges
+    of the [w, x, w_fp] decode that receive a gradient) and the supervised step (B live samples, every sample live)."""
+    from types import SimpleNamespace
+    from semivl_amd.train import _plan_head
+    B, N, img = 2, 21, torch.zeros(2, 3, 8, 8)
+
+    def head():
+        return SimpleNamespace(num_classes=N, remat="auto", chunk_class_images=1344, act_limit_bytes=123, _bwd_ranges="stale",
+                               _live_class_images="stale", _remat_step="stale")
+    h = head()
+    _plan_head(h, {}, 4 * B, {3 * B: [(B, 3 * B)]}, img)         # semivl, nothing in cfg
+    assert h._bwd_ranges == {6: [(2, 6)]} and h._live_class_images == 4 * B * N and h._remat_step == {}
+    assert h.remat == "auto" and h.chunk_class_images == 1344    # untouched without their cfg keys
+    assert h.act_limit_bytes is None                             # a CPU image: no device to take a fraction of
+    h = head()
+    _plan_head(h, dict(head_remat=True, head_chunk_class_images="84", act_mem_fraction=0.5), B, None, img)   # supervised
+    assert h._bwd_ranges is None and h._live_class_images == B * N and h._remat_step == {}
+    assert h.remat is True and h.chunk_class_images == 84 and h.act_limit_bytes is None
+    h = head()
+    _plan_head(h, dict(head_remat=None, head_chunk_class_images=0, act_mem_fraction=None), B, None, img)
+    assert h.remat is None and h.chunk_class_images == 1344      # head_remat is honoured as given; a false chunk size is not
+    assert h.act_limit_bytes is None                             # act_mem_fraction=None: no limit, on any device
+    _plan_head(None, {}, B, None, img)                           # a model without a decode head: nothing to plan
+
+
 def test_head_chunk_plan():
     """Sample chunks of the class-batched decoder (memory plan): live ranges announced by the step are kept apart from the
     dead samples, chunks never exceed the class-image budget, and the plan tiles the batch exactly."""
