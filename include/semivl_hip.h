@@ -487,6 +487,36 @@ int svl_concept_max_f32(const float* pred, int B, int NC, int64_t HW, const int*
 int svl_iou_hist_i64(const int64_t* pred, const int64_t* target, int64_t n, int K, int ignore_index, int64_t* hist,
                      svl_stream_t stream);
 
+/* Pseudo-label / guidance quality counts of the semi-supervised step (monitor.py): one pass over the n = B H W pixels of
+ *   mask_w int64 [n]  pseudo-label            conf float [n]  its confidence          ign int64 [n]  255 = padding
+ *   mc     int64 [n] or NULL  MaskCLIP guidance, 255 = none
+ *   gt     int64 [n] or NULL  held-back annotation; anything outside [0, N) = no annotation (255 void, 254 padding)
+ * adds (+=, the caller zeroes and accumulates over steps) into stats int64 [13 N + 2 bins + 1].  With
+ *   v = ign != 255;  k = v && conf >= thresh (fp32, as the cross-entropy kernels compare; NaN is not confident);
+ *   m = v && 0 <= mc < N;  g = v && 0 <= gt < N;  p = mask_w (outside [0, N): counts nowhere as a prediction)
+ * the rows, [N] each, count the pixels with
+ *    0 pl_area      v, p==c              7 plc_gt_area  k, g, gt==c
+ *    1 plc_area     k, p==c              8 plc_inter    k, g, gt==c, p==c
+ *    2 mc_area      m, mc==c             9 plc_area_gt  k, g, p==c
+ *    3 agree        m, mc==c, p==c      10 mc_gt_area   m, g, gt==c
+ *    4 gt_area      g, gt==c            11 mc_inter     m, g, gt==c, mc==c
+ *    5 pl_inter     g, gt==c, p==c      12 mc_area_gt   m, g, mc==c
+ *    6 pl_area_gt   g, p==c
+ * then conf_hist [bins] over v, conf_hist_correct [bins] over g && p==gt, and one slot that receives n.  The bin is
+ * min((int)(conf * (float)bins), bins - 1) in fp32; a conf that is not >= 0 goes to bin 0.  Rows (5, 6, 4), (8, 9, 7) and
+ * (11, 12, 10) are intersectionAndUnion(pred, target', N, 255)'s (intersection, prediction area, target area) with target' =
+ * gt where the row's condition holds and 255 elsewhere.  Rows of a NULL mc / gt get nothing added.  Integer counts: two
+ * runs agree bit for bit.  The int64 maps are read with 16-byte loads when all of them are 16-byte aligned and conf is
+ * 8-byte aligned, with scalar loads otherwise.  Refused (SVL_ERR_INVALID_ARG): null mask_w / conf / ign / stats, n < 1,
+ * N < 1, bins < 1, a table (13 N + 2 bins 32-bit counters) beyond 64 KB of LDS, n so large that one block of the capped
+ * grid would see 2^32 pixels. */
+int svl_pl_stats_i64(const int64_t* mask_w, const float* conf, const int64_t* ign, const int64_t* mc, const int64_t* gt,
+                     int64_t n, int N, int bins, float thresh, int64_t* stats, svl_stream_t stream);
+/* pixels one trip of svl_pl_stats_i64's capped grid covers on the 16-byte path (host only) */
+int64_t svl_pl_stats_pass_pixels(void);
+/* the meter's per-step bookkeeping: sum[i] += losses[i] for i < k (k <= 64), steps[0] += 1; one launch, stream-ordered */
+int svl_pl_add_losses(const float* losses, int k, double* sum, int64_t* steps, svl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Normalisation / elementwise / attention helpers (maskclip_vit.py:120-144, vlg_head.py:39-137).
  * ---------------------------------------------------------------------------------------------- */

@@ -140,22 +140,27 @@ def draw_color_jitter(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.25):
 
 class GpuAugmenter:
     """semi.py `SemiDataset` train modes on the device.  `size` = crop size, `scale_ratio_range` = cfg['scale_ratio_range']
-    (VOC (0.5, 2.0))."""
+    (VOC (0.5, 2.0)).  `unlabeled_gt`: the unlabelled samples' annotation, which the loader already resamples through the
+    image's geometry, is handed on too (the reference's `pleval`): `train_u` returns it as a seventh tensor and `batch()`
+    adds it as `mask_u` for the first unlabelled view -- what monitor.PseudoLabelMeter counts the pseudo-labels against."""
 
     def __init__(self, size, scale_ratio_range=(0.5, 2.0), device="cuda", img_scale=None,
-                 labeled_photometric_distortion=False):
+                 labeled_photometric_distortion=False, unlabeled_gt=False):
         if labeled_photometric_distortion:
             raise NotImplementedError("labeled_photometric_distortion (mmseg PhotoMetricDistortion, semi.py:90-93) is "
                                       "False in every shipped SemiVL recipe (experiments.py:73)")
         self.size, self.ratio, self.device = size, tuple(scale_ratio_range), torch.device(device)
         self.img_scale = tuple(img_scale) if img_scale is not None else None
         self._scratch = None
+        self.unlabeled_gt = bool(unlabeled_gt)
 
     @classmethod
     def from_cfg(cls, cfg, device="cuda"):
-        """The keys SemiDataset.__init__ reads (semi.py:17-28)."""
+        """The keys SemiDataset.__init__ reads (semi.py:17-28); cfg['pl_monitor']['gt'] switches `unlabeled_gt` on."""
+        from .monitor import pl_monitor_from_cfg
+        mon = pl_monitor_from_cfg(cfg)
         return cls(cfg["crop_size"], cfg.get("scale_ratio_range", (0.5, 2.0)), device, cfg.get("img_scale"),
-                   cfg.get("labeled_photometric_distortion", False))
+                   cfg.get("labeled_photometric_distortion", False), unlabeled_gt=bool(mon and mon["gt"]))
 
     def _geom(self, img, mask, ignore_value):
         H, W = img.shape[:2]
@@ -204,7 +209,8 @@ class GpuAugmenter:
         return to_float(im), mask_i64(mk)
 
     def train_u(self, img_u8, mask_u8=None):
-        """Unlabeled sample (semi.py:97-125): img_w, img_s1, img_s2, ignore_mask, cutmix_box1, cutmix_box2."""
+        """Unlabeled sample (semi.py:97-125): img_w, img_s1, img_s2, ignore_mask, cutmix_box1, cutmix_box2; with
+        `unlabeled_gt` also the resampled annotation as int64 (254 on the padding and 255 = void left as they are)."""
         img = img_u8.to(self.device)
         mask = mask_u8.to(self.device) if mask_u8 is not None else torch.zeros(img.shape[:2], dtype=torch.uint8,
                                                                               device=self.device)
@@ -212,7 +218,8 @@ class GpuAugmenter:
         s1, s2 = self._strong(im), self._strong(im)
         box1, box2 = self._box(), self._box()
         ign = mask_i64(torch.where(mk == 254, mk, torch.zeros_like(mk)), 254, 255)   # 255 on the padding, 0 elsewhere
-        return to_float(im), to_float(s1), to_float(s2), ign, box1, box2
+        out = (to_float(im), to_float(s1), to_float(s2), ign, box1, box2)
+        return out + (mask_i64(mk),) if self.unlabeled_gt else out
 
     def batch(self, labeled, unlabeled, unlabeled_other):
         """Lists of (img_u8 [H,W,3], mask_u8 [H,W]) -> the 12-tensor dict of one SemiVL step (semivl.py:205-221)."""
@@ -220,9 +227,12 @@ class GpuAugmenter:
         us = [self.train_u(i, m) for i, m in unlabeled]
         uo = [self.train_u(i, m) for i, m in unlabeled_other]
         st = lambda seq, k: torch.stack([s[k] for s in seq])
-        return dict(img_x=st(xs, 0), mask_x=st(xs, 1), img_w=st(us, 0), img_s1=st(us, 1), img_s2=st(us, 2),
-                    ignore_mask=st(us, 3), mix1=st(us, 4), mix2=st(us, 5), img_w_other=st(uo, 0),
-                    img_s1_other=st(uo, 1), img_s2_other=st(uo, 2), ignore_mask_other=st(uo, 3))
+        out = dict(img_x=st(xs, 0), mask_x=st(xs, 1), img_w=st(us, 0), img_s1=st(us, 1), img_s2=st(us, 2),
+                   ignore_mask=st(us, 3), mix1=st(us, 4), mix2=st(us, 5), img_w_other=st(uo, 0),
+                   img_s1_other=st(uo, 1), img_s2_other=st(uo, 2), ignore_mask_other=st(uo, 3))
+        if self.unlabeled_gt:
+            out["mask_u"] = st(us, 6)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ host side: decode + splits

@@ -133,6 +133,9 @@ SIGNATURES = {
     "svl_maskclip_labels": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     "svl_concept_max_f32": (_I, [_P, _I, _I, _L, _P, _I, _P, _P]),
     "svl_iou_hist_i64": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "svl_pl_stats_i64": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P]),
+    "svl_pl_stats_pass_pixels": (_L, []),
+    "svl_pl_add_losses": (_I, [_P, _I, _P, _P, _P]),
     "svl_layernorm_fwd": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P]),
     "svl_layernorm_fwd_planes": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P]),
     "svl_layernorm_fwd_planes_f16x2": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P, _P, _P]),

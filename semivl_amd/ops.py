@@ -1974,6 +1974,38 @@ def iou_hist(pred, target, K, ignore_index, hist):
             "svl_iou_hist_i64")
 
 
+def pl_stats_len(num_classes, bins):
+    """Length of pl_stats' table: 13 rows [num_classes], two histograms [bins], the pixel count."""
+    return 13 * int(num_classes) + 2 * int(bins) + 1
+
+
+def pl_stats(mask_w, conf, ign, stats, num_classes, bins, thresh, mc=None, gt=None):
+    """stats (int64 [13 N + 2 bins + 1], accumulated) += the pseudo-label / guidance quality counts of one batch
+    (svl_pl_stats_i64; layout in include/semivl_hip.h).  mask_w / ign / mc / gt int64, conf fp32, all of one shape and
+    contiguous; mc / gt None: their rows get nothing.  One launch on the current stream, no sync."""
+    n = mask_w.numel()
+    for name, t_, dt in (("mask_w", mask_w, torch.int64), ("conf", conf, torch.float32), ("ign", ign, torch.int64),
+                         ("mc", mc, torch.int64), ("gt", gt, torch.int64)):
+        if t_ is None:
+            continue
+        if not t_.is_cuda or t_.dtype != dt or t_.numel() != n or not t_.is_contiguous():
+            raise ValueError(f"pl_stats: {name} must be a contiguous {dt} GPU tensor of {n} elements, got "
+                             f"{tuple(t_.shape)} {t_.dtype} on {t_.device}")
+    if (not stats.is_cuda or stats.dtype != torch.int64 or not stats.is_contiguous()
+            or stats.numel() != pl_stats_len(num_classes, bins)):
+        raise ValueError(f"pl_stats: stats must be a contiguous int64 GPU tensor of {pl_stats_len(num_classes, bins)} "
+                         f"elements, got {tuple(stats.shape)} {stats.dtype}")
+    L.check(L.load().svl_pl_stats_i64(_p(mask_w), _p(conf), _p(ign), _p(mc), _p(gt), n, int(num_classes), int(bins),
+                                      float(thresh), _p(stats), _st()), "svl_pl_stats_i64")
+
+
+def pl_add_losses(losses, loss_sum, steps):
+    """loss_sum (float64 [k]) += losses (fp32 [k]); steps (int64 [1]) += 1: one launch, no sync."""
+    assert losses.dtype == torch.float32 and loss_sum.dtype == torch.float64 and steps.dtype == torch.int64
+    assert losses.numel() == loss_sum.numel() and losses.is_contiguous() and loss_sum.is_contiguous()
+    L.check(L.load().svl_pl_add_losses(_p(losses), losses.numel(), _p(loss_sum), _p(steps), _st()), "svl_pl_add_losses")
+
+
 def set_gemm_emulation(mode):
     """0: exact fp32 MFMA (default); 6 / 3: bf16 split emulation for the large dense GEMMs (include/semivl_hip.h)."""
     L.check(L.load().svl_set_gemm_emulation(int(mode)), "svl_set_gemm_emulation")

@@ -236,7 +236,7 @@ def _step_scope(model, head_attrs):
 
 
 def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                      return_aux=False, teacher=None):
+                      return_aux=False, teacher=None, monitor=None):
     """One iteration of semivl.py:223-328 (see _semivl_train_step for the body).  Per-step overrides taken from `cfg`
     (`wgrad_stream`, `overlap_streams`, `head_remat`, `head_chunk_class_images`) and the decode head's per-step memory
     plan are undone when the step ends -- also when it raises -- so that a later grad-enabled decode outside a training
@@ -257,10 +257,16 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
     (teacher.update_buffers(optimizer.ema_decay_at(optimizer.step_count)), one launch); its weights are the optimizer's EMA
     arena and need nothing.  With return_aux, mask_w / conf_w / mask_w_other are the teacher's, pred_w_other is the
     teacher's logits for img_w_other, pred_w stays the student's and pred_w_teacher is added.  With teacher.labels False the
-    step only maintains the teacher."""
+    step only maintains the teacher.
+
+    `monitor` (a monitor.PseudoLabelMeter, or None: the step launches exactly what it launches without one): the label maps
+    of the weak view the step trains on -- mask_w, conf_w, the guidance when the step is guided, the teacher's maps when it
+    supplies the labels -- are counted against batch['ignore_mask'] and, when the batch carries it, the held-back annotation
+    batch['mask_u'] (monitor.update, one launch on the main stream after the label join), and the step's loss vector is
+    added to the meter's sum (monitor.add_losses, one launch).  Neither reads anything back; `aux` gets no new key."""
     with _step_scope(model, _HEAD_RESTORE_SEMIVL):
         return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux,
-                                  teacher)
+                                  teacher, monitor)
 
 
 def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, return_aux=False,
@@ -431,7 +437,7 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
 
 # ------------------------------------------------------------------------------------------------ the semivl step
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                       return_aux=False, teacher=None):
+                       return_aux=False, teacher=None, monitor=None):
     """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
     returned `losses` is a device float[8] (LOSS_NAMES order).  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs)
@@ -465,10 +471,15 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     lab = _label_pass(model, teacher, b, cfg, s)                                             # 2. (forks to the second stream)
     preds4, preds_s = _student_forwards(model, b, cfg, fp_masks, s)                          # 3.
     _join_labels(lab, preds4[:s.B], s)                                                       # 4. (joins it)
+    if monitor is not None:     # the maps the step trains on, counted on the main stream; nothing is read back
+        monitor.update(lab.mask_w, lab.conf_w, b["ignore_mask"], cfg["conf_thresh"],
+                       mclip=lab.mclip if s.guided else None, mask_u=b.get("mask_u"))
     mix = _cutmix_labels(lab, b, s.guided)                                                   # 5.
     # 6. / 7.: normalisers -> per-branch gradient scales, then the four fused cross entropies and the loss vector
     norm = _normalisers(preds4[s.B:2 * s.B], b["mask_x"], lab, b["ignore_mask"], mix, cw_x, cfg, s)
     losses, dl4, dls = _branch_losses(preds4, preds_s, lab, b["ignore_mask"], mix, norm, ce_kw_x, cfg, s)
+    if monitor is not None:
+        monitor.add_losses(losses)
     if cfg.get("step_barrier", False) and dist.is_initialized() and dist.get_world_size() > 1:
         # semivl.py:325: the reference synchronises all ranks before every backward.  It orders nothing the gradient
         # all-reduce does not order already, so it is off by default; the flag restores the reference's
