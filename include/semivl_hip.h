@@ -517,6 +517,30 @@ int64_t svl_pl_stats_pass_pixels(void);
 /* the meter's per-step bookkeeping: sum[i] += losses[i] for i < k (k <= 64), steps[0] += 1; one launch, stream-ordered */
 int svl_pl_add_losses(const float* losses, int k, double* sum, int64_t* steps, svl_stream_t stream);
 
+/* Confusion table of the evaluation report (report.py): one pass over the n pixels of pred / target (int64) adds (+=, the
+ * caller zeroes and accumulates over batches) into table int64 [(K+1) x (K+1)], rows = annotation, columns = prediction.
+ * A pixel with target == ignore_index is counted nowhere; any other pixel adds 1 at table[r][c] with
+ *   r = target if 0 <= target < K else K        (254, -1: targets that are neither a class nor ignored)
+ *   c = pred   if 0 <= pred   < K else K
+ * -- both keys are formed before anything is indexed with them.  The table is a superset of svl_iou_hist_i64's rows:
+ *   intersection[k] = table[k][k];  prediction area[k] = sum_{r=0..K} table[r][k];  target area[k] = sum_{c=0..K} table[k][c].
+ * Integer counts: two runs agree bit for bit.  K <= svl_confusion_lds_max_classes(): block-private 32-bit counters in LDS
+ * ((K+1)^2 x 4 bytes; above 64 KB one block per CU), flushed with 64-bit atomics before they could wrap; above it the waves'
+ * aggregated counts go straight into 64-bit global atomics.  The maps are read with 16-byte loads when both are 16-byte
+ * aligned, with scalar loads otherwise.  Refused (SVL_ERR_INVALID_ARG, table untouched): null pointers, n <= 0, K < 1,
+ * K > 1024, 0 <= ignore_index < K (the reference's intersectionAndUnion counts an ignored class as a hit there; not
+ * reproduced). */
+int svl_confusion_i64(const int64_t* pred, const int64_t* target, int64_t n, int K, int ignore_index, int64_t* table,
+                      svl_stream_t stream);
+/* the largest K whose table svl_confusion_i64 keeps in LDS (host only) */
+int svl_confusion_lds_max_classes(void);
+/* measurement aid (tools/time_confusion.py): moves that boundary process-wide; K < 0 restores the built-in value, K above
+ * 201 ((K+1)^2 x 4 bytes beyond the 160 KB of LDS) is refused.  Results do not depend on it. */
+int svl_set_confusion_lds_max_classes(int K);
+/* out[i] = (uint8_t)label[i] (numpy's astype(np.uint8): the low byte) for the palette PNG export: 16-byte loads and 8-byte
+ * stores when label is 16-byte and out 8-byte aligned, one by one otherwise and on the n % 8 tail.  Refused: null, n <= 0. */
+int svl_label_u8_i64(const int64_t* label, int64_t n, uint8_t* out, svl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Normalisation / elementwise / attention helpers (maskclip_vit.py:120-144, vlg_head.py:39-137).
  * ---------------------------------------------------------------------------------------------- */

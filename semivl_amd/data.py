@@ -352,6 +352,33 @@ class StepLoader(_PrefetchLoader):
         return self.aug.batch(lab, unl, unl)
 
 
+class ValLoader(_PrefetchLoader):
+    """The validation loader of third_party/unimatch/eval.py:125-128 (batch_size=1, drop_last=False) for `evaluate` /
+    `report.evaluate_report`: yields (img float [1, 3, h, w], mask int64 [1, H, W], id) on the GPU, id = '<img> <lbl>' as
+    the split file lists it.  Built from SemiDataset(cfg, 'val') -- the split file is cfg['val_id_path'] when given, else
+    the reference's splits/<dataset>/val.txt -- and GpuAugmenter.val, with decoding ahead in `workers` host threads.
+    Sharded as ids[rank::world] WITHOUT padding: the reference's DistributedSampler pads by wrap-around to a multiple of
+    the world size and so counts a few images twice; here every image is counted exactly once (ranks may differ by one
+    image, the single all-reduce of the counts does not mind)."""
+
+    def __init__(self, cfg, aug, rank=0, world=1, workers=2, prefetch=2):
+        self.set = SemiDataset(cfg, "val", id_path=cfg.get("val_id_path"))
+        self.aug, self.order = aug, list(range(len(self.set)))[rank::world]
+        self.ids = [self.set.ids[i] for i in self.order]
+        self.steps, self.workers, self.prefetch = len(self.order), workers, prefetch
+
+    def _decode(self, k):
+        return self.set[self.order[k]][:2]
+
+    def _augment(self, host):
+        img, mask = self.aug.val(*host)
+        return dict(img=img[None], mask=mask[None])
+
+    def __iter__(self):
+        for id_, b in zip(self.ids, super().__iter__()):
+            yield b["img"], b["mask"], id_
+
+
 class LabeledLoader(_PrefetchLoader):
     """One epoch of the supervised baseline's loader (third_party/unimatch/supervised.py:239-244) as ready
     `dict(img_x, mask_x)` batches on the GPU for `train.supervised_train_step`: the labelled set as its split file lists

@@ -136,6 +136,10 @@ SIGNATURES = {
     "svl_pl_stats_i64": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P]),
     "svl_pl_stats_pass_pixels": (_L, []),
     "svl_pl_add_losses": (_I, [_P, _I, _P, _P, _P]),
+    "svl_confusion_i64": (_I, [_P, _P, _L, _I, _I, _P, _P]),
+    "svl_confusion_lds_max_classes": (_I, []),
+    "svl_set_confusion_lds_max_classes": (_I, [_I]),
+    "svl_label_u8_i64": (_I, [_P, _L, _P, _P]),
     "svl_layernorm_fwd": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P]),
     "svl_layernorm_fwd_planes": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P]),
     "svl_layernorm_fwd_planes_f16x2": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P, _P, _P]),

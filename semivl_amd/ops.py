@@ -2006,6 +2006,45 @@ def pl_add_losses(losses, loss_sum, steps):
     L.check(L.load().svl_pl_add_losses(_p(losses), losses.numel(), _p(loss_sum), _p(steps), _st()), "svl_pl_add_losses")
 
 
+def confusion_len(K):
+    """Length of confusion's table: (K + 1) x (K + 1), the extra row / column for labels outside [0, K)."""
+    return (int(K) + 1) ** 2
+
+
+def confusion(pred, target, K, ignore_index, table):
+    """table (int64 [(K+1)^2], accumulated) += the confusion counts of one batch (svl_confusion_i64; rows = annotation,
+    columns = prediction, layout in include/semivl_hip.h).  pred / target int64, of one size and contiguous.  One launch on
+    the current stream, no sync."""
+    n = pred.numel()
+    for name, t_ in (("pred", pred), ("target", target)):
+        if not t_.is_cuda or t_.dtype != torch.int64 or t_.numel() != n or not t_.is_contiguous():
+            raise ValueError(f"confusion: {name} must be a contiguous {torch.int64} GPU tensor of {n} elements, got "
+                             f"{tuple(t_.shape)} {t_.dtype} on {t_.device}")
+    if (not table.is_cuda or table.dtype != torch.int64 or not table.is_contiguous()
+            or table.numel() != confusion_len(K)):
+        raise ValueError(f"confusion: table must be a contiguous int64 GPU tensor of {confusion_len(K)} elements, got "
+                         f"{tuple(table.shape)} {table.dtype} on {table.device}")
+    L.check(L.load().svl_confusion_i64(_p(pred), _p(target), n, int(K), int(ignore_index), _p(table), _st()),
+            "svl_confusion_i64")
+
+
+def label_u8(label, out=None):
+    """uint8 tensor of label's shape with out[i] = (uint8)label[i] (svl_label_u8_i64; numpy's astype(np.uint8)): the
+    exported map crosses PCIe at 1 byte per pixel.  label: contiguous int64 GPU tensor; `out`: a contiguous uint8 GPU tensor
+    of as many elements to write instead of a fresh one."""
+    if not label.is_cuda or label.dtype != torch.int64 or not label.is_contiguous() or label.numel() == 0:
+        raise ValueError(f"label_u8: label must be a non-empty contiguous {torch.int64} GPU tensor, got "
+                         f"{tuple(label.shape)} {label.dtype} on {label.device}")
+    if out is None:
+        out = torch.empty(label.shape, dtype=torch.uint8, device=label.device)
+    elif (not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != label.numel()
+          or out.device != label.device):
+        raise ValueError(f"label_u8: out must be a contiguous uint8 GPU tensor of {label.numel()} elements on "
+                         f"{label.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
+    L.check(L.load().svl_label_u8_i64(_p(label), label.numel(), _p(out), _st()), "svl_label_u8_i64")
+    return out
+
+
 def set_gemm_emulation(mode):
     """0: exact fp32 MFMA (default); 6 / 3: bf16 split emulation for the large dense GEMMs (include/semivl_hip.h)."""
     L.check(L.load().svl_set_gemm_emulation(int(mode)), "svl_set_gemm_emulation")
