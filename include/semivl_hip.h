@@ -541,6 +541,26 @@ int svl_set_confusion_lds_max_classes(int K);
  * stores when label is 16-byte and out 8-byte aligned, one by one otherwise and on the n % 8 tail.  Refused: null, n <= 0. */
 int svl_label_u8_i64(const int64_t* label, int64_t n, uint8_t* out, svl_stream_t stream);
 
+/* Debug panels of the training driver (panel.py; the figure of semivl.py:371-406 / utils/plot_utils.py): RGB tiles written
+ * into a u8 canvas.  `dst` points at the tile's first byte for sample 0; pixel (b, y, x), channel c lands at
+ * dst[b * batch_stride + y * row_stride + 3 x + c] (strides in bytes; dst may have any byte alignment).  Nothing outside the
+ * B tiles of H x W x 3 bytes is written.  Both read their input once, 4 consecutive pixels of a sample per thread with
+ * 16-byte loads, and store the 12 bytes as three 4-byte words where the address is 4-byte aligned and the 4 pixels share a
+ * row, byte by byte otherwise; capped grid, grid-strided, no atomics: reruns agree bit for bit.
+ * Refused by both (SVL_ERR_INVALID_ARG, nothing written): null pointers, B / H / W < 1, B H W >= 2^31 - 3,
+ * row_stride < 3 W, B > 1 and batch_stride < (H - 1) row_stride + 3 W (tiles would overlap).
+ *
+ * svl_panel_image_u8: img fp32 [B][3][H][W] (4-byte aligned), normalised with mean3 / std3 (HOST pointers, 3 floats each):
+ *   v = img * std3[c] + mean3[c]   -- two separately rounded fp32 operations, torch's .mul(std).add(mean), no contraction
+ *   v = clamp(v, 0, 1), NaN -> 0;   byte = (uint8_t)(v * 255.0f + 0.5f)   -- again separately rounded
+ * svl_panel_label_u8: label int64 [B][H][W] (8-byte aligned); palette: DEVICE u8 [K][3], 1 <= K <= 256 (refused otherwise):
+ *   pixel = palette[l] for 0 <= l < K, (255, 255, 255) otherwise (-1, K, 254, 255, 2^40: plot_utils.py's colorize_label);
+ *   the key is checked before anything is indexed with it. */
+int svl_panel_image_u8(const float* img, int B, int H, int W, const float* mean3, const float* std3, uint8_t* dst,
+                       int64_t batch_stride, int64_t row_stride, svl_stream_t stream);
+int svl_panel_label_u8(const int64_t* label, int B, int H, int W, const uint8_t* palette, int K, uint8_t* dst,
+                       int64_t batch_stride, int64_t row_stride, svl_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Normalisation / elementwise / attention helpers (maskclip_vit.py:120-144, vlg_head.py:39-137).
  * ---------------------------------------------------------------------------------------------- */

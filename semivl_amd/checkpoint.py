@@ -77,14 +77,23 @@ def convert_clip_visual(clip_state_dict, backbone=True):
     return res
 
 
-def save_checkpoint(path, model, optimizer, epoch, ddp_prefix=True, ema_model=None):
-    """semivl.py:426-433.  The reference saves the DDP-wrapped model, hence the `module.` prefix on every key."""
+def save_checkpoint(path, model, optimizer, epoch, ddp_prefix=True, ema_model=None, extra=None):
+    """semivl.py:426-433.  The reference saves the DDP-wrapped model, hence the `module.` prefix on every key.  `extra`: a
+    dict merged into the file beside the reference's keys (the trainer's `previous_best`, `seed`, `total_iters`); it may not
+    replace one of them.  None: the file is what it always was."""
     pre = "module." if ddp_prefix else ""
     ck = {"model": {pre + k: v.detach().cpu() for k, v in model.state_dict().items()},
           "optimizer": optimizer.state_dict() if optimizer is not None else None,
           "epoch": epoch}
     if ema_model is not None:
         ck["ema_model"] = {pre + k: v.detach().cpu() for k, v in ema_model.state_dict().items()}
+    if extra is not None:
+        if not isinstance(extra, dict):
+            raise ValueError(f"save_checkpoint: extra must be a dict, got {type(extra).__name__}")
+        for k in extra:
+            if k in ("model", "optimizer", "epoch", "ema_model"):
+                raise ValueError(f"save_checkpoint: extra may not replace the key {k!r}")
+        ck.update(extra)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(ck, path)
     return ck

@@ -140,6 +140,8 @@ SIGNATURES = {
     "svl_confusion_lds_max_classes": (_I, []),
     "svl_set_confusion_lds_max_classes": (_I, [_I]),
     "svl_label_u8_i64": (_I, [_P, _L, _P, _P]),
+    "svl_panel_image_u8": (_I, [_P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _L, _L, _P]),
+    "svl_panel_label_u8": (_I, [_P, _I, _I, _I, _P, _I, _P, _L, _L, _P]),
     "svl_layernorm_fwd": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P]),
     "svl_layernorm_fwd_planes": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P]),
     "svl_layernorm_fwd_planes_f16x2": (_I, [_P, _P, _P, _F, _L, _I, _P, _P, _P, _L, _P, _P, _P]),

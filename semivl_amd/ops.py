@@ -7,6 +7,7 @@ import collections
 import ctypes as C
 import os
 import math
+import numbers
 import weakref
 
 import torch
@@ -2043,6 +2044,57 @@ def label_u8(label, out=None):
                          f"{label.device}, got {tuple(out.shape)} {out.dtype} on {out.device}")
     L.check(L.load().svl_label_u8_i64(_p(label), label.numel(), _p(out), _st()), "svl_label_u8_i64")
     return out
+
+
+def _panel_tile(name, src, dtype, lead, canvas, y0, x0):
+    """The checks both panel kernels share -> (B, H, W, pointer to the tile's first byte, batch stride, row stride)."""
+    if (not src.is_cuda or src.dtype != dtype or src.dim() != lead + 3 or not src.is_contiguous() or src.numel() == 0
+            or (lead and src.shape[1] != 3)):
+        want = "[B, 3, H, W]" if lead else "[B, H, W]"
+        raise ValueError(f"{name}: the input must be a non-empty contiguous {dtype} GPU tensor {want}, got "
+                         f"{tuple(src.shape)} {src.dtype} on {src.device}")
+    Bn, H, W = src.shape[0], src.shape[-2], src.shape[-1]
+    if (not canvas.is_cuda or canvas.dtype != torch.uint8 or canvas.dim() != 4 or canvas.shape[3] != 3
+            or canvas.stride(3) != 1 or canvas.stride(2) != 3 or canvas.device != src.device):
+        raise ValueError(f"{name}: canvas must be a uint8 GPU tensor [B, rows, cols, 3] with packed pixels on {src.device}, "
+                         f"got {tuple(canvas.shape)} {canvas.dtype} strides {tuple(canvas.stride())} on {canvas.device}")
+    if canvas.shape[0] != Bn:
+        raise ValueError(f"{name}: canvas holds {canvas.shape[0]} samples, the input {Bn}")
+    for what, v in (("y0", y0), ("x0", x0)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError(f"{name}: {what} must be an int, got {v!r}")
+    if not (0 <= y0 and y0 + H <= canvas.shape[1] and 0 <= x0 and x0 + W <= canvas.shape[2]):
+        raise ValueError(f"{name}: tile {H} x {W} at origin ({y0}, {x0}) does not lie inside the canvas "
+                         f"{canvas.shape[1]} x {canvas.shape[2]}")
+    bs, rs = int(canvas.stride(0)), int(canvas.stride(1))
+    return Bn, H, W, C.c_void_p(canvas.data_ptr() + int(y0) * rs + int(x0) * 3), bs, rs
+
+
+def panel_image(img, mean, std, canvas, y0, x0):
+    """canvas[b, y0 + y, x0 + x, c] = (uint8)(clamp(img[b, c, y, x] * std[c] + mean[c], 0, 1) * 255 + 0.5), NaN -> 0
+    (svl_panel_image_u8; every operation rounded on its own).  img: contiguous fp32 GPU [B, 3, H, W]; mean / std: 3 numbers
+    each; canvas: uint8 GPU [B, rows, cols, 3] with packed pixels, any row / batch stride and byte alignment.  One launch on
+    the current stream, no sync; nothing outside the tile is written."""
+    Bn, H, W, dst, bs, rs = _panel_tile("panel_image", img, torch.float32, 1, canvas, y0, x0)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(f"panel_image: mean and std must hold 3 numbers each, got {mean!r} and {std!r}")
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    L.check(L.load().svl_panel_image_u8(_p(img), Bn, H, W, m3, s3, dst, bs, rs, _st()), "svl_panel_image_u8")
+    return canvas
+
+
+def panel_label(label, palette, canvas, y0, x0):
+    """canvas[b, y0 + y, x0 + x, :] = palette[l] for 0 <= l = label[b, y, x] < K, (255, 255, 255) otherwise
+    (svl_panel_label_u8).  label: contiguous int64 GPU [B, H, W]; palette: contiguous uint8 GPU [K, 3], 1 <= K <= 256;
+    canvas as in panel_image.  One launch on the current stream, no sync; nothing outside the tile is written."""
+    Bn, H, W, dst, bs, rs = _panel_tile("panel_label", label, torch.int64, 0, canvas, y0, x0)
+    if (not palette.is_cuda or palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3
+            or not palette.is_contiguous() or not 1 <= palette.shape[0] <= 256 or palette.device != label.device):
+        raise ValueError(f"panel_label: palette must be a contiguous uint8 GPU tensor [K, 3] with 1 <= K <= 256 on "
+                         f"{label.device}, got {tuple(palette.shape)} {palette.dtype} on {palette.device}")
+    L.check(L.load().svl_panel_label_u8(_p(label), Bn, H, W, _p(palette), palette.shape[0], dst, bs, rs, _st()),
+            "svl_panel_label_u8")
+    return canvas
 
 
 def set_gemm_emulation(mode):

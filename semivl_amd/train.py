@@ -236,7 +236,7 @@ def _step_scope(model, head_attrs):
 
 
 def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                      return_aux=False, teacher=None, monitor=None):
+                      return_aux=False, teacher=None, monitor=None, panel=None):
     """One iteration of semivl.py:223-328 (see _semivl_train_step for the body).  Per-step overrides taken from `cfg`
     (`wgrad_stream`, `overlap_streams`, `head_remat`, `head_chunk_class_images`) and the decode head's per-step memory
     plan are undone when the step ends -- also when it raises -- so that a later grad-enabled decode outside a training
@@ -263,10 +263,16 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
     of the weak view the step trains on -- mask_w, conf_w, the guidance when the step is guided, the teacher's maps when it
     supplies the labels -- are counted against batch['ignore_mask'] and, when the batch carries it, the held-back annotation
     batch['mask_u'] (monitor.update, one launch on the main stream after the label join), and the step's loss vector is
-    added to the meter's sum (monitor.add_losses, one launch).  Neither reads anything back; `aux` gets no new key."""
+    added to the meter's sum (monitor.add_losses, one launch).  Neither reads anything back; `aux` gets no new key.
+
+    `panel` (a panel.StepPanel, or None: the step launches and returns exactly what it does without one): what the reference
+    plots once per epoch (semivl.py:375-397) is rendered into the panel's canvas after the losses, on the main stream -- the
+    four images after CutMix, the label maps of the logits of x, s1, s2 and w_fp through the step's own _smax(pred, s.up)
+    (the kernel that makes mask_w: a tile shows what the step would train on), mask_x, the two mixed pseudo-label maps and
+    mask_w, and when guided the two mixed guidance maps and mclip.  Nothing the step computes reads the canvas."""
     with _step_scope(model, _HEAD_RESTORE_SEMIVL):
         return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux,
-                                  teacher, monitor)
+                                  teacher, monitor, panel)
 
 
 def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, return_aux=False,
@@ -437,7 +443,7 @@ def _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, red
 
 # ------------------------------------------------------------------------------------------------ the semivl step
 def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, reducer=None, fp_masks=None,
-                       return_aux=False, teacher=None, monitor=None):
+                       return_aux=False, teacher=None, monitor=None, panel=None):
     """One iteration of semivl.py:223-328 (method 'semivl', CELoss(ignore 255) or OHEM (cfg['criterion']) / CELoss; conf_mode 'pixelwise' /
     'pixelavg' / 'pixelratio', train_utils.py:30-49; mcc_loss_reduce 'mean_all' / 'mean_valid' / 'mean', semivl.py:52-58).  `batch`: the 12 step tensors on the GPU.  No host syncs: the
     returned `losses` is a device float[8] (LOSS_NAMES order).  CELoss kwargs `label_smoothing` / `weight` (celoss_kwargs)
@@ -480,6 +486,8 @@ def _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, re
     losses, dl4, dls = _branch_losses(preds4, preds_s, lab, b["ignore_mask"], mix, norm, ce_kw_x, cfg, s)
     if monitor is not None:
         monitor.add_losses(losses)
+    if panel is not None:
+        _panel_capture(panel, iters, b, preds4, preds_s, lab, mix, s)
     if cfg.get("step_barrier", False) and dist.is_initialized() and dist.get_world_size() > 1:
         # semivl.py:325: the reference synchronises all ranks before every backward.  It orders nothing the gradient
         # all-reduce does not order already, so it is off by default; the flag restores the reference's
@@ -699,6 +707,20 @@ def _branch_losses(preds4, preds_s, lab, ign, mix, norm, ce_kw_x, cfg, s):
     losses = ops.empty(8, device=ign.device)
     ops.semivl_loss(sums, norm.numel_u, s.lam, losses, norm.factors, norm.mc_counts)
     return losses, dl4, dls
+
+
+def _panel_capture(panel, iters, b, preds4, preds_s, lab, mix, s):
+    """The debug figure of semivl.py:375-397 in the reference's tile order; two _smax launches give the four prediction maps
+    ([x, w_fp] are neighbours in preds4, [s1, s2] are preds_s)."""
+    B = s.B
+    with torch.no_grad():
+        pm4 = _smax(preds4[B:3 * B].detach(), s.up)[1]
+        pms = _smax(preds_s.detach(), s.up)[1]
+    rows = [(pm4[:B], pms[:B], pms[B:], pm4[B:]),
+            (b["mask_x"], mix.mw[0], mix.mw[1], lab.mask_w)]
+    if s.guided:
+        rows.append((None, mix.mc[0], mix.mc[1], lab.mclip))
+    panel.capture(iters, (b["img_x"], b["img_s1"], b["img_s2"], b["img_w"]), rows)
 
 
 def _semivl_aux(lab, preds4, preds_s, dl4, dls, mask_x_ohem, s):
