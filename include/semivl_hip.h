@@ -649,7 +649,11 @@ int svl_bound2_f32(const float* rnorm, int64_t rows, const float* bias, int64_t 
 int svl_permute_rows_f32(const float* src, int64_t outer, int A, int B, int C, float* dst, svl_stream_t stream);
 
 /* GroupNorm (+ optional ReLU) on NHWC class-images: x [imgs, HW, C] (pixel stride ldx), groups of C/G channels,
- * stats [imgs, G, 2] = (mean, rstd); y pixel stride ldy (lets the result land in a concat slice). vlg_head.py:74-137 */
+ * stats [imgs, G, 2] = (mean, rstd); y pixel stride ldy (lets the result land in a concat slice). vlg_head.py:74-137
+ * Every entry point of the family takes C % 4 == 0, C <= 1024 with 256 % (C / 4) == 0, G <= 64, (C / G) % 4 == 0, pixel
+ * strides that are multiples of 4 and >= C, 16-byte aligned x / y / dy / dx / gamma / beta / scsh (all accesses are
+ * channel quads) and imgs <= 65535 (the apply passes put the images on gridDim.y); anything else is
+ * SVL_ERR_INVALID_ARG with nothing launched. */
 int svl_groupnorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, int imgs,
                       int64_t HW, int C, int G, int relu, float* y, int64_t ldy, float* stats, svl_stream_t stream);
 /* Conv2d(3x3, stride 1, pad 1, no bias; NHWC, optional second concat source read at image img / rep) of the Up blocks

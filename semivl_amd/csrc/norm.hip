@@ -986,6 +986,10 @@ inline bool gn_shape_ok(int C, int G) {
   const int CQ = C / 4;
   return CQ <= 256 && 256 % CQ == 0 && G <= 64;
 }
+// the apply passes put the images on gridDim.y, which the hardware limits to 65535
+constexpr int GN_MAX_IMGS = 65535;
+// every tensor access is a 16-byte channel quad
+inline bool gn_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -1202,6 +1206,10 @@ extern "C" int svl_groupnorm_fwd(const float* x, int64_t ldx, const float* gamma
   SVL_CHECK_ARG(x && gamma && beta && y && stats && imgs > 0 && HW > 0, "svl_groupnorm_fwd: bad args");
   SVL_CHECK_ARG(gn_shape_ok(C, G) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= C && ldy >= C,
                 "svl_groupnorm_fwd: unsupported C=%d G=%d ldx=%ld ldy=%ld", C, G, (long)ldx, (long)ldy);
+  SVL_CHECK_ARG(imgs <= GN_MAX_IMGS, "svl_groupnorm_fwd: imgs=%d exceeds %d (the apply pass puts the images on gridDim.y)", imgs,
+                GN_MAX_IMGS);
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
+                "svl_groupnorm_fwd: x, y, gamma and beta must be 16-byte aligned (float4 accesses)");
   hipStream_t st = (hipStream_t)stream;
   if (gn_wide(imgs, HW, C))
     hipLaunchKernelGGL(groupnorm_stats_kernel<1024>, dim3(imgs), dim3(1024), 0, st, x, (long)ldx, eps, (long)HW, C, G, stats);
@@ -1237,6 +1245,8 @@ __global__ void gn_table_kernel(const float* __restrict__ stats, const float* __
 extern "C" int svl_groupnorm_scale_shift(const float* stats, const float* gamma, const float* beta, int imgs, int C, int G,
                                          float* scsh, svl_stream_t stream) {
   SVL_CHECK_ARG(stats && gamma && beta && scsh && imgs > 0 && gn_shape_ok(C, G), "svl_groupnorm_scale_shift: bad args");
+  SVL_CHECK_ARG(gn_al16(gamma) && gn_al16(beta) && gn_al16(scsh),
+                "svl_groupnorm_scale_shift: gamma, beta and scsh must be 16-byte aligned (float4 accesses)");
   const long n = (long)imgs * (C / 4);
   hipLaunchKernelGGL(gn_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, stats, gamma, beta,
                      (long)imgs, C, G, scsh);
@@ -1252,6 +1262,9 @@ extern "C" int svl_groupnorm_apply(const float* x, int64_t ldx, const float* gam
   SVL_CHECK_ARG(x && gamma && beta && y && stats && imgs > 0 && HW > 0, "svl_groupnorm_apply: bad args");
   SVL_CHECK_ARG(gn_shape_ok(C, G) && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= C && ldy >= C,
                 "svl_groupnorm_apply: unsupported C=%d G=%d ldx=%ld ldy=%ld", C, G, (long)ldx, (long)ldy);
+  SVL_CHECK_ARG(imgs <= GN_MAX_IMGS, "svl_groupnorm_apply: imgs=%d exceeds %d (the images are on gridDim.y)", imgs, GN_MAX_IMGS);
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
+                "svl_groupnorm_apply: x, y, gamma and beta must be 16-byte aligned (float4 accesses)");
   const long npix = (long)imgs * HW;
   hipLaunchKernelGGL(groupnorm_apply_kernel, gn_apply_grid(imgs, HW, C), dim3(256), 0, (hipStream_t)stream, x, (long)ldx,
                      gamma, beta, npix, (long)HW, C, G, relu, stats, y, (long)ldy);
@@ -1266,6 +1279,13 @@ extern "C" int svl_groupnorm_bwd(const float* dy, int64_t lddy, const float* x, 
                 "svl_groupnorm_bwd: bad args (relu needs y or beta)");
   SVL_CHECK_ARG(gn_shape_ok(C, G) && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0 && (!relu || !y || ldy % 4 == 0),
                 "svl_groupnorm_bwd: unsupported C=%d G=%d", C, G);
+  SVL_CHECK_ARG(lddy >= C && ldx >= C && lddx >= C && (!relu || !y || ldy >= C),
+                "svl_groupnorm_bwd: a pixel stride is below C=%d (lddy=%ld ldx=%ld ldy=%ld lddx=%ld)", C, (long)lddy, (long)ldx,
+                (long)ldy, (long)lddx);
+  SVL_CHECK_ARG(imgs <= GN_MAX_IMGS, "svl_groupnorm_bwd: imgs=%d exceeds %d (the apply pass puts the images on gridDim.y)", imgs,
+                GN_MAX_IMGS);
+  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(dx) && gn_al16(gamma) && (!relu || (y ? gn_al16(y) : gn_al16(beta))),
+                "svl_groupnorm_bwd: dy, x, y, dx, gamma and beta must be 16-byte aligned (float4 accesses)");
   hipStream_t st = (hipStream_t)stream;
   if (gn_wide(imgs, HW, C))
     hipLaunchKernelGGL(groupnorm_bwd_sums_kernel<1024>, dim3(imgs), dim3(1024), 0, st, dy, (long)lddy, x, (long)ldx, y, (long)ldy,
@@ -1291,6 +1311,11 @@ extern "C" int svl_groupnorm_bwd_apply(const float* dy, int64_t lddy, const floa
                 "svl_groupnorm_bwd_apply: bad args (relu needs beta)");
   SVL_CHECK_ARG(gn_shape_ok(C, G) && lddy % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, "svl_groupnorm_bwd_apply: unsupported C=%d G=%d",
                 C, G);
+  SVL_CHECK_ARG(lddy >= C && ldx >= C && lddx >= C, "svl_groupnorm_bwd_apply: a pixel stride is below C=%d (lddy=%ld ldx=%ld lddx=%ld)",
+                C, (long)lddy, (long)ldx, (long)lddx);
+  SVL_CHECK_ARG(imgs <= GN_MAX_IMGS, "svl_groupnorm_bwd_apply: imgs=%d exceeds %d (the images are on gridDim.y)", imgs, GN_MAX_IMGS);
+  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(dx) && gn_al16(gamma) && (!relu || gn_al16(beta)),
+                "svl_groupnorm_bwd_apply: dy, x, dx, gamma and beta must be 16-byte aligned (float4 accesses)");
   const long npix = (long)imgs * HW;
   hipLaunchKernelGGL(groupnorm_bwd_apply_kernel, gn_apply_grid(imgs, HW, C), dim3(256), 0, (hipStream_t)stream, dy, (long)lddy, x,
                      (long)ldx, (const float*)nullptr, 0L, stats, gamma, beta, chan_sums, npix, (long)HW, C, G, relu, dx, (long)lddx);

@@ -1047,9 +1047,12 @@ def groupnorm_apply(x, ldx, gamma, beta, imgs, HW, Cc, G, relu, stats, y, ldy):
     return y
 
 
-def groupnorm_bwd(dy, lddy, x, ldx, y, ldy, stats, gamma, imgs, HW, Cc, G, relu, dx, lddx, beta=None):
-    """With `beta` given the ReLU mask is re-derived from x (the forward's own fma) and y is not read."""
-    cs = empty(imgs, 2, Cc, device=x.device)
+def groupnorm_bwd(dy, lddy, x, ldx, y, ldy, stats, gamma, imgs, HW, Cc, G, relu, dx, lddx, beta=None, cs=None):
+    """With `beta` given the ReLU mask is re-derived from x (the forward's own fma) and y is not read.  `cs`: a contiguous
+    [imgs, 2, C] tensor that receives the per-image channel sums (what groupnorm_bwd_from_sums takes) instead of a fresh one."""
+    if cs is None:
+        cs = empty(imgs, 2, Cc, device=x.device)
+    assert cs.is_contiguous() and cs.numel() == imgs * 2 * Cc
     L.check(L.load().svl_groupnorm_bwd(_p(dy), lddy, _p(x), ldx, _p(None if beta is not None else y), ldy, _p(stats),
                                        _p(gamma), _p(beta), imgs, HW, Cc, G, 1 if relu else 0, _p(dx), lddx, _p(cs),
                                        _st()), "svl_groupnorm_bwd")
@@ -2157,10 +2160,13 @@ def bn_bwd_reduce(dy, x, y, C, mean, invstd, remask=None):
     return sums
 
 
-def bn_bwd_apply(dy, x, y, C, mean, invstd, gamma, sums, count, want_dres=False, remask_beta=None):
+def bn_bwd_apply(dy, x, y, C, mean, invstd, gamma, sums, count, want_dres=False, remask_beta=None, dx_out=None, dres_out=None):
+    """`dx_out` / `dres_out`: [rows, C] views with unit column stride (a channel slice of a wider slab included) to write
+    instead of fresh tensors; dres_out implies want_dres."""
     rows = x.shape[0]
-    dx = empty(rows, C, device=x.device)
-    dres = empty(rows, C, device=x.device) if want_dres else None
+    want_dres = want_dres or dres_out is not None
+    dx = empty(rows, C, device=x.device) if dx_out is None else dx_out
+    dres = (empty(rows, C, device=x.device) if dres_out is None else dres_out) if want_dres else None
     if remask_beta is not None:
         y = None
     L.check(L.load().svl_bn_bwd_apply(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(y), y.stride(0) if y is not None else 0,
