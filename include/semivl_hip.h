@@ -565,7 +565,11 @@ int svl_panel_label_u8(const int64_t* label, int B, int H, int W, const uint8_t*
  * Normalisation / elementwise / attention helpers (maskclip_vit.py:120-144, vlg_head.py:39-137).
  * ---------------------------------------------------------------------------------------------- */
 
-/* LayerNorm over the last dim C of x [rows, C]; stats [rows, 2] = (mean, rstd). */
+/* LayerNorm over the last dim C of x [rows, C] (C % 4 == 0); stats [rows, 2] = (mean, rstd):
+ *   mean = sum(x) / C;  var = sum((x - mean)^2) / C (two passes, biased);  rstd = 1 / sqrt(var + eps);
+ *   y = (x - mean) * rstd * gamma + beta   (left to right in fp32; a product and the sum behind it may be fused).
+ * Every LayerNorm entry point below reads and writes x / y / gamma / beta / dy / dx / dx_add as 16-byte channel quads: a
+ * pointer that is not 16-byte aligned is refused (SVL_ERR_INVALID_ARG) before anything is launched. */
 int svl_layernorm_fwd(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C,
                       float* y, float* stats, svl_stream_t stream);
 /* The same with the result ALSO (y != NULL) or ONLY (y == NULL) emitted as packed bf16x3 planes, the A operand of the
@@ -591,8 +595,12 @@ int svl_layernorm_fwd_pack_f16x2(const float* x, const float* gamma, const float
 int svl_layernorm_bwd_pack_f16x2(const float* dy, const float* x, const float* stats, const float* gamma, int64_t rows, int C,
                                  const float* dx_add, float* dx, void* planes, int64_t planes_rows, int64_t row_off,
                                  int32_t* sexp, float* rnorm, unsigned* tensor_amax, svl_stream_t stream);
-/* dx = LN backward (+ dx_add if non-NULL, fused residual-grad add). If dgamma_part != NULL also writes
- * per-block partial sums dgamma_part/dbeta_part [nparts, C] (nparts = svl_layernorm_bwd_parts(rows)). */
+/* dx = LN backward (+ dx_add if non-NULL, fused residual-grad add), C <= 1024, from the stats it is given:
+ *   xhat = (x - mean) * rstd;  m1 = sum_c(dy gamma) / C;  m2 = sum_c(dy gamma xhat) / C;
+ *   dx = rstd * (dy gamma - m1 - xhat m2) (+ dx_add).
+ * If dgamma_part != NULL (dbeta_part then too) also writes per-block partial sums dgamma_part/dbeta_part [nparts, C]
+ * (nparts = svl_layernorm_bwd_parts(rows)) of dy * xhat and of dy over the block's rows, in a fixed order:
+ *   dgamma = sum_r dy xhat = column sum of dgamma_part,  dbeta = sum_r dy = column sum of dbeta_part. */
 int svl_layernorm_bwd_parts(int64_t rows);
 int svl_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, int64_t rows,
                       int C, const float* dx_add, float* dx, float* dgamma_part, float* dbeta_part,
@@ -604,13 +612,18 @@ int svl_softmax_rows_fwd(float* s, int64_t rows, int cols, int64_t ld, float sca
 int svl_softmax_rows_bwd(float* dp, const float* p, int64_t rows, int cols, int64_t ld, float scale,
                          svl_stream_t stream);
 
-/* y = x / max(||x||_2, eps) over rows of [rows, C]; inv_norm [rows] saved. (maskclip_vit.py:555, vlg_head.py:215) */
+/* y = x / max(||x||_2, eps) over rows of [rows, C]; inv_norm [rows] = 1 / max(||x||_2, eps) saved.
+ * (maskclip_vit.py:555, vlg_head.py:215)   Backward: dx = inv_norm * (dy - y * <dy, y>).  This is the gradient of
+ * x / max(||x||_2, eps) only while the clamp is inactive (||x||_2 >= eps); where it is active the gradient is dy / eps, from
+ * which the formula differs by y <dy, y> / eps (nothing for a zero row, y = 0).  The project calls it with eps in
+ * {0, 1e-12} on CLIP embeddings, whose norms are far above either. */
 int svl_l2norm_fwd(const float* x, int64_t rows, int C, float eps, float* y, float* inv_norm, svl_stream_t stream);
 int svl_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, int64_t rows, int C, float* dx,
                    svl_stream_t stream);
 
 /* out[c] (+)= sum_r x[r*ld + c]  (bias gradients). Two deterministic stages through ws
- * (svl_colsum_ws_floats(rows, C) floats). */
+ * (svl_colsum_ws_floats(rows, C) floats): the order of the additions is fixed for a given (rows, C, ld, alignment), so two
+ * calls give the same bits; which order it is is not part of the contract (no chain is longer than rows + 8 additions). */
 int64_t svl_colsum_ws_floats(int64_t rows, int C);
 int svl_colsum_f32(const float* x, int64_t rows, int C, int64_t ld, float* out, int accumulate, float* ws,
                    svl_stream_t stream);

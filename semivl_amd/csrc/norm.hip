@@ -1000,6 +1000,8 @@ extern "C" int svl_layernorm_fwd_planes(const float* x, const float* gamma, cons
                 "svl_layernorm_fwd: bad args");
   SVL_CHECK_ARG(!planes || (C % 16 == 0 && planes_rows >= rows && planes_rows % 256 == 0),
                 "svl_layernorm_fwd_planes: C %% 16 == 0 and planes_rows (%% 256 == 0) >= rows");
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
+                "svl_layernorm_fwd: x / y / gamma / beta must be 16-byte aligned");
   const long rpb = planes ? 32 : 4;
   const int grid = (int)((rows + rpb - 1) / rpb > 4096 * 4 ? 4096 * 4 : (rows + rpb - 1) / rpb);
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
@@ -1013,6 +1015,8 @@ extern "C" int svl_layernorm_fwd_planes_f16x2(const float* x, const float* gamma
   SVL_CHECK_ARG(x && gamma && beta && planes && sexp && stats && rows > 0 && C > 0 && C % 16 == 0 && planes_rows >= rows &&
                     planes_rows % 256 == 0,
                 "svl_layernorm_fwd_planes_f16x2: bad args (C %% 16 == 0, planes_rows (%% 256 == 0) >= rows, sexp required)");
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
+                "svl_layernorm_fwd_planes_f16x2: x / y / gamma / beta must be 16-byte aligned");
   const long nb = (rows + 31) / 32;
   const int grid = (int)(nb > 4096 * 4 ? 4096 * 4 : nb);
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
@@ -1039,6 +1043,8 @@ extern "C" int svl_layernorm_bwd(const float* dy, const float* x, const float* s
   SVL_CHECK_ARG(dy && x && stats && gamma && dx && rows > 0 && C > 0 && C % 4 == 0 && C <= 1024,
                 "svl_layernorm_bwd: bad args (C=%d)", C);
   SVL_CHECK_ARG((dgamma_part == nullptr) == (dbeta_part == nullptr), "svl_layernorm_bwd: dgamma/dbeta go together");
+  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(gamma) && gn_al16(dx_add) && gn_al16(dx),
+                "svl_layernorm_bwd: dy / x / gamma / dx_add / dx must be 16-byte aligned");
   // With weight gradients a block keeps per-column partial sums over its rows (few, long blocks: nparts slabs to reduce).
   // Without them (the ViT's frozen LayerNorms: every call of the encoder's backward) nothing ties rows together: 8 rows per
   // block, i.e. two per wave -- the row loop is a load -> two wave reductions -> store chain, and only many resident waves
@@ -1069,6 +1075,8 @@ extern "C" int svl_layernorm_fwd_pack_f16x2(const float* x, const float* gamma, 
                                             int64_t row_off, int32_t* sexp, float* rnorm, int row_rnorm,
                                             unsigned* tensor_amax, svl_stream_t stream) {
   SVL_CHECK_ARG(x && gamma && beta && stats, "svl_layernorm_fwd_pack_f16x2: bad args");
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
+                "svl_layernorm_fwd_pack_f16x2: x / y / gamma / beta must be 16-byte aligned");
   if (int rc = lnp_check("svl_layernorm_fwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
   if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
   const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
@@ -1084,6 +1092,8 @@ extern "C" int svl_layernorm_bwd_pack_f16x2(const float* dy, const float* x, con
                                             int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm,
                                             unsigned* tensor_amax, svl_stream_t stream) {
   SVL_CHECK_ARG(dy && x && stats && gamma && dx, "svl_layernorm_bwd_pack_f16x2: bad args");
+  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(gamma) && gn_al16(dx_add) && gn_al16(dx),
+                "svl_layernorm_bwd_pack_f16x2: dy / x / gamma / dx_add / dx must be 16-byte aligned");
   if (int rc = lnp_check("svl_layernorm_bwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
   if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
   const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};

@@ -1208,6 +1208,7 @@ def test_patch_embed(dev):
 # ------------------------------------------------------------------------------------------------ norms
 @pytest.mark.parametrize("rows,C,eps", [(1025, 768, 1e-6), (77, 256, 1e-5), (4, 1024, 1e-5)])
 def test_layernorm(dev, rows, C, eps):
+    """(The edge shapes, hostile rows and derived bounds of these kernels: tests/test_rownorm_kernels_gpu.py.)"""
     from semivl_amd import ops
     x = rnd(rows, C, dev=dev, seed=10).requires_grad_(True)
     g = (1 + 0.1 * torch.randn(C, device=dev)).requires_grad_(True)
@@ -1225,6 +1226,7 @@ def test_layernorm(dev, rows, C, eps):
 
 
 def test_softmax_rows(dev):
+    """(Every width, stride and input kind under a derived bound: tests/test_rownorm_kernels_gpu.py.)"""
     from semivl_amd import ops
     rows, cols, ld = 100, 1025, 1028
     s = rnd(rows, ld, dev=dev, seed=11, scale=3)
@@ -1242,6 +1244,7 @@ def test_softmax_rows(dev):
 
 
 def test_l2norm_colsum_eltwise(dev):
+    """(l2norm's clamp and colsum's kernel choices, exact on integer data: tests/test_rownorm_kernels_gpu.py.)"""
     from semivl_amd import ops
     x = rnd(1000, 512, dev=dev, seed=12).requires_grad_(True)
     ref = x / x.norm(dim=1, keepdim=True)
