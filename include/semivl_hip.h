@@ -1071,6 +1071,36 @@ int svl_droppath_fwd_f32(const float* branch, const float* resid, const float* m
 int svl_droppath_bwd_f32(const float* dout, const float* mask, float scale, float* dbranch, int B, int T, int E,
                          svl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * CLIP text tower (third_party/zegclip/models/backbones/text_encoder.py:79-87): the forward-only pieces beside the GEMMs,
+ * svl_layernorm_fwd and svl_l2norm_fwd.  fp32, row-major matrices without padding.  A null pointer or a size outside its
+ * range is SVL_ERR_INVALID_ARG, named in svl_last_error(), and nothing is written.  No atomics: results are bitwise
+ * reproducible.
+ *   svl_text_embed_f32       tokens int64 [n, L], table [V, W], pos [L, W] -> x [n * L, W] with x[(i, t)] = table[tok[i, t]] +
+ *                            pos[t] (one fp32 addition) and eot int32 [n] = index of the first maximum of tok[i, :]
+ *                            (torch.argmax).  A token outside [0, V) is never dereferenced: its row of x is NaN.  16-byte
+ *                            accesses when W % 4 == 0 and table, pos and x are 16-byte aligned.
+ *   svl_causal_attn_fwd_f32  qkv [n * L, 3 W] laid out q | k | v with W = 64 H (head dim 64, scale 64^-0.5), 1 <= L <= 192
+ *                            -> out [n * L, W].  Query t attends keys 0 .. t of its own sequence: the -inf upper triangle
+ *                            of CLIPTextEncoder.build_attention_mask.  Keys above t are not read for row t (no score, no
+ *                            exponential, no value term), so row t does not depend on them in any bit.  No probabilities are
+ *                            written.
+ *   svl_quickgelu_f32        y = x * sigmoid(1.702 x) on `count` elements; y may be x.  16-byte accesses when both pointers
+ *                            are 16-byte aligned (scalar for the last count % 4 elements), scalar otherwise.
+ *   svl_gather_rows_f32      out[i, :] = x[i * L + idx[i], :] for x [n * L, E], idx int32 [n].  An index outside [0, L) is
+ *                            never dereferenced: its row of out is NaN.
+ *   svl_segment_mean_f32     x [m, E], offsets int32 [N + 1] on the device (prefix offsets, offsets[0] = 0, offsets[N] = m)
+ *                            -> out [N, E]: the rows offsets[c] .. offsets[c + 1] - 1 added in ascending order, then divided
+ *                            by their count; a segment of one row is a copy.  N > m (some segment must be empty) is refused;
+ *                            rows outside [0, m) are never read and an empty segment yields NaN (callers check the table on
+ *                            the host). */
+int svl_text_embed_f32(const int64_t* tokens, const float* table, const float* pos, int n, int L, int V, int W, float* x,
+                       int* eot, svl_stream_t stream);
+int svl_causal_attn_fwd_f32(const float* qkv, int n, int L, int H, float* out, svl_stream_t stream);
+int svl_quickgelu_f32(const float* x, float* y, int64_t count, svl_stream_t stream);
+int svl_gather_rows_f32(const float* x, const int* idx, int n, int L, int E, float* out, svl_stream_t stream);
+int svl_segment_mean_f32(const float* x, int64_t m, int E, const int* offsets, int N, float* out, svl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

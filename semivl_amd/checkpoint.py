@@ -13,6 +13,7 @@
 Host-side plumbing only: nothing here runs inside a training step.
 """
 import os
+import re
 
 import torch
 
@@ -75,6 +76,28 @@ def convert_clip_visual(clip_state_dict, backbone=True):
     if proj is not None:
         res["proj"] = {"weight": proj}
     return res
+
+
+_TEXT_KEY = re.compile(r"^(token_embedding\.weight|positional_embedding|text_projection|ln_final\.(weight|bias)|"
+                       r"transformer\.resblocks\.\d+\.(ln_[12]\.(weight|bias)|attn\.in_proj_(weight|bias)|"
+                       r"attn\.out_proj\.(weight|bias)|mlp\.c_(fc|proj)\.(weight|bias)))$")
+
+
+def clip_text_keys(clip_state_dict):
+    """The keys of CLIP's text tower in a CLIP state dict, in its order: token_embedding.weight, positional_embedding,
+    ln_final.*, text_projection and transformer.resblocks.{i}.{ln_1, ln_2, attn.in_proj_*, attn.out_proj, mlp.c_fc,
+    mlp.c_proj}.*.  `visual.*`, `logit_scale`, `input_resolution`, `context_length`, `vocab_size` are not among them."""
+    return [k for k in clip_state_dict if _TEXT_KEY.match(k)]
+
+
+def convert_clip_text(clip_state_dict):
+    """{'meta': {}, 'state_dict': {<CLIP's own key>: fp32 tensor}} of the text tower (clip_<model>_text_encoder.pth): what
+    model.text_encoder.CLIPTextEncoder loads.  The reference has no such file: it makes its text embeddings with the `clip`
+    package, from the same tensors."""
+    keys = clip_text_keys(clip_state_dict)
+    if "token_embedding.weight" not in keys or "text_projection" not in keys:
+        raise ValueError("convert_clip_text: the state dict holds no CLIP text tower (no token_embedding.weight / text_projection)")
+    return {"meta": {}, "state_dict": {k: clip_state_dict[k].detach().float().clone() for k in keys}}
 
 
 def save_checkpoint(path, model, optimizer, epoch, ddp_prefix=True, ema_model=None, extra=None):

@@ -229,6 +229,11 @@ SIGNATURES = {
     "svl_prompt_rows_bwd_f32": (_I, [_P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _P]),
     "svl_droppath_fwd_f32": (_I, [_P, _P, _P, _F, _P, _I, _I, _I, _P]),
     "svl_droppath_bwd_f32": (_I, [_P, _P, _F, _P, _I, _I, _I, _P]),
+    "svl_text_embed_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "svl_causal_attn_fwd_f32": (_I, [_P, _I, _I, _I, _P, _P]),
+    "svl_quickgelu_f32": (_I, [_P, _P, _L, _P]),
+    "svl_gather_rows_f32": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "svl_segment_mean_f32": (_I, [_P, _L, _I, _P, _I, _P, _P]),
 }
 
 _lib = None

@@ -358,6 +358,47 @@ def nested_set(dic, key, value):
     dic[keys[-1]] = value
 
 
+def text_embedding_files(spec, nclass):
+    """cfg['text_embedding_files'] = dict(text=PATH, mcc=PATH, pl=PATH) -> the three paths (mcc and pl default to text), checked
+    here rather than in the first step: every file must hold `nclass` rows, or as many rows as the concept counts of its name
+    (text_embeddings.get_class_to_concept_idxs: the two built-in lists, or a `.concepts.json` sidecar) add up to, for `nclass`
+    classes."""
+    if not isinstance(spec, dict):
+        raise ValueError(f"cfg['text_embedding_files'] must be a dict(text=..., mcc=..., pl=...), got {type(spec).__name__}")
+    for k in spec:
+        if k not in ("text", "mcc", "pl"):
+            raise ValueError(f"cfg['text_embedding_files']: unknown key {k!r} (text, mcc, pl)")
+    if "text" not in spec:
+        raise ValueError("cfg['text_embedding_files']: the key 'text' is required")
+    out = {}
+    for k in ("text", "mcc", "pl"):
+        v = spec.get(k, spec["text"])
+        if not isinstance(v, str) or not v:
+            raise ValueError(f"cfg['text_embedding_files'][{k!r}] must be a path string, got {v!r}")
+        out[k] = v
+    if out["pl"] != out["text"]:     # VLM reads one file for both, as the reference asserts (vlm.py)
+        raise ValueError(f"cfg['text_embedding_files']['pl'] must name the same file as 'text' ({out['text']!r}), got {out['pl']!r}")
+    for k, v in out.items():
+        try:
+            shape = np.load(_resolve(v), mmap_mode="r").shape
+        except FileNotFoundError:
+            raise ValueError(f"cfg['text_embedding_files'][{k!r}]: no file {v!r}") from None
+        if len(shape) != 2:
+            raise ValueError(f"cfg['text_embedding_files'][{k!r}]: {v!r} holds an array of shape {tuple(shape)}, not [rows, embed]")
+        if shape[0] == nclass:
+            continue
+        try:
+            idxs = get_class_to_concept_idxs(v)
+        except ValueError:
+            raise ValueError(f"cfg['text_embedding_files'][{k!r}]: {v!r} has {shape[0]} rows for nclass = {nclass} and no "
+                             f"concept counts (.concepts.json) beside it") from None
+        rows = sum(len(i) for i in idxs.values())
+        if len(idxs) != nclass or rows != shape[0]:
+            raise ValueError(f"cfg['text_embedding_files'][{k!r}]: {v!r} has {shape[0]} rows; its concept counts cover {rows} "
+                             f"rows of {len(idxs)} classes, nclass = {nclass}")
+    return out
+
+
 def build_model(cfg):
     """builder.py:104-159."""
     model_type = cfg["model"]
@@ -371,11 +412,17 @@ def build_model(cfg):
             nested_set(mcfg, "img_size", cfg["crop_size"])
             nested_set(mcfg, "model.backbone.img_size", (cfg["crop_size"], cfg["crop_size"]))
             nested_set(mcfg, "model.decode_head.img_size", cfg["crop_size"])
-        prefix = {"pascal": "voc12_wbg", "cityscapes": "cityscapes", "coco": "coco", "ade": "ade"}[cfg["dataset"]]
-        base = "configs/_base_/datasets/text_embedding/"
-        nested_set(mcfg, "model.load_text_embedding", f"{base}{prefix}_{cfg['text_embedding_variant']}.npy")
-        nested_set(mcfg, "model.load_mcc_text_embedding", f"{base}{prefix}_{cfg['mcc_text']}.npy")
-        nested_set(mcfg, "model.load_pl_text_embedding", f"{base}{prefix}_{cfg['pl_text']}.npy")
+        if cfg.get("text_embedding_files") is not None:    # (not a reference key) any class list: tools/text_embeddings.py
+            files = text_embedding_files(cfg["text_embedding_files"], cfg["nclass"])
+            nested_set(mcfg, "model.load_text_embedding", files["text"])
+            nested_set(mcfg, "model.load_mcc_text_embedding", files["mcc"])
+            nested_set(mcfg, "model.load_pl_text_embedding", files["pl"])
+        else:
+            prefix = {"pascal": "voc12_wbg", "cityscapes": "cityscapes", "coco": "coco", "ade": "ade"}[cfg["dataset"]]
+            base = "configs/_base_/datasets/text_embedding/"
+            nested_set(mcfg, "model.load_text_embedding", f"{base}{prefix}_{cfg['text_embedding_variant']}.npy")
+            nested_set(mcfg, "model.load_mcc_text_embedding", f"{base}{prefix}_{cfg['mcc_text']}.npy")
+            nested_set(mcfg, "model.load_pl_text_embedding", f"{base}{prefix}_{cfg['pl_text']}.npy")
     if cfg.get("clip_encoder") is not None:
         ccfg = copy.deepcopy(load_model_cfg(cfg["clip_encoder"]))
         ccfg["img_size"] = mcfg["img_size"]

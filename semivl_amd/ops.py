@@ -2249,3 +2249,75 @@ def bcast_rows_bwd(dslab, c_off, Cc, imgs, HW, out=None):
     assert tuple(out.shape) == (imgs, Cc)
     L.check(L.load().svl_bcast_rows_bwd(_p(dslab), ldd, c_off, imgs, HW, Cc, _p(out), ldo, _st()), "svl_bcast_rows_bwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ CLIP text tower (csrc/text.hip)
+def text_embed(tokens, table, pos):
+    """tokens int64 [n, L], table [V, W], pos [L, W] -> (x [n * L, W] = table[tok] + pos, eot int32 [n] = argmax of each
+    row).  The ids are checked on the host before the launch (one sync: this runs once per class list, never in a step);
+    an id outside [0, V) raises ValueError and nothing is launched."""
+    _chk(tokens, torch.int64), _chk(table), _chk(pos)
+    assert tokens.dim() == 2 and tokens.is_contiguous() and table.is_contiguous() and pos.is_contiguous()
+    n, Lc = tokens.shape
+    V, W = table.shape
+    assert tuple(pos.shape) == (Lc, W), (tuple(pos.shape), (Lc, W))
+    if n and Lc:
+        lo, hi = int(tokens.min()), int(tokens.max())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"text_embed: token id {lo if lo < 0 else hi} outside [0, {V})")
+    x = empty(n * Lc, W, device=tokens.device)
+    eot = empty(n, dtype=torch.int32, device=tokens.device)
+    L.check(L.load().svl_text_embed_f32(_p(tokens), _p(table), _p(pos), n, Lc, V, W, _p(x), _p(eot), _st()),
+            "svl_text_embed_f32")
+    return x, eot
+
+
+def causal_attn_fwd(qkv, n, Lc, H, out=None):
+    """qkv [n * L, 3 * 64 H] (q | k | v) -> [n * L, 64 H]; query t attends keys 0 .. t of its sequence."""
+    _chk(qkv)
+    valid = n >= 1 and 1 <= Lc <= 192 and H >= 1      # anything else is the library's to refuse, by name
+    assert not valid or (qkv.is_contiguous() and tuple(qkv.shape) == (n * Lc, 3 * 64 * H)), tuple(qkv.shape)
+    if out is None:
+        out = empty(n * Lc, 64 * H, device=qkv.device) if valid else empty(1, device=qkv.device)
+    L.check(L.load().svl_causal_attn_fwd_f32(_p(qkv), n, Lc, H, _p(out), _st()), "svl_causal_attn_fwd_f32")
+    return out
+
+
+def quickgelu(x, out=None):
+    """x * sigmoid(1.702 x), elementwise; out may be x."""
+    _chk(x)
+    if out is None:
+        out = torch.empty_like(x)
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()
+    L.check(L.load().svl_quickgelu_f32(_p(x), _p(out), x.numel(), _st()), "svl_quickgelu_f32")
+    return out
+
+
+def gather_rows(x, idx, Lc):
+    """x [n * L, E], idx int32 [n] -> out [n, E] with out[i] = x[i * L + idx[i]]."""
+    _chk(x), _chk(idx, torch.int32)
+    rows, E = x.shape
+    n = idx.numel()
+    assert x.is_contiguous() and idx.is_contiguous() and rows == n * Lc, (rows, n, Lc)
+    out = empty(n, E, device=x.device)
+    L.check(L.load().svl_gather_rows_f32(_p(x), _p(idx), n, Lc, E, _p(out), _st()), "svl_gather_rows_f32")
+    return out
+
+
+def segment_mean(x, offsets_i32):
+    """x [m, E], offsets int32 [N + 1] on the device (model.text_embeddings.concept_offsets) -> [N, E], the mean of each
+    segment's rows.  The table is checked on the host (one sync, as text_embed): an empty segment, a descending table or
+    one that does not span [0, m] raises ValueError and nothing is launched."""
+    _chk(x), _chk(offsets_i32, torch.int32)
+    m, E = x.shape
+    assert x.is_contiguous() and offsets_i32.is_contiguous() and offsets_i32.dim() == 1
+    offs = offsets_i32.tolist()
+    N = len(offs) - 1
+    if N < 1 or offs[0] != 0 or offs[-1] != m:
+        raise ValueError(f"segment_mean: offsets must run from 0 to {m}, got {offs[:1]} .. {offs[-1:]}")
+    for c in range(N):
+        if offs[c + 1] <= offs[c]:
+            raise ValueError(f"segment_mean: segment {c} is empty (offsets {offs[c]} .. {offs[c + 1]})")
+    out = empty(N, E, device=x.device)
+    L.check(L.load().svl_segment_mean_f32(_p(x), m, E, _p(offsets_i32), N, _p(out), _st()), "svl_segment_mean_f32")
+    return out
