@@ -16,9 +16,9 @@
  *     the same call (capture-legal: events only), so from the caller's point of view everything is ordered on `stream`;
  *   - host-side state: one helper stream + two events per (device, caller stream) pair, created lazily under a mutex on
  *     first use and kept until svl_stream_release(stream) / svl_shutdown(); per-device kernel attributes set once per
- *     device; and the process-wide configuration switches svl_set_gemm_emulation / svl_set_conv_tiled (relaxed
- *     atomics seeded from the environment, read once per call, selecting between kernels that compute the same
- *     function).  Nothing else is mutable: the library is re-entrant across host threads, devices and streams -- calls
+ *     device; the process-wide arithmetic mode svl_set_gemm_emulation (a relaxed atomic seeded from the environment,
+ *     read once per call) and the environment's A/B switches (svl_switches, read once per process), all selecting
+ *     between kernels that compute the same function.  Nothing else is mutable: the library is re-entrant across host threads, devices and streams -- calls
  *     that use different streams never share a helper stream, an event or a buffer;
  *   - tensors are dense fp32 unless stated; token tensors are [rows, C] row-major ("NHWC"/[B,T,C]);
  *   - returns 0 (SVL_OK) or a negative svl_status; svl_last_error() gives the message (thread-local).
@@ -42,7 +42,7 @@ typedef enum svl_status {
   SVL_ERR_UNSUPPORTED = -3
 } svl_status;
 
-int svl_version(void); /* 606: + svl_grad_clip_f32, svl_grad_clip_ws_doubles, svl_adamw_step_dscale, svl_sgd_step_dscale (gradient-norm clipping on the arena, formed and applied on the device); 605: + svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32, svl_ce_up_lsw_num_blocks, svl_class_weight_sum_f64, svl_class_weight_sum_ws_doubles, svl_scale_from_sum_f32 (label_smoothing / class weights of the labelled cross entropy); 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
+int svl_version(void); /* 607: + svl_gemm_route (the routing of svl_gemm_f32 as a host-only query), svl_switches; - svl_set_conv_tiled; 606: + svl_grad_clip_f32, svl_grad_clip_ws_doubles, svl_adamw_step_dscale, svl_sgd_step_dscale (gradient-norm clipping on the arena, formed and applied on the device); 605: + svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32, svl_ce_up_lsw_num_blocks, svl_class_weight_sum_f64, svl_class_weight_sum_ws_doubles, svl_scale_from_sum_f32 (label_smoothing / class weights of the labelled cross entropy); 604: + svl_gap_tokens_{fwd,bwd}, svl_bcast_rows_{fwd,bwd} (the pooling branch of the DeepLabV3+ head); 603: + svl_layernorm_{fwd,bwd}_pack_f16x2, tensor_amax of svl_split_planes_f16x2, svl_gemm_desc::a_amax / b_amax, svl_absmax_launches (ViT glue passes read each matrix once); 602: + svl_target_prob_f32, svl_target_prob_up_f32, svl_ohem_ws_bytes, svl_ohem_threshold_f32, svl_ohem_relabel_i64 (the OHEM supervised criterion); 601: + SVL_B_NC_GELU / SVL_B_NC_LN / SVL_B_PATCHT producers, svl_gemm_desc::b_stats / b_gamma / b_beta (ViT fine-tuning weight gradients); 600: round-6 ABI (+ svl_permute4_f32, svl_bound2_f32, svl_attention tail kernels replace the row kernels); 502: + svl_ce_up_fused_f32, svl_softmax_max_up_f32, svl_ce_up_num_blocks (pixel losses on head-resolution logits); 501: + svl_attention_{fwd,bwd}_h2, svl_attention_h2_ws_bytes (fused attention on fp16 x 2 pre-packed operands); 500: round-5 ABI (fp16 x 2 planes: svl_split_planes_f16x2, svl_planes_bytes_fmt, fmt / scale fields of svl_pgemm_desc); 401: + svl_conv3x3_weight_planes, svl_gemm_desc::conv_w_planes, w_planes of svl_conv3x3_gn_f32; 400: round-4 ABI (gn_in / svl_conv3x3_gn_f32 / svl_groupnorm_apply / _scale_shift, svl_permute_rows_f32,
                            svl_stream_prepare, svl_last_gemm_path; gn_in arguments of the tiled weight gradient and the Conv2d(C -> 1)
                            entries, `accumulate` of svl_avgpool_cat_bwd); 300: round-3 ABI (packed-planes operands; planes outputs of LayerNorm / attention; loss-mode arguments of
                            the pixel-loss entries; 200 = round 2: helper-stream contexts, caller-owned scratch everywhere) */
@@ -179,7 +179,27 @@ typedef struct svl_gemm_desc {
                               * every other launch ignores them.  NULL: the pass runs. */
 } svl_gemm_desc;
 
+/* Validates the descriptor (SVL_ERR_INVALID_ARG / SVL_ERR_UNSUPPORTED before anything is launched), ROUTES it and runs the
+ * route.  The route is host arithmetic on the descriptor, the arithmetic mode and svl_switches() alone -- svl_gemm_route
+ * returns it without launching.  Families, in the order they are tried: the short-K row stream (fp32, or the split pipe in
+ * mode 6), the elementwise Conv2d(1 -> N) kernel, the spatially tiled narrow 3x3 convolution, the whole-image dilated 3x3
+ * convolution, then -- with a ragged row count (M >= 8192, M % 128 != 0) cut into a 128-aligned part and the leftover rows
+ * on the helper stream, each routed on its own -- the in-register split kernel (modes 3 / 6: bf16 x 2, bf16 x 3 or, with
+ * emu_ws, fp16 x 2 after the operand-maximum passes) or the exact fp32 kernel. */
 int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream);
+
+/* What svl_gemm_f32(d) would do, without doing it: same validation and status, same routing function, no launch and no device
+ * call.  Pointers are read for their alignment (and for being null) only, so host addresses serve. */
+typedef struct svl_gemm_route_info {
+  int path;          /* the value svl_last_gemm_path() reports after the launch                                             */
+  int h2;            /* 1: the in-register split kernel runs on fp16 x 2 terms (emu_ws given and worth its maximum passes)  */
+  int tile_m, tile_n;/* block tile of the exact fp32 / in-register split kernel that serves the launch (the 128-aligned part  */
+  int blocks_per_cu; /* of a ragged launch) and the blocks of it a CU holds; 0 for the families that do not tile this way    */
+  int max_passes;    /* operand-maximum passes the launch makes (svl_absmax_launches() grows by this; both parts of a ragged
+                      * launch together; the producers' transformed B operand has a pass of its own kind, not counted)      */
+  int ragged_rows;   /* rows of the leftover part of a ragged launch (M % 128), else 0                                      */
+} svl_gemm_route_info;
+int svl_gemm_route(const svl_gemm_desc* d, svl_gemm_route_info* out);
 
 /* Process-wide (relaxed-atomic, read once per call) arithmetic mode of the LARGE dense GEMMs (M >= 256, N >= 96, K >= 64, dense operand modes):
  *   0  v_mfma_f32_32x32x2_f32, exact fp32 fma chain (default);
@@ -189,15 +209,20 @@ int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream);
  *      the backward), the forward / input gradient of the spatially tiled 3x3 convolutions, and the K = 64 / 128 row
  *      streams with the ConvTranspose2d(k 2, s 2) pixel-shuffle store (SVL_OUT_CONVT2X; csrc/gemm_shortk.hip);
  *   3  2-term split, 3 products (~16 mantissa bits, 5.3x the MFMA rate); dense GEMMs only.
- * Initial value: environment variable SVL_GEMM_EMU (0 if unset).  Inputs, outputs and accumulation stay fp32.
- * A/B switches (read once per process): SVL_ATTN_NO_EMU, SVL_CONV_TILED_NO_EMU keep those kernels on the fp32 pipe. */
+ * Initial value: environment variable SVL_GEMM_EMU (0 if unset).  Inputs, outputs and accumulation stay fp32. */
 int svl_set_gemm_emulation(int mode);
 int svl_get_gemm_emulation(void);
-/* 1 (default): narrow (N = 32 / 64) 3x3 stride-1 convolutions run on the spatially tiled kernel; 0: implicit GEMM only.
- * Initial value: 0 if the environment variable SVL_CONV_NO_TILED is set. */
-int svl_set_conv_tiled(int on);
+/* The environment's A/B switches of the GEMM / convolution dispatch as SVL_SW_* bits; every bit is set unless its variable
+ * is.  The library reads the four variables here, once per process, and nowhere else. */
+enum {
+  SVL_SW_EMU_H2 = 1,         /* SVL_GEMM_EMU_NO_H2: mode 6 keeps the bf16 x 3 form where emu_ws would allow fp16 x 2         */
+  SVL_SW_SHORTK = 2,         /* SVL_GEMM_NO_SHORTK: no short-K row stream, no elementwise Conv2d(1 -> N) kernel             */
+  SVL_SW_CONV_TILED = 4,     /* SVL_CONV_NO_TILED: narrow / dilated 3x3 convolutions stay on the implicit GEMM              */
+  SVL_SW_CONV_TILED_EMU = 8  /* SVL_CONV_TILED_NO_EMU: mode 6 keeps the tiled 3x3 kernels on the fp32 pipe                  */
+};
+int svl_switches(void);
 /* Measurement aid (bench.py prices a launch against the pipe that served it; no reference counterpart): which kernel family
- * the calling thread's LAST svl_gemm_f32 call dispatched to -- 0 exact fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 bf16 split
+ * the calling thread's LAST svl_gemm_f32 (or svl_conv3x3_gn_f32 / svl_conv3x3_wgrad_tiled) call dispatched to -- 0 exact fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 bf16 split
  * products (v_mfma_f32_32x32x16_bf16; emulation mode 3 / 6: dense, implicit-GEMM forward / input gradient / weight gradient,
  * tiled 3x3), 2 the short-K row stream (fp32 MFMA, HBM-bound), 3 an elementwise kernel (no MFMA), 4 the in-register split
  * kernel on fp16 x 2 terms (three products; svl_gemm_desc::emu_ws). */

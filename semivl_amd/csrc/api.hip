@@ -1,6 +1,7 @@
 // Error plumbing, version, and the per-(device, stream) helper-stream contexts of libsemivl_hip.so.
 #include "svl_common.h"
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include <map>
 #include <mutex>
@@ -15,7 +16,15 @@ void svl_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int svl_version(void) { return 606; }
+extern "C" int svl_version(void) { return 607; }
+
+// The only place the library reads these four variables (a function-local static: initialised once, thread-safely).
+extern "C" int svl_switches(void) {
+  static const int sw = (getenv("SVL_GEMM_EMU_NO_H2") ? 0 : SVL_SW_EMU_H2) | (getenv("SVL_GEMM_NO_SHORTK") ? 0 : SVL_SW_SHORTK) |
+                        (getenv("SVL_CONV_NO_TILED") ? 0 : SVL_SW_CONV_TILED) |
+                        (getenv("SVL_CONV_TILED_NO_EMU") ? 0 : SVL_SW_CONV_TILED_EMU);
+  return sw;
+}
 
 extern "C" int svl_last_error(char* buf, size_t len) {
   const size_t n = strlen(g_err);

@@ -28,5 +28,6 @@ struct ConvTiledP {
                                                     // slab's weights is then a copy instead of 9 N 16 splits per block
 };
 
+int svl_conv3x3_tiled_path();    // SVL_PATH_BF16X (mode 6, unless SVL_CONV_TILED_NO_EMU) or SVL_PATH_F32: the pipe the tiled kernels run on
 bool svl_conv3x3_tiled_eligible(const ConvTiledP& p);
 int svl_conv3x3_tiled_launch(const ConvTiledP& p, hipStream_t st, int* tiles_per_img = nullptr);

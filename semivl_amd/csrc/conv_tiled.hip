@@ -1015,6 +1015,11 @@ extern "C" int svl_conv3x3_weight_planes(const float* w, int N, int Ct, void* pl
   return SVL_OK;
 }
 
+// mode 6 runs the tiled kernels on the split pipe unless SVL_CONV_TILED_NO_EMU is set (the value svl_last_gemm_path reports)
+int svl_conv3x3_tiled_path() {
+  return svl_switch(SVL_SW_CONV_TILED_EMU) && svl_get_gemm_emulation() == 6 ? SVL_PATH_BF16X : SVL_PATH_F32;
+}
+
 bool svl_conv3x3_tiled_eligible(const ConvTiledP& p) {
   auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   if (!(p.N == 32 || p.N == 64)) return false;
@@ -1030,8 +1035,7 @@ int svl_conv3x3_tiled_launch(const ConvTiledP& p, hipStream_t st, int* tiles_per
   if (tiles_per_img) *tiles_per_img = tx * ty;
   const long blocks = (long)p.imgs * tx * ty;
   SVL_CHECK_ARG(blocks < (1L << 31), "svl_conv3x3_tiled: grid too large");
-  static const int emu_ok = getenv("SVL_CONV_TILED_NO_EMU") ? 0 : 1;
-  if (emu_ok && svl_get_gemm_emulation() == 6) {   // the split emulation covers the narrow convolutions too
+  if (svl_conv3x3_tiled_path() == SVL_PATH_BF16X) {   // the split emulation covers the narrow convolutions too
     const bool wpre = p.w_planes != nullptr;     // planes given: the fp16 x 2 kernel; else the bf16 x 3 kernel splits the fp32 weights per block
     // persistent blocks: two per CU (the LDS image allows two), each walking tiles b, b + grid, ...
     static const long resident = [] {
@@ -1086,6 +1090,7 @@ extern "C" int svl_conv3x3_gn_f32(const float* src1, int64_t ld1, int C1, const 
   int tiles = 0;
   const int rc = svl_conv3x3_tiled_launch(t, st, &tiles);
   if (rc != SVL_OK) return rc;
+  svl_set_last_gemm_path(svl_conv3x3_tiled_path());
   const int G = N / 16;
   const long count = (long)imgs * G;
   hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, ws, tiles, G,
@@ -1128,8 +1133,7 @@ extern "C" int svl_conv3x3_dgrad_gnb_f32(const float* dy, int64_t lddy, int C1, 
                                          svl_stream_t stream) {
   SVL_CHECK_ARG(dy && w && out && gnb_x && gnb_table && gnb_stats && ws && chan_sums && imgs > 0 && N % 16 == 0,
                 "svl_conv3x3_dgrad_gnb_f32: bad args");
-  static const int emu_ok = getenv("SVL_CONV_TILED_NO_EMU") ? 0 : 1;
-  if (!emu_ok || svl_get_gemm_emulation() != 6) return SVL_ERR_UNSUPPORTED;      // (epilogue of the split kernel only)
+  if (svl_conv3x3_tiled_path() != SVL_PATH_BF16X) return SVL_ERR_UNSUPPORTED;      // (epilogue of the split kernel only)
   ConvTiledP t;
   t.src1 = dy; t.ld1 = lddy; t.C1 = C1; t.src2 = nullptr; t.ld2 = 0; t.C2 = 0; t.rep = 1;
   t.w = w; t.K = 9 * C1; t.out = out; t.ldo = ldo; t.bias = nullptr; t.act = SVL_ACT_NONE; t.accumulate = accumulate;
@@ -1642,7 +1646,7 @@ extern "C" int svl_conv3x3_wgrad_tiled_groups(int imgs, int H, int W, int Ct, in
   long g = (Co > 32 ? 512 : 768) / (nslab < 1 ? 1 : nslab);
   // the bf16 x 6 kernel: twelve-wave blocks with double-buffered LDS, ONE block per CU -> one round of 256 blocks (any
   // value is valid for either kernel; the arithmetic switch is only read here to size the grid well)
-  if (svl_get_gemm_emulation() == 6 && !getenv("SVL_CONV_TILED_NO_EMU")) {
+  if (svl_conv3x3_tiled_path() == SVL_PATH_BF16X) {
     if (Co == 32 && Ct % 64 == 0) g = 256 / (Ct / 64);
     if (Co == 32 && Ct == 32) g = 512;               // <1, 1, 2>: 256 blocks, each leaves two slabs
     if (Co == 64) g = 256 / (nslab < 1 ? 1 : nslab);
@@ -1658,8 +1662,7 @@ extern "C" int svl_conv3x3_wgrad_tiled(const float* dy, int64_t lddy, int Co, co
                                        const float* src2, int64_t ld2, int C2, int rep, int imgs, int H, int W,
                                        float* slabs, int groups, const float* gn_in, svl_stream_t stream) {
   auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  static const int emu_ok = getenv("SVL_CONV_TILED_NO_EMU") ? 0 : 1;
-  const bool emu6 = emu_ok && svl_get_gemm_emulation() == 6;
+  const bool emu6 = svl_conv3x3_tiled_path() == SVL_PATH_BF16X;
   // Co = 128 exists on the bf16 x 6 kernel only (two blocks of 64 output channels per patch group)
   SVL_CHECK_ARG(dy && src1 && slabs && (Co == 32 || Co == 64 || (Co == 128 && emu6)) && C1 > 0 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 &&
                     (C1 + C2) % 32 == 0 &&
@@ -1675,6 +1678,7 @@ extern "C" int svl_conv3x3_wgrad_tiled(const float* dy, int64_t lddy, int Co, co
   const int tx = (W + PW - 1) / PW, ty = (H + PH - 1) / PH;
   dim3 grid((unsigned)groups, (unsigned)(Ct / 32));
   hipStream_t st = (hipStream_t)stream;
+  bool split = true;    // which pipe the chosen kernel runs on (svl_last_gemm_path)
   if (emu6 && Co == 32 && Ct == 32 && groups >= 2 && groups % 2 == 0 && H >= 2 * WPH) {
     const int ty8 = (H + 2 * WPH - 1) / (2 * WPH);
     hipLaunchKernelGGL((conv3x3_wgrad_tiled_h2_kernel<1, 1, 2>), dim3((unsigned)(groups / 2), 1u), dim3(768), 0, st, p, tx, ty8);
@@ -1682,8 +1686,12 @@ extern "C" int svl_conv3x3_wgrad_tiled(const float* dy, int64_t lddy, int Co, co
     const int ty4 = (H + WPH - 1) / WPH;
     if (Co == 32) hipLaunchKernelGGL((conv3x3_wgrad_tiled_h2_kernel<1, 2>), dim3((unsigned)groups, (unsigned)(Ct / 64)), dim3(768), 0, st, p, tx, ty4);
     else hipLaunchKernelGGL((conv3x3_wgrad_tiled_h2_kernel<2, 1>), dim3((unsigned)groups, (unsigned)(Ct / 32), (unsigned)(Co / 64)), dim3(768), 0, st, p, tx, ty4);
-  } else if (Co == 32) hipLaunchKernelGGL((conv3x3_wgrad_tiled_kernel<1, 32>), grid, dim3(256), 0, st, p, tx, ty);
-  else hipLaunchKernelGGL((conv3x3_wgrad_tiled_kernel<2, 32>), grid, dim3(256), 0, st, p, tx, ty);
+  } else {
+    split = false;
+    if (Co == 32) hipLaunchKernelGGL((conv3x3_wgrad_tiled_kernel<1, 32>), grid, dim3(256), 0, st, p, tx, ty);
+    else hipLaunchKernelGGL((conv3x3_wgrad_tiled_kernel<2, 32>), grid, dim3(256), 0, st, p, tx, ty);
+  }
+  svl_set_last_gemm_path(split ? SVL_PATH_BF16X : SVL_PATH_F32);
   SVL_LAUNCH_CHECK("svl_conv3x3_wgrad_tiled");
   return SVL_OK;
 }

@@ -1508,25 +1508,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   gemm_epilogue<TM, TN, WTM, WTN>(p, acc, m0, n0, wr, wc, l31, hi, zo, zi);
 }
 
-// Process-wide configuration switches (include/semivl_hip.h): relaxed atomics, read once per entry-point call; the
-// environment seeds them on first use.  They select between kernels computing the same function, never touch device
-// state, and are the only mutable globals of the library besides the per-(device, stream) helper contexts (api.hip).
+// Process-wide arithmetic mode (include/semivl_hip.h): a relaxed atomic, read once per entry-point call; the environment seeds
+// it on first use.  With the A/B switches (svl_switches(), api.hip) it selects between kernels computing the same function,
+// never touches device state, and is the only mutable global of the library besides the per-(device, stream) helper contexts.
 static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
-static std::atomic<int> g_band{-1};
-static int svl_band_n(int tiles_n) {
-  int band = g_band.load(std::memory_order_relaxed);
-  if (band < 0) {
-    band = 8;
-    if (band < 0) band = 0;
-    g_band.store(band, std::memory_order_relaxed);
-  }
-  return (band <= 0 || tiles_n <= band) ? tiles_n : band;
-}
-static std::atomic<int> g_conv_tiled{-1};  // -1: read SVL_CONV_NO_TILED once
+static int svl_band_n(int tiles_n) { return tiles_n <= 8 ? tiles_n : 8; }   // column tiles per band (tile_to_mn)
 static std::atomic<int> g_emu_mode{-1};    // -1: read SVL_GEMM_EMU once; 0 exact fp32 MFMA; 3 / 6: bf16 split emulation
-static std::atomic<int> g_ragged_fork{-1};
 // which kernel family served the calling thread's last svl_gemm_f32 (svl_last_gemm_path: measurement aid of bench.py)
-enum { SVL_PATH_F32 = 0, SVL_PATH_BF16X = 1, SVL_PATH_SHORTK = 2, SVL_PATH_ELTWISE = 3, SVL_PATH_H2X = 4 };
 static thread_local int g_last_path = 0;
 // hipFuncSetAttribute is per device: one bit per device ordinal and kernel instantiation
 // (the bit is set only AFTER the attribute call succeeded: attr_done)
@@ -1604,14 +1592,22 @@ int launch_cfg(const GemmP& p, int batch, hipStream_t st) {
 }
 
 // Tile choice: wide-N problems use 128x128; narrow N gets 128x64 / 128x32; short-M (wgrad) gets 32x128 / 64x128.
-template <int AMODE, int BMODE>
-int launch_mode(const GemmP& p, int batch, hipStream_t st) {
+// (the route reports it, launch_mode instantiates it)
+inline void exact_tile(int M, int N, int* bm, int* bn) {
   // short-M problems (conv / linear wgrad with few output channels): widen the wave tile along N so that each
   // A fragment read feeds 2-4 MFMAs (32x32 wave tiles spend one LDS read per MFMA operand).
-  if (p.M <= 32 && p.N > 32) return launch_cfg<32, 128, 1, 4, AMODE, BMODE>(p, batch, st);
-  if (p.M <= 64 && p.N > 64) return launch_cfg<64, 128, 2, 2, AMODE, BMODE>(p, batch, st);
-  if (p.N <= 32) return launch_cfg<128, 32, 4, 1, AMODE, BMODE>(p, batch, st);
-  if (p.N <= 64) return launch_cfg<128, 64, 2, 2, AMODE, BMODE>(p, batch, st);
+  if (M <= 32 && N > 32) { *bm = 32; *bn = 128; }
+  else if (M <= 64 && N > 64) { *bm = 64; *bn = 128; }
+  else { *bm = 128; *bn = N <= 32 ? 32 : (N <= 64 ? 64 : 128); }
+}
+template <int AMODE, int BMODE>
+int launch_mode(const GemmP& p, int batch, hipStream_t st) {
+  int bm, bn;
+  exact_tile(p.M, p.N, &bm, &bn);
+  if (bm == 32) return launch_cfg<32, 128, 1, 4, AMODE, BMODE>(p, batch, st);
+  if (bm == 64) return launch_cfg<64, 128, 2, 2, AMODE, BMODE>(p, batch, st);
+  if (bn == 32) return launch_cfg<128, 32, 4, 1, AMODE, BMODE>(p, batch, st);
+  if (bn == 64) return launch_cfg<128, 64, 2, 2, AMODE, BMODE>(p, batch, st);
   // (measured and rejected on this workload: BK = 32 variants -- occupancy 3 -> 2 blocks/CU, -10 %; 128x256 tiles;
   //  256x32 / 256x64 tiles for the narrow convs: -8 ... -25 %)
   return launch_cfg<128, 128, 2, 2, AMODE, BMODE>(p, batch, st);
@@ -1659,6 +1655,7 @@ int launch_shortk(const GemmP& p, bool fast, hipStream_t st) {
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool is_b_producer(int bm) { return bm == SVL_B_NC_GELU || bm == SVL_B_NC_LN || bm == SVL_B_PATCHT; }
 
 // largest |x| of a strided block into *out (atomicMax: the caller zeroes it)
 std::atomic<long> g_absmax_launches{0};   // operand-maximum passes launched so far (svl_absmax_launches: introspection for tests)
@@ -1723,7 +1720,9 @@ int svl_gemm_part_emu2(int h2, const GemmP& p, int a_rm, int b_rm, int batch, hi
 }
 #else   // part 0: the C-ABI
 
-extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
+// ---------------------------------------------------------------------------------------------------------- validation
+// Checks the descriptor and fills the kernels' parameter block (vector-load eligibility included).  Nothing is launched.
+static int gemm_fill(const svl_gemm_desc* d, GemmP* out) {
   SVL_CHECK_ARG(d != nullptr, "svl_gemm_f32: null desc");
   SVL_CHECK_ARG(d->M > 0 && d->N > 0 && d->K >= 0, "svl_gemm_f32: bad sizes M=%d N=%d K=%d", d->M, d->N, d->K);
   SVL_CHECK_ARG(d->batch >= 1 && d->batch_inner >= 1, "svl_gemm_f32: bad batch %d/%d", d->batch, d->batch_inner);
@@ -1731,8 +1730,7 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
   SVL_CHECK_ARG(d->batch <= 65535, "svl_gemm_f32: batch %d > 65535", d->batch);
   if (d->ksplit > 0)
     SVL_CHECK_ARG((long)d->ksplit * d->batch >= d->K, "svl_gemm_f32: ksplit*batch < K");
-  hipStream_t st = (hipStream_t)stream;
-  GemmP p;
+  GemmP& p = *out;
   memset(&p, 0, sizeof(p));
   p.M = d->M; p.N = d->N; p.K = d->K;
   p.batch_inner = d->batch_inner; p.ksplit = d->ksplit;
@@ -1785,8 +1783,7 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     p.A.vec = dense_vec(d->A);
   }
   p.B.vec = b_conv ? conv_vec(d->B) : dense_vec(d->B);
-  const bool b_prod = d->b_mode == SVL_B_NC_GELU || d->b_mode == SVL_B_NC_LN || d->b_mode == SVL_B_PATCHT;
-  if (b_prod) {
+  if (is_b_producer(d->b_mode)) {
     SVL_CHECK_ARG(d->a_mode == SVL_A_MCONTIG && d->out_mode == SVL_OUT_STRIDED && (d->batch == 1 || d->ksplit > 0),
                   "svl_gemm_f32: B producers need A = SVL_A_MCONTIG, a strided output and no operand batch");
     p.b_stats = d->b_stats; p.b_gamma = d->b_gamma; p.b_beta = d->b_beta;
@@ -1812,154 +1809,197 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     svl_set_error("svl_gemm_f32: resid is not supported with SVL_OUT_CONVT2X");
     return SVL_ERR_UNSUPPORTED;
   }
+  return SVL_OK;
+}
 
+// ------------------------------------------------------------------------------------------------------------- routing
+// Which kernel serves a launch, as data.  gemm_route() is host arithmetic on the descriptor, its parameter block, the
+// arithmetic mode and the switches: no HIP call, no global written.  gemm_execute() runs a route; svl_gemm_route() reports it.
+enum GemmFamily {
+  FAM_EXACT_DENSE, FAM_EXACT_CONV,         // exact fp32 kernel (parts 1 / 2)
+  FAM_BF16X3, FAM_BF16X2, FAM_H2X2,        // in-register split kernel: three / two bf16 terms, two fp16 terms + tensor scales
+  FAM_SHORTK, FAM_SHORTK_X6,               // short-K row stream on the fp32 / the split pipe
+  FAM_CIN1, FAM_TILED3X3, FAM_DIL3X3       // elementwise Conv2d(1 -> N), tiled narrow 3x3, whole-image dilated 3x3
+};
+struct MaxPass {       // one operand-maximum pass over a strided block into word `word` of emu_ws
+  const float* x;      // null: the producer's transformed B operand (absmax_bx_launch)
+  long rows, cols, ld;
+  int word;
+};
+struct PartRoute {     // one launch of the exact or the in-register split kernel
+  int family, path;
+  int a_rm, b_rm;      // split kernel: operand layouts
+  int npass;           // FAM_H2X2: its maximum passes, and the maxima the caller holds instead (a_amax / b_amax)
+  MaxPass pass[3];
+  const unsigned *take_a, *take_b;
+};
+struct GemmRoute {
+  int family, path;    // of the launch as a whole (a ragged launch: of its 128-aligned part)
+  bool sk_fast;        // FAM_SHORTK: whole-row store epilogue
+  int m_main;          // > 0: ragged fork, rows [0, m_main) are part[0], the leftover rows part[1] on the helper stream
+  PartRoute part[2];
+};
+
+static ShortKP shortk_x6_params(const svl_gemm_desc* d) {
+  ShortKP q;
+  q.A = d->A.ptr; q.lda = d->A.ld; q.B = d->B.ptr; q.ldb = d->B.ld; q.C = d->C; q.ldc_m = d->ldc_m;
+  q.M = d->M; q.N = d->N; q.K = d->K; q.out_mode = d->out_mode; q.ct_H = d->ct_H; q.ct_W = d->ct_W;
+  q.ct_Cout = d->ct_Cout; q.alpha = d->alpha; q.bias = d->bias; q.bias_mod = d->bias_mod; q.act = d->act;
+  return q;
+}
+static ConvTiledP tiled_params(const svl_gemm_desc* d) {
+  const svl_conv_geom& cv = d->conv;
+  ConvTiledP t;
+  t.src1 = d->A.ptr; t.ld1 = d->A.ld; t.C1 = cv.C1;
+  t.src2 = cv.src2; t.ld2 = cv.ld2; t.C2 = cv.C2; t.rep = cv.rep;
+  t.w = d->B.ptr; t.K = d->K;
+  t.out = d->C; t.ldo = d->ldc_m;
+  t.bias = d->bias_mod > 0 ? nullptr : d->bias; t.act = d->act; t.accumulate = d->accumulate;
+  t.imgs = (int)((long)d->M / ((long)cv.H * cv.W)); t.H = cv.H; t.W = cv.W; t.N = d->N;
+  t.sign = cv.sign;
+  t.gn_part = nullptr;
+  t.gn_in = nullptr;
+  t.gnb_x = t.gnb_table = t.gnb_stats = nullptr;
+  t.gnb_part = nullptr;
+  t.w_planes = d->conv_w_planes;
+  return t;
+}
+static ConvDilP dil_params(const svl_gemm_desc* d) {
+  const svl_conv_geom& cv = d->conv;
+  ConvDilP t;
+  t.src = d->A.ptr; t.ld = d->A.ld; t.C = cv.C1;
+  t.out = d->C; t.ldo = d->ldc_m;
+  t.imgs = (int)((long)d->M / ((long)cv.H * cv.W)); t.H = cv.H; t.W = cv.W; t.N = d->N;
+  t.dil = cv.dil; t.sign = cv.sign; t.accumulate = d->accumulate;
+  t.w_planes = d->conv_w_planes;
+  return t;
+}
+// the two parts of a ragged launch: rows [0, m_main) and the leftover rows
+static void ragged_parts(const GemmP& p, int m_main, GemmP* mainp, GemmP* rem) {
+  *mainp = *rem = p;
+  mainp->M = m_main;
+  rem->M = p.M - m_main;
+  rem->A.p = p.A.p + (long)m_main * p.A.ld;
+  rem->C = p.C + (long)m_main * p.ldc_m;
+  if (p.preact) rem->preact = p.preact + (long)m_main * p.ldc_m;
+  if (p.resid) rem->resid = p.resid + (long)m_main * p.ldr_m;
+  rem->A.vec = p.A.vec && aligned16(rem->A.p);
+}
+
+// One launch of the exact or the in-register split kernel.  The exact kernel takes every supported mode pair.  In modes 3 / 6
+// four kinds of launch join the split kernel above their thresholds; each case below only DESCRIBES its operands (layouts,
+// the elements a maximum pass would read, the passes themselves), the decision that follows is one.
+static int route_part(const svl_gemm_desc* d, const GemmP& q, int emu_mode, int sw, PartRoute* r) {
   const int am = d->a_mode, bm = d->b_mode;
-  int emu_mode = g_emu_mode.load(std::memory_order_relaxed);
-  if (emu_mode < 0) {
-    emu_mode = env_int("SVL_GEMM_EMU", 0);
-    g_emu_mode.store(emu_mode, std::memory_order_relaxed);
-  }
-  g_last_path = SVL_PATH_F32;
-  // fp16 x 2 form of the in-register split kernel (round 5): three products instead of six, one power-of-two scale per operand
-  // TENSOR found by a maximum pass over exactly the elements the launch reads (d->emu_ws: 8 bytes of device scratch private to
-  // this call; without it, or for launches too small to pay for the two extra passes, the bf16 x 3 form serves the launch).
-  static const int h2_on = getenv("SVL_GEMM_EMU_NO_H2") ? 0 : 1;
-  unsigned* h2_ws = static_cast<unsigned*>(d->emu_ws);
-  const unsigned* a_amax = d->a_amax;
-  const unsigned* b_amax = d->b_amax;
-  // Worth it when the halved matrix work outweighs the two maximum passes: measured, the fp16 x 2 form runs at ~240 TF where
-  // the bf16 x 3 form runs at ~170 (1.7e-15 s saved per FLOP) and a maximum pass reads at ~4 TB/s (x 1.2 for its launch) --
-  // the K = 128 pixel-wise layers and the 1 x 1 weight gradients lose, the dilated 3 x 3 layers and the ViT's split-K weight
-  // gradients gain.  `elems` = operand elements the two passes read.
-  auto h2_ok = [&](const GemmP& q, double elems) {
-    const double flops = 2.0 * q.M * q.N * q.K;
-    return emu_mode == 6 && h2_on && h2_ws != nullptr && flops >= 4.0e9 && flops * 1.7e-15 > elems * 4.0 / 4.0e12 * 1.2;
-  };
-  auto h2_begin = [&]() -> int {
-    SVL_HIP_CHECK(hipMemsetAsync(h2_ws, 0, 8, st));
-    return SVL_OK;
-  };
-  auto launch = [&](const GemmP& q) -> int {
-    // B-operand producers of the ViT weight gradients (dY^T @ f(X)): the dense thresholds of the split emulation
-    if (b_prod) {
-      if ((emu_mode == 3 || emu_mode == 6) && q.M >= 256 && q.N >= 96 && q.K >= 64) {
-        g_last_path = SVL_PATH_BF16X;
-        const double b_elems = bm == SVL_B_PATCHT ? (double)q.K * q.cv.patch * q.cv.patch * q.cv.C1 : (double)q.N * q.K;
-        const double elems = (double)q.M * q.K + b_elems;
-        if (h2_ok(q, elems) && 2.0 * q.M * q.N * q.K * 1.7e-15 > elems * 4.0 / 4.0e12 * 1.5) {
-          // (a_amax / b_amax: a maximum the caller already holds replaces its pass; the producers' transformed operands
-          //  -- absmax_bx_launch -- always take theirs)
-          const unsigned* b_have = bm == SVL_B_PATCHT ? b_amax : nullptr;
-          int rc = h2_begin();
-          if (!rc && !a_amax) rc = absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st);
-          if (!rc && (a_amax || b_have)) rc = amax_take(a_amax, b_have, h2_ws, st);
-          if (!rc && !b_have) {
-            if (bm == SVL_B_PATCHT) {   // the zero fill adds only zeros: the image's own maximum is the operand's
-              const int P = q.cv.patch;
-              const long imgs = q.K / ((long)((q.cv.H + P - 1) / P) * ((q.cv.W + P - 1) / P));
-              rc = absmax_launch(q.B.p, imgs * q.cv.C1 * q.cv.H, q.cv.W, q.cv.W, h2_ws + 1, st);
-            } else {
-              rc = absmax_bx_launch(q, bm, h2_ws + 1, st);
-            }
-          }
-          if (rc) return rc;
-          GemmP q2 = q;
-          q2.amax = h2_ws;
-          g_last_path = SVL_PATH_H2X;
-          return svl_gemm_part_emu2(1, q2, 1, bm, d->batch, st);
-        }
-        return emu_mode == 6 ? svl_gemm_part_emu3(q, 1, bm, d->batch, st) : svl_gemm_part_emu2(0, q, 1, bm, d->batch, st);
-      }
-      return bm == SVL_B_PATCHT ? svl_gemm_part_mode_conv(am, bm, q, d->batch, st)
-                                : svl_gemm_part_mode_dense(am, bm, q, d->batch, st);
-    }
-    // implicit-GEMM convolutions (NHWC im2col on the fly, forward and mirrored-tap input gradient) join the split
-    // emulation when every 4-k piece stays inside one tap (channels % 4) and K is a whole number of 16-deep steps
-    if ((emu_mode == 3 || emu_mode == 6) && am == SVL_A_CONV && bm == SVL_B_KCONTIG && d->out_mode == SVL_OUT_STRIDED &&
-        d->batch == 1 && d->ksplit == 0 && q.M >= 256 && q.N >= 96 && q.K >= 64 && (q.K % 16) == 0 && q.A.vec && q.B.vec) {
-      g_last_path = SVL_PATH_BF16X;
-      const long px = (long)(q.M / (q.cv.Ho * q.cv.Wo)) * q.cv.H * q.cv.W;
-      if (h2_ok(q, (double)px * q.cv.C1 + (q.cv.C2 > 0 ? (double)(px / q.cv.rep) * q.cv.C2 : 0.0) + (double)q.N * q.K)) {
-        // operands: the NHWC source(s) of the implicit im2col, the [N, K] weights
-        int rc = h2_begin();
-        if (!rc) rc = absmax_launch(q.A.p, px, q.cv.C1, q.A.ld, h2_ws, st);
-        if (!rc && q.cv.C2 > 0) rc = absmax_launch(q.cv.src2, px / q.cv.rep, q.cv.C2, q.cv.ld2, h2_ws, st);
-        if (!rc) rc = absmax_launch(q.B.p, q.N, q.K, q.B.ld, h2_ws + 1, st);
-        if (rc) return rc;
-        GemmP q2 = q;
-        q2.amax = h2_ws;
-        g_last_path = SVL_PATH_H2X;
-        return svl_gemm_part_emu2(1, q2, 2, 0, 1, st);
-      }
-      return emu_mode == 6 ? svl_gemm_part_emu3(q, 2, 0, 1, st) : svl_gemm_part_emu2(0, q, 2, 0, 1, st);
-    }
-    // weight gradients of the implicit-GEMM convolutions (A = dy^T, B = im2col(x)^T, split-K over the pixels): the
-    // dilated / 1x1 / transposed-conv layers of the decoder.  One 128-row tile holds all of Cout = 128 (Cout = 64 wastes half of
-    // every tile: measured slower than the fp32 kernel's 64-row tiles, 46 vs 53 TF, and left there); a thread's 8 consecutive k must be pixels of one image row.
-    if ((emu_mode == 3 || emu_mode == 6) && am == SVL_A_MCONTIG && bm == SVL_B_CONVW && d->out_mode == SVL_OUT_STRIDED &&
-        q.M >= 96 && q.N >= 96 && q.K >= 1024 && (q.K % 16) == 0 && (d->ksplit % 16) == 0 && (q.cv.Wo % 8) == 0 &&
-        q.A.vec && q.B.vec) {
-      g_last_path = SVL_PATH_BF16X;
-      const long px = (long)(q.K / (q.cv.Ho * q.cv.Wo)) * q.cv.H * q.cv.W;
-      if ((d->batch == 1 || d->ksplit > 0) &&
-          h2_ok(q, (double)q.K * q.M + (double)px * q.cv.C1 + (q.cv.C2 > 0 ? (double)(px / q.cv.rep) * q.cv.C2 : 0.0))) {
-        // operands: dy^T [K pixels, M], the NHWC source(s) of im2col(x)^T
-        int rc = h2_begin();
-        if (!rc) rc = absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st);
-        if (!rc) rc = absmax_launch(q.B.p, px, q.cv.C1, q.B.ld, h2_ws + 1, st);
-        if (!rc && q.cv.C2 > 0) rc = absmax_launch(q.cv.src2, px / q.cv.rep, q.cv.C2, q.cv.ld2, h2_ws + 1, st);
-        if (rc) return rc;
-        GemmP q2 = q;
-        q2.amax = h2_ws;
-        g_last_path = SVL_PATH_H2X;
-        return svl_gemm_part_emu2(1, q2, 1, 2, d->batch, st);
-      }
-      return emu_mode == 6 ? svl_gemm_part_emu3(q, 1, 2, d->batch, st) : svl_gemm_part_emu2(0, q, 1, 2, d->batch, st);
-    }
-    // (the pixel-shuffle store of ConvTranspose2d(k 2, s 2) stays with the short-K stream kernel, whose epilogue writes
-    //  whole rows: through this kernel's 32 x 32 accumulator layout the K = 128 ConvTranspose of up1 ran at 31 TF, 88 there)
-    if ((emu_mode == 3 || emu_mode == 6) && (am == SVL_A_KCONTIG || am == SVL_A_MCONTIG) &&
-        (bm == SVL_B_KCONTIG || bm == SVL_B_NCONTIG) && d->out_mode == SVL_OUT_STRIDED && q.M >= 256 && q.N >= 96 &&
-        q.K >= 64) {
-      g_last_path = SVL_PATH_BF16X;
-      // Dense launches (the ViT's split-K weight gradients): round 5 measured +17 % on in_proj (2304 x 768 x 32800) and -9 % on
-      // out_proj (768 x 768: the two maximum passes weigh three times as much per FLOP) with the form on for both, and left
-      // it opt-in.  Round 6: on by default for the launches whose halved matrix work outweighs the passes by 1.5 x (in_proj
-      // only at the ViT's shapes): 323.7 -> 319.8 ms per VOC step with both on, same call; the float64 comparison of the
-      // full-size step passes with it (tests/test_fullsize_gpu.py, FP64_RATCHET).
-      const double dense_elems = (double)q.M * q.K + (double)q.N * q.K;
-      if ((d->batch == 1 || d->ksplit > 0) && h2_ok(q, dense_elems) &&
-          2.0 * q.M * q.N * q.K * 1.7e-15 > dense_elems * 4.0 / 4.0e12 * 1.5) {
-        // dense operands: [M, K] or [K, M], [N, K] or [K, N]
-        // (a_amax / b_amax: a maximum the caller already holds -- the pack pass that split the same matrix a moment ago
-        //  left it, svl_split_planes_f16x2 -- replaces that operand's pass over 4 B per element)
-        int rc = (a_amax && b_amax) ? SVL_OK : h2_begin();
-        if (!rc && !a_amax) rc = am == SVL_A_MCONTIG ? absmax_launch(q.A.p, q.K, q.M, q.A.ld, h2_ws, st)
-                                                      : absmax_launch(q.A.p, q.M, q.K, q.A.ld, h2_ws, st);
-        if (!rc && !b_amax) rc = bm == SVL_B_NCONTIG ? absmax_launch(q.B.p, q.K, q.N, q.B.ld, h2_ws + 1, st)
-                                                      : absmax_launch(q.B.p, q.N, q.K, q.B.ld, h2_ws + 1, st);
-        if (!rc && (a_amax || b_amax)) rc = amax_take(a_amax, b_amax, h2_ws, st);
-        if (rc) return rc;
-        GemmP q2 = q;
-        q2.amax = h2_ws;
-        g_last_path = SVL_PATH_H2X;
-        return svl_gemm_part_emu2(1, q2, am == SVL_A_MCONTIG, bm == SVL_B_NCONTIG, d->batch, st);
-      }
-      return emu_mode == 6 ? svl_gemm_part_emu3(q, am == SVL_A_MCONTIG, bm == SVL_B_NCONTIG, d->batch, st)
-                             : svl_gemm_part_emu2(0, q, am == SVL_A_MCONTIG, bm == SVL_B_NCONTIG, d->batch, st);
-    }
-    if ((am == SVL_A_KCONTIG || am == SVL_A_MCONTIG) && (bm == SVL_B_KCONTIG || bm == SVL_B_NCONTIG))
-      return svl_gemm_part_mode_dense(am, bm, q, d->batch, st);
-    if ((am == SVL_A_CONV && bm == SVL_B_KCONTIG) || (am == SVL_A_MCONTIG && bm == SVL_B_CONVW) ||
-        (am == SVL_A_PATCH && bm == SVL_B_KCONTIG))
-      return svl_gemm_part_mode_conv(am, bm, q, d->batch, st);
+  const bool a_dense = am == SVL_A_KCONTIG || am == SVL_A_MCONTIG, b_dense = bm == SVL_B_KCONTIG || bm == SVL_B_NCONTIG;
+  const bool b_prod = is_b_producer(bm), strided = d->out_mode == SVL_OUT_STRIDED;
+  memset(r, 0, sizeof(*r));
+  r->path = SVL_PATH_F32;
+  if (b_prod) r->family = bm == SVL_B_PATCHT ? FAM_EXACT_CONV : FAM_EXACT_DENSE;
+  else if (a_dense && b_dense) r->family = FAM_EXACT_DENSE;
+  else if ((am == SVL_A_CONV && bm == SVL_B_KCONTIG) || (am == SVL_A_MCONTIG && bm == SVL_B_CONVW) ||
+           (am == SVL_A_PATCH && bm == SVL_B_KCONTIG)) r->family = FAM_EXACT_CONV;
+  else {
     svl_set_error("svl_gemm_f32: unsupported mode combination a=%d b=%d", am, bm);
     return SVL_ERR_UNSUPPORTED;
-  };
+  }
+  if (emu_mode != 3 && emu_mode != 6) return SVL_OK;
+
+  const svl_conv_geom& cv = q.cv;
+  const bool big = q.M >= 256 && q.N >= 96 && q.K >= 64;    // the dense thresholds of the split emulation
+  int a_rm, b_rm, np = 0;
+  MaxPass ps[3];
+  const unsigned *take_a = nullptr, *take_b = nullptr;
+  double elems;          // operand elements the maximum passes read
+  bool margin = false;   // the halved matrix work must outweigh the passes by 1.5 x, not 1.2 x (below)
+  if (b_prod && big) {
+    // B-operand producers of the ViT weight gradients (dY^T @ f(X)).  a_amax / b_amax: a maximum the caller already holds
+    // replaces its pass; the producers' transformed operands always take theirs
+    a_rm = 1; b_rm = bm; margin = true;
+    const double b_elems = bm == SVL_B_PATCHT ? (double)q.K * cv.patch * cv.patch * cv.C1 : (double)q.N * q.K;
+    elems = (double)q.M * q.K + b_elems;
+    take_a = d->a_amax;
+    take_b = bm == SVL_B_PATCHT ? d->b_amax : nullptr;
+    if (!take_a) ps[np++] = {q.A.p, q.K, q.M, q.A.ld, 0};
+    if (!take_b) {
+      if (bm == SVL_B_PATCHT) {   // the zero fill adds only zeros: the image's own maximum is the operand's
+        const int P = cv.patch;
+        const long imgs = q.K / ((long)((cv.H + P - 1) / P) * ((cv.W + P - 1) / P));
+        ps[np++] = {q.B.p, imgs * cv.C1 * cv.H, cv.W, cv.W, 1};
+      } else {
+        ps[np++] = {nullptr, 0, 0, 0, 1};
+      }
+    }
+  } else if (am == SVL_A_CONV && bm == SVL_B_KCONTIG && strided && d->batch == 1 && d->ksplit == 0 && big && (q.K % 16) == 0 &&
+             q.A.vec && q.B.vec) {
+    // implicit-GEMM convolutions (NHWC im2col on the fly, forward and mirrored-tap input gradient): every 4-k piece stays
+    // inside one tap (channels % 4) and K is a whole number of 16-deep steps.  Operands: the NHWC source(s), the [N, K] weights
+    a_rm = 2; b_rm = 0;
+    const long px = (long)(q.M / (cv.Ho * cv.Wo)) * cv.H * cv.W;
+    elems = (double)px * cv.C1 + (cv.C2 > 0 ? (double)(px / cv.rep) * cv.C2 : 0.0) + (double)q.N * q.K;
+    ps[np++] = {q.A.p, px, cv.C1, q.A.ld, 0};
+    if (cv.C2 > 0) ps[np++] = {cv.src2, px / cv.rep, cv.C2, cv.ld2, 0};
+    ps[np++] = {q.B.p, q.N, q.K, q.B.ld, 1};
+  } else if (am == SVL_A_MCONTIG && bm == SVL_B_CONVW && strided && q.M >= 96 && q.N >= 96 && q.K >= 1024 && (q.K % 16) == 0 &&
+             (d->ksplit % 16) == 0 && (cv.Wo % 8) == 0 && q.A.vec && q.B.vec) {
+    // weight gradients of the implicit-GEMM convolutions (A = dy^T, B = im2col(x)^T, split-K over the pixels): the dilated /
+    // 1x1 / transposed-conv layers of the decoder.  One 128-row tile holds all of Cout = 128 (Cout = 64 wastes half of every
+    // tile: measured slower than the fp32 kernel's 64-row tiles, 46 vs 53 TF, and left there); a thread's 8 consecutive k
+    // must be pixels of one image row.  Operands: dy^T [K pixels, M], the NHWC source(s) of im2col(x)^T
+    a_rm = 1; b_rm = 2;
+    const long px = (long)(q.K / (cv.Ho * cv.Wo)) * cv.H * cv.W;
+    elems = (double)q.K * q.M + (double)px * cv.C1 + (cv.C2 > 0 ? (double)(px / cv.rep) * cv.C2 : 0.0);
+    ps[np++] = {q.A.p, q.K, q.M, q.A.ld, 0};
+    ps[np++] = {q.B.p, px, cv.C1, q.B.ld, 1};
+    if (cv.C2 > 0) ps[np++] = {cv.src2, px / cv.rep, cv.C2, cv.ld2, 1};
+  } else if (a_dense && b_dense && strided && big) {
+    // dense operands [M, K] or [K, M], [N, K] or [K, N] (the ViT's split-K weight gradients among them).  a_amax / b_amax: a
+    // maximum the caller already holds -- the pack pass that split the same matrix a moment ago left it,
+    // svl_split_planes_f16x2 -- replaces that operand's pass over 4 B per element.
+    // (the pixel-shuffle store of ConvTranspose2d(k 2, s 2) stays with the short-K stream kernel, whose epilogue writes
+    //  whole rows: through this kernel's 32 x 32 accumulator layout the K = 128 ConvTranspose of up1 ran at 31 TF, 88 there)
+    a_rm = am == SVL_A_MCONTIG; b_rm = bm == SVL_B_NCONTIG; margin = true;
+    elems = (double)q.M * q.K + (double)q.N * q.K;
+    take_a = d->a_amax;
+    take_b = d->b_amax;
+    if (!take_a) ps[np++] = a_rm ? MaxPass{q.A.p, q.K, q.M, q.A.ld, 0} : MaxPass{q.A.p, q.M, q.K, q.A.ld, 0};
+    if (!take_b) ps[np++] = b_rm ? MaxPass{q.B.p, q.K, q.N, q.B.ld, 1} : MaxPass{q.B.p, q.N, q.K, q.B.ld, 1};
+  } else {
+    return SVL_OK;
+  }
+  r->family = emu_mode == 6 ? FAM_BF16X3 : FAM_BF16X2;
+  r->path = SVL_PATH_BF16X;
+  r->a_rm = a_rm; r->b_rm = b_rm;
+  // fp16 x 2 form (round 5): three products instead of six, one power-of-two scale per operand TENSOR found by a maximum pass
+  // over exactly the elements the launch reads (d->emu_ws: 8 bytes of device scratch private to this call).  Worth it when
+  // the halved matrix work outweighs the passes: measured, the fp16 x 2 form runs at ~240 TF where the bf16 x 3 form runs at
+  // ~170 (1.7e-15 s saved per FLOP) and a maximum pass reads at ~4 TB/s (x 1.2 for its launch) -- the K = 128 pixel-wise
+  // layers and the 1 x 1 weight gradients lose, the dilated 3 x 3 layers and the ViT's split-K weight gradients gain
+  // (DESIGN.md, round 5).  Dense and producer launches ask for 1.5 x: round 5 measured +17 % on in_proj (2304 x 768 x 32800)
+  // and -9 % on out_proj (768 x 768: the passes weigh three times as much per FLOP) with the form on for both; with the margin
+  // it serves in_proj only at the ViT's shapes (323.7 -> 319.8 ms per VOC step; tests/test_fullsize_gpu.py, FP64_RATCHET).
+  const double flops = 2.0 * q.M * q.N * q.K;
+  auto worth = [&](double factor) { return flops * 1.7e-15 > elems * 4.0 / 4.0e12 * factor; };
+  if (emu_mode == 6 && (sw & SVL_SW_EMU_H2) && d->emu_ws != nullptr && (d->batch == 1 || d->ksplit > 0) && flops >= 4.0e9 &&
+      worth(1.2) && (!margin || worth(1.5))) {
+    r->family = FAM_H2X2;
+    r->path = SVL_PATH_H2X;
+    r->npass = np;
+    for (int i = 0; i < np; ++i) r->pass[i] = ps[i];
+    r->take_a = take_a; r->take_b = take_b;
+  }
+  return SVL_OK;
+}
+
+static int gemm_route(const svl_gemm_desc* d, const GemmP& p, int emu_mode, int sw, GemmRoute* r) {
+  const int am = d->a_mode, bm = d->b_mode;
+  const svl_conv_geom& cv = d->conv;
+  const bool a_conv = am == SVL_A_CONV, emu = emu_mode == 3 || emu_mode == 6;
+  const bool plain_act = d->act == SVL_ACT_NONE || d->act == SVL_ACT_RELU || d->act == SVL_ACT_GELU;
+  memset(r, 0, sizeof(*r));
 
   // Short-K row streams (per-pixel linears / 1x1 convolutions of the head): dedicated persistent kernel
-  static const int shortk = getenv("SVL_GEMM_NO_SHORTK") ? 0 : 1;   // thread-safe one-time init, immutable afterwards
-  {
+  if (sw & SVL_SW_SHORTK) {
     const bool a_dense = am == SVL_A_KCONTIG ||
                          (a_conv && cv.KH == 1 && cv.KW == 1 && cv.pad == 0 && p.cv.stride == 1 && cv.C2 == 0 &&
                           p.cv.Ho == cv.H && p.cv.Wo == cv.W);
@@ -1967,124 +2007,159 @@ extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
     // projection's input gradient N = 640: 2 N FLOP per operand byte, more matrix- than store-bound) go to the bf16-pipe
     // kernel instead: 94 -> 109 TF and 80 -> 87 TF solo, ADE 24.86 -> 25.40 img/s, VOC 77.50 -> 77.84 in the step (same
     // box, round 4).  K = 64 (ConvTranspose of up2) and the pixel-shuffle stores stay here.
-    const bool sk_to_emu = (emu_mode == 3 || emu_mode == 6) && d->K > 64 && d->out_mode == SVL_OUT_STRIDED;
-    if (shortk && !sk_to_emu && a_dense && bm == SVL_B_KCONTIG && d->batch == 1 && d->ksplit == 0 && d->K % 64 == 0 && d->K >= 64 &&
+    const bool sk_to_emu = emu && d->K > 64 && d->out_mode == SVL_OUT_STRIDED;
+    if (!sk_to_emu && a_dense && bm == SVL_B_KCONTIG && d->batch == 1 && d->ksplit == 0 && d->K % 64 == 0 && d->K >= 64 &&
         d->K <= 128 && d->M >= 32768 && d->N >= 96 && p.A.vec && p.B.vec &&
         (d->out_mode == SVL_OUT_STRIDED || d->out_mode == SVL_OUT_CONVT2X)) {
-      const bool fast = (d->ldc_n == 1 || d->out_mode == SVL_OUT_CONVT2X) && !d->resid && !d->preact && !d->accumulate &&
-                        (d->act == SVL_ACT_NONE || d->act == SVL_ACT_RELU || d->act == SVL_ACT_GELU);
+      r->sk_fast = (d->ldc_n == 1 || d->out_mode == SVL_OUT_CONVT2X) && !d->resid && !d->preact && !d->accumulate && plain_act;
       // the ConvTranspose2d(k 2, s 2) layers (and any K = 64 stream) in emulation mode 6: the same stream structure on
       // the split pipe (gemm_shortk.hip) -- these were the largest launches left on the fp32 matrix pipe
-      if (fast && emu_mode == 6 && (d->out_mode == SVL_OUT_CONVT2X || d->K == 64)) {
-        ShortKP q;
-        q.A = d->A.ptr; q.lda = d->A.ld; q.B = d->B.ptr; q.ldb = d->B.ld; q.C = d->C; q.ldc_m = d->ldc_m;
-        q.M = d->M; q.N = d->N; q.K = d->K; q.out_mode = d->out_mode; q.ct_H = d->ct_H; q.ct_W = d->ct_W;
-        q.ct_Cout = d->ct_Cout; q.alpha = d->alpha; q.bias = d->bias; q.bias_mod = d->bias_mod; q.act = d->act;
-        if (svl_shortk_x6_eligible(q)) {
-          g_last_path = SVL_PATH_BF16X;
-          return svl_shortk_x6_launch(q, st);
-        }
-      }
-      g_last_path = SVL_PATH_SHORTK;
-      return launch_shortk(p, fast, st);
+      const bool x6 = r->sk_fast && emu_mode == 6 && (d->out_mode == SVL_OUT_CONVT2X || d->K == 64) &&
+                      svl_shortk_x6_eligible(shortk_x6_params(d));
+      r->family = x6 ? FAM_SHORTK_X6 : FAM_SHORTK;
+      r->path = x6 ? SVL_PATH_BF16X : SVL_PATH_SHORTK;
+      return SVL_OK;
+    }
+    // Conv2d(1 -> N) forward with a 3x3 kernel: elementwise kernel instead of a K = 9 implicit GEMM
+    if (a_conv && bm == SVL_B_KCONTIG && cv.C1 == 1 && cv.C2 == 0 && d->K == 9 && cv.KH == 3 && p.cv.stride == 1 &&
+        d->batch == 1 && d->ksplit == 0 && d->out_mode == SVL_OUT_STRIDED && d->ldc_n == 1 && !d->resid && !d->preact &&
+        !d->accumulate && d->N % 4 == 0 && 256 % (d->N / 4) == 0 && d->ldc_m % 4 == 0 && aligned16(d->C) && d->M >= 32768 &&
+        plain_act) {
+      r->family = FAM_CIN1;
+      r->path = SVL_PATH_ELTWISE;
+      return SVL_OK;
     }
   }
 
-  // Conv2d(1 -> N) forward with a 3x3 kernel: elementwise kernel instead of a K = 9 implicit GEMM
-  if (shortk && a_conv && bm == SVL_B_KCONTIG && cv.C1 == 1 && cv.C2 == 0 && d->K == 9 && cv.KH == 3 && p.cv.stride == 1 &&
-      d->batch == 1 && d->ksplit == 0 && d->out_mode == SVL_OUT_STRIDED && d->ldc_n == 1 && !d->resid && !d->preact &&
-      !d->accumulate && d->N % 4 == 0 && 256 % (d->N / 4) == 0 && d->ldc_m % 4 == 0 && aligned16(d->C) && d->M >= 32768 &&
-      (d->act == SVL_ACT_NONE || d->act == SVL_ACT_RELU || d->act == SVL_ACT_GELU)) {
-    const int ppb = 256 / (d->N / 4);
-    long blocks = ((long)d->M + ppb - 1) / ppb;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(conv_cin1_fwd_kernel<9>, dim3((unsigned)blocks), dim3(256), 0, st, p);
-    g_last_path = SVL_PATH_ELTWISE;
-    SVL_LAUNCH_CHECK("svl_gemm_f32/conv_cin1");
-    return SVL_OK;
-  }
-
-  // Narrow 3x3 convolutions (N = 32 / 64): spatially tiled kernel (conv_tiled.hip) instead of the implicit GEMM
-  int conv_tiled = g_conv_tiled.load(std::memory_order_relaxed);
-  if (conv_tiled < 0) {
-    conv_tiled = getenv("SVL_CONV_NO_TILED") ? 0 : 1;
-    g_conv_tiled.store(conv_tiled, std::memory_order_relaxed);
-  }
-  if (conv_tiled && am == SVL_A_CONV && bm == SVL_B_KCONTIG && d->out_mode == SVL_OUT_STRIDED && d->batch == 1 &&
-      d->ksplit == 0 && cv.KH == 3 && cv.KW == 3 && cv.dil == 1 && cv.pad == 1 && p.cv.stride == 1 &&
-      d->alpha == 1.0f && !d->preact && !d->resid && d->B.ld == d->K && d->ldc_n == 1 &&
-      (long)d->M % ((long)cv.H * cv.W) == 0) {
-    ConvTiledP t;
-    t.src1 = d->A.ptr; t.ld1 = d->A.ld; t.C1 = cv.C1;
-    t.src2 = cv.src2; t.ld2 = cv.ld2; t.C2 = cv.C2; t.rep = cv.rep;
-    t.w = d->B.ptr; t.K = d->K;
-    t.out = d->C; t.ldo = d->ldc_m;
-    t.bias = d->bias_mod > 0 ? nullptr : d->bias; t.act = d->act; t.accumulate = d->accumulate;
-    t.imgs = (int)((long)d->M / ((long)cv.H * cv.W)); t.H = cv.H; t.W = cv.W; t.N = d->N;
-    t.sign = cv.sign;
-    t.gn_part = nullptr;
-    t.gn_in = nullptr;
-    t.gnb_x = t.gnb_table = t.gnb_stats = nullptr;
-    t.gnb_part = nullptr;
-    t.w_planes = d->conv_w_planes;
-    if ((d->bias == nullptr || d->bias_mod == 0) && svl_conv3x3_tiled_eligible(t)) {
-      static const int temu = getenv("SVL_CONV_TILED_NO_EMU") ? 0 : 1;
-      g_last_path = (temu && emu_mode == 6) ? SVL_PATH_BF16X : SVL_PATH_F32;
-      return svl_conv3x3_tiled_launch(t, st);
+  // 3x3 / stride 1 convolutions with kernels of their own (conv_tiled.hip, conv_dil.hip) instead of the implicit GEMM
+  if ((sw & SVL_SW_CONV_TILED) && a_conv && bm == SVL_B_KCONTIG && d->out_mode == SVL_OUT_STRIDED && d->batch == 1 &&
+      d->ksplit == 0 && cv.KH == 3 && cv.KW == 3 && p.cv.stride == 1 && d->alpha == 1.0f && !d->preact && !d->resid &&
+      d->B.ld == d->K && d->ldc_n == 1 && (long)d->M % ((long)cv.H * cv.W) == 0) {
+    // narrow outputs (N = 32 / 64): spatially tiled kernel
+    if (cv.dil == 1 && cv.pad == 1 && (d->bias == nullptr || d->bias_mod == 0) && svl_conv3x3_tiled_eligible(tiled_params(d))) {
+      r->family = FAM_TILED3X3;
+      r->path = svl_conv3x3_tiled_path();
+      return SVL_OK;
     }
-  }
-
-  // Dilated 3x3 convolutions on 32 x 32 maps (the ASPP branches and their input gradients) with pre-split weight planes, in the
-  // split-product mode: whole-image tiles on fp16 x 2 terms (conv_dil.hip) instead of the implicit GEMM
-  if (conv_tiled && emu_mode == 6 && d->conv_w_planes && am == SVL_A_CONV && bm == SVL_B_KCONTIG && d->out_mode == SVL_OUT_STRIDED &&
-      d->batch == 1 && d->ksplit == 0 && cv.KH == 3 && cv.KW == 3 && cv.dil > 1 && cv.pad == cv.dil && p.cv.stride == 1 &&
-      cv.C2 == 0 && d->alpha == 1.0f && !d->preact && !d->resid && !d->bias && d->act == SVL_ACT_NONE && d->B.ld == d->K &&
-      d->ldc_n == 1 && (long)d->M % ((long)cv.H * cv.W) == 0) {
-    ConvDilP t;
-    t.src = d->A.ptr; t.ld = d->A.ld; t.C = cv.C1;
-    t.out = d->C; t.ldo = d->ldc_m;
-    t.imgs = (int)((long)d->M / ((long)cv.H * cv.W)); t.H = cv.H; t.W = cv.W; t.N = d->N;
-    t.dil = cv.dil; t.sign = cv.sign; t.accumulate = d->accumulate;
-    t.w_planes = d->conv_w_planes;
-    if (d->K == 9 * cv.C1 && svl_conv3x3_dil_eligible(t)) {
-      g_last_path = SVL_PATH_H2X;
-      return svl_conv3x3_dil_launch(t, st);
+    // dilated convolutions on 32 x 32 maps (the ASPP branches and their input gradients) with pre-split weight planes, in
+    // the split-product mode: whole-image tiles on fp16 x 2 terms
+    if (emu_mode == 6 && d->conv_w_planes && cv.dil > 1 && cv.pad == cv.dil && cv.C2 == 0 && !d->bias && d->act == SVL_ACT_NONE &&
+        d->K == 9 * cv.C1 && svl_conv3x3_dil_eligible(dil_params(d))) {
+      r->family = FAM_DIL3X3;
+      r->path = SVL_PATH_H2X;
+      return SVL_OK;
     }
   }
 
   // Ragged token count (M = images x 1025 tokens = 128 k + r): the r leftover rows would cost one more full-length
   // block per column tile, i.e. a whole extra round of the grid on a launch whose tile count is otherwise an exact
   // multiple of the resident-block count (measured -14 % on the N = 768 GEMMs).  Their rows are independent, so they
-  // run as a second, thin-tile launch on a helper stream, concurrent with the 128-row-aligned part.
-  int ragged_fork = g_ragged_fork.load(std::memory_order_relaxed);
-  if (ragged_fork < 0) {
-    ragged_fork = 1;
-    g_ragged_fork.store(ragged_fork, std::memory_order_relaxed);
+  // run as a second, thin-tile launch on a helper stream, concurrent with the 128-row-aligned part -- and are routed on
+  // their own (8 ... 127 rows: the exact kernel).
+  int rc;
+  if (am == SVL_A_KCONTIG && (bm == SVL_B_KCONTIG || bm == SVL_B_NCONTIG) && d->out_mode == SVL_OUT_STRIDED && d->batch == 1 &&
+      d->ksplit == 0 && d->M >= 8192 && (d->M % 128) != 0 && (long)d->N * d->K >= 768 * 768) {
+    r->m_main = (d->M / 128) * 128;
+    GemmP mainp, rem;
+    ragged_parts(p, r->m_main, &mainp, &rem);
+    rc = route_part(d, mainp, emu_mode, sw, &r->part[0]);
+    if (rc == SVL_OK) rc = route_part(d, rem, emu_mode, sw, &r->part[1]);
+  } else {
+    rc = route_part(d, p, emu_mode, sw, &r->part[0]);
   }
-  if (ragged_fork && am == SVL_A_KCONTIG && (bm == SVL_B_KCONTIG || bm == SVL_B_NCONTIG) &&
-      d->out_mode == SVL_OUT_STRIDED && d->batch == 1 && d->ksplit == 0 && d->M >= 8192 && (d->M % 128) != 0 &&
-      (long)d->N * d->K >= 768 * 768) {
-    const int m_main = (d->M / 128) * 128;
-    GemmP rem = p, mainp = p;
-    mainp.M = m_main;
-    rem.M = d->M - m_main;
-    rem.A.p = p.A.p + (long)m_main * p.A.ld;
-    rem.C = p.C + (long)m_main * p.ldc_m;
-    if (p.preact) rem.preact = p.preact + (long)m_main * p.ldc_m;
-    if (p.resid) rem.resid = p.resid + (long)m_main * p.ldr_m;
-    rem.A.vec = p.A.vec && aligned16(rem.A.p);
-    hipStream_t aux = nullptr, keep = st;
-    int rc = svl_fork(st, &aux);
-    if (rc != SVL_OK) return rc;
-    st = aux;
-    rc = launch(rem);
-    st = keep;
-    if (rc != SVL_OK) return rc;
-    rc = launch(mainp);
-    if (rc != SVL_OK) return rc;
-    return svl_join(st);
+  r->family = r->part[0].family;
+  r->path = r->part[0].path;
+  return rc;
+}
+
+// ----------------------------------------------------------------------------------------------------------- execution
+static int execute_part(const svl_gemm_desc* d, const GemmP& q, const PartRoute& r, hipStream_t st) {
+  const int am = d->a_mode, bm = d->b_mode;
+  switch (r.family) {
+    case FAM_EXACT_DENSE: return svl_gemm_part_mode_dense(am, bm, q, d->batch, st);
+    case FAM_EXACT_CONV: return svl_gemm_part_mode_conv(am, bm, q, d->batch, st);
+    case FAM_BF16X3: return svl_gemm_part_emu3(q, r.a_rm, r.b_rm, d->batch, st);
+    case FAM_BF16X2: return svl_gemm_part_emu2(0, q, r.a_rm, r.b_rm, d->batch, st);
   }
-  return launch(p);
+  // FAM_H2X2: the operand maxima (passes into the zeroed words, or the words the caller holds), then the kernel
+  unsigned* ws = static_cast<unsigned*>(d->emu_ws);
+  if (!(r.take_a && r.take_b)) SVL_HIP_CHECK(hipMemsetAsync(ws, 0, 8, st));
+  for (int i = 0; i < r.npass; ++i) {
+    const MaxPass& m = r.pass[i];
+    const int rc = m.x ? absmax_launch(m.x, m.rows, m.cols, m.ld, ws + m.word, st) : absmax_bx_launch(q, bm, ws + m.word, st);
+    if (rc != SVL_OK) return rc;
+  }
+  if (r.take_a || r.take_b) {
+    const int rc = amax_take(r.take_a, r.take_b, ws, st);
+    if (rc != SVL_OK) return rc;
+  }
+  GemmP q2 = q;
+  q2.amax = ws;
+  return svl_gemm_part_emu2(1, q2, r.a_rm, r.b_rm, d->batch, st);
+}
+
+static int gemm_execute(const svl_gemm_desc* d, const GemmP& p, const GemmRoute& r, hipStream_t st) {
+  switch (r.family) {
+    case FAM_SHORTK_X6: return svl_shortk_x6_launch(shortk_x6_params(d), st);
+    case FAM_SHORTK: return launch_shortk(p, r.sk_fast, st);
+    case FAM_CIN1: {
+      const int ppb = 256 / (d->N / 4);
+      long blocks = ((long)d->M + ppb - 1) / ppb;
+      if (blocks > 256 * 16) blocks = 256 * 16;
+      hipLaunchKernelGGL(conv_cin1_fwd_kernel<9>, dim3((unsigned)blocks), dim3(256), 0, st, p);
+      SVL_LAUNCH_CHECK("svl_gemm_f32/conv_cin1");
+      return SVL_OK;
+    }
+    case FAM_TILED3X3: return svl_conv3x3_tiled_launch(tiled_params(d), st);
+    case FAM_DIL3X3: return svl_conv3x3_dil_launch(dil_params(d), st);
+  }
+  if (r.m_main == 0) return execute_part(d, p, r.part[0], st);
+  GemmP mainp, rem;
+  ragged_parts(p, r.m_main, &mainp, &rem);
+  hipStream_t aux = nullptr;
+  int rc = svl_fork(st, &aux);
+  if (rc != SVL_OK) return rc;
+  rc = execute_part(d, rem, r.part[1], aux);
+  if (rc != SVL_OK) return rc;
+  rc = execute_part(d, mainp, r.part[0], st);
+  if (rc != SVL_OK) return rc;
+  return svl_join(st);
+}
+
+extern "C" int svl_gemm_f32(const svl_gemm_desc* d, svl_stream_t stream) {
+  GemmP p;
+  int rc = gemm_fill(d, &p);
+  if (rc != SVL_OK) return rc;
+  GemmRoute r;
+  rc = gemm_route(d, p, svl_get_gemm_emulation(), svl_switches(), &r);
+  if (rc != SVL_OK) return rc;
+  g_last_path = r.path;
+  return gemm_execute(d, p, r, (hipStream_t)stream);
+}
+
+extern "C" int svl_gemm_route(const svl_gemm_desc* d, svl_gemm_route_info* out) {
+  SVL_CHECK_ARG(out != nullptr, "svl_gemm_route: null out pointer");
+  memset(out, 0, sizeof(*out));
+  GemmP p;
+  int rc = gemm_fill(d, &p);
+  if (rc != SVL_OK) return rc;
+  GemmRoute r;
+  rc = gemm_route(d, p, svl_get_gemm_emulation(), svl_switches(), &r);
+  if (rc != SVL_OK) return rc;
+  out->path = r.path;
+  out->h2 = r.family == FAM_H2X2;
+  if (r.family == FAM_EXACT_DENSE || r.family == FAM_EXACT_CONV) {
+    out->tile_m = out->tile_n = 128;     // (the producers run on one tile shape)
+    if (!is_b_producer(d->b_mode)) exact_tile(r.m_main ? r.m_main : d->M, d->N, &out->tile_m, &out->tile_n);
+    out->blocks_per_cu = 3;
+  } else if (r.family == FAM_BF16X3 || r.family == FAM_BF16X2 || r.family == FAM_H2X2) {
+    out->tile_m = out->tile_n = 128;
+    out->blocks_per_cu = 2;
+  }
+  for (const PartRoute& part : r.part)
+    for (int i = 0; i < part.npass; ++i) out->max_passes += part.pass[i].x != nullptr;
+  out->ragged_rows = r.m_main ? d->M - r.m_main : 0;
+  return SVL_OK;
 }
 
 extern "C" int svl_set_gemm_emulation(int mode) {
@@ -2092,12 +2167,9 @@ extern "C" int svl_set_gemm_emulation(int mode) {
   g_emu_mode.store(mode, std::memory_order_relaxed);
   return SVL_OK;
 }
+void svl_set_last_gemm_path(int path) { g_last_path = path; }
 extern "C" int svl_last_gemm_path(void) { return g_last_path; }
 extern "C" int64_t svl_absmax_launches(void) { return (int64_t)g_absmax_launches.load(std::memory_order_relaxed); }
-extern "C" int svl_set_conv_tiled(int on) {
-  g_conv_tiled.store(on ? 1 : 0, std::memory_order_relaxed);
-  return SVL_OK;
-}
 extern "C" int svl_get_gemm_emulation(void) {
   int m = g_emu_mode.load(std::memory_order_relaxed);
   if (m < 0) {   // first use: the environment decides (the attention / tiled-conv dispatch may ask before any GEMM ran)

@@ -46,6 +46,12 @@ void svl_set_error(const char* fmt, ...);
 int svl_fork(hipStream_t st, hipStream_t* aux);
 int svl_join(hipStream_t st);
 
+// The environment's A/B switches (svl_switches(), include/semivl_hip.h: SVL_SW_* bits), read once per process.
+inline bool svl_switch(int bit) { return (svl_switches() & bit) != 0; }
+// The kernel family an entry point outside svl_gemm_f32 ran on, for svl_last_gemm_path() (gemm.hip).
+void svl_set_last_gemm_path(int path);
+enum { SVL_PATH_F32 = 0, SVL_PATH_BF16X = 1, SVL_PATH_SHORTK = 2, SVL_PATH_ELTWISE = 3, SVL_PATH_H2X = 4 };
+
 // ---- device helpers --------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

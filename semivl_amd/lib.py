@@ -43,6 +43,11 @@ class GemmDesc(C.Structure):
                 ("a_amax", C.c_void_p), ("b_amax", C.c_void_p)]
 
 
+class GemmRouteInfo(C.Structure):
+    _fields_ = [("path", C.c_int), ("h2", C.c_int), ("tile_m", C.c_int), ("tile_n", C.c_int), ("blocks_per_cu", C.c_int),
+                ("max_passes", C.c_int), ("ragged_rows", C.c_int)]
+
+
 class PGemmDesc(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("a_rows", C.c_int64), ("b_rows", C.c_int64),
                 ("m_off", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
@@ -83,7 +88,8 @@ SIGNATURES = {
     "svl_gemm_f32": (_I, [C.POINTER(GemmDesc), _P]),
     "svl_set_gemm_emulation": (_I, [_I]),
     "svl_get_gemm_emulation": (_I, []),
-    "svl_set_conv_tiled": (_I, [_I]),
+    "svl_gemm_route": (_I, [C.POINTER(GemmDesc), C.POINTER(GemmRouteInfo)]),
+    "svl_switches": (_I, []),
     "svl_planes_rows": (_L, [_L]),
     "svl_planes_bytes": (_L, [_L, _I]),
     "svl_split_planes_bf16x3": (_I, [_P, _L, _L, _L, _I, _P, _L, _L, _P]),

@@ -5,6 +5,7 @@ path is issued through libsemivl_hip.so.  All tensors are fp32 CUDA(HIP) tensors
 """
 import collections
 import ctypes as C
+import functools
 import os
 import math
 import numbers
@@ -112,19 +113,28 @@ class Op:
         return L.Operand(C.c_void_p(self.t.data_ptr() + 4 * self.off), self.ld, self.bso, self.bsi)
 
 
-# In-register split kernel on fp16 x 2 terms with per-tensor scales (svl_gemm_desc.emu_ws; round 5): SVL_GEMM_EMU_NO_H2=1 keeps
-# the bf16 x 3 form for every launch (A/B runs).
-EMU_H2 = not os.environ.get("SVL_GEMM_EMU_NO_H2")
+# The environment's A/B switches of the GEMM / convolution dispatch as the LIBRARY read them (svl_switches: SVL_SW_* bits, set
+# unless the variable is): SVL_GEMM_EMU_NO_H2 (mode 6 keeps the bf16 x 3 form for every launch), SVL_GEMM_NO_SHORTK,
+# SVL_CONV_NO_TILED (narrow 3x3 convolutions on the implicit GEMM), SVL_CONV_TILED_NO_EMU (tiled 3x3 kernels on the fp32 pipe).
+SW_EMU_H2, SW_SHORTK, SW_CONV_TILED, SW_CONV_TILED_EMU = 1, 2, 4, 8
+
+
+@functools.lru_cache(maxsize=None)
+def switches():
+    return L.load().svl_switches()
+
+
 # conv_fwd launches on the in-register fp16 x 2 form (implicit-GEMM convolutions the tiled / whole-image kernels do not take).
 # Round 5 ended with them OFF (the float64 gate of tests/test_fullsize_gpu.py at 4.0 - 4.4 x); since the split-K slab sums run in
 # double and the gate compares under the product's own tie decisions they are ON (mode-6 families <= 2.5 x).
 EMU_H2_CONVFWD = True
 
 
-def gemm(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batch=1, batch_inner=1, ksplit=0,
-         c_bso=0, c_bsi=0, alpha=1.0, bias=None, bias_mod=0, act=ACT_NONE, resid=None, r_off=0, ldr_m=None, ldr_n=1,
-         r_bso=0, r_bsi=0, accumulate=False, out_mode=OUT_STRIDED, conv=None, ct=(0, 0, 0), preact=None, w_planes=None,
-         emu_h2=True, b_aux=None, amax=None):
+def gemm_desc(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batch=1, batch_inner=1, ksplit=0,
+              c_bso=0, c_bsi=0, alpha=1.0, bias=None, bias_mod=0, act=ACT_NONE, resid=None, r_off=0, ldr_m=None, ldr_n=1,
+              r_bso=0, r_bsi=0, accumulate=False, out_mode=OUT_STRIDED, conv=None, ct=(0, 0, 0), preact=None, w_planes=None,
+              b_aux=None, amax=None):
+    """The svl_gemm_desc of a launch (no library call; host tensors serve for gemm_route)."""
     d = L.GemmDesc()
     if amax is not None:    # (a_amax, b_amax): operand maxima the caller holds (Planes.amax); each may be None
         d.a_amax, d.b_amax = _p(amax[0]), _p(amax[1])
@@ -150,9 +160,30 @@ def gemm(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batc
         d.ldr_m = ldr_m if ldr_m is not None else d.ldc_m
         d.ldr_n, d.r_bs_outer, d.r_bs_inner = ldr_n, r_bso, r_bsi
     d.accumulate = 1 if accumulate else 0
+    return d
+
+
+def wants_emu_ws(d, emu_h2=True):
+    """Pre-filter of the fp16 x 2 form of the in-register split kernel (svl_gemm_desc.emu_ws; round 5): launches it cannot
+    serve get no scratch.  It only saves an allocation -- the library decides (svl_gemm_route)."""
+    return bool(switches() & SW_EMU_H2 and emu_h2 and 2.0 * d.M * d.N * d.K >= 4.0e9 and (d.batch == 1 or d.ksplit > 0)
+                and get_gemm_emulation() == 6)
+
+
+def gemm_route(d):
+    """What svl_gemm_f32(d) would do (lib.GemmRouteInfo): host arithmetic in the library, no launch, no device call."""
+    info = L.GemmRouteInfo()
+    rc = L.load().svl_gemm_route(C.byref(d), C.byref(info))
+    if rc != 0:
+        L.check(rc, "svl_gemm_route")
+    return info
+
+
+def gemm(a_mode, b_mode, M, N, K, A, B, Cout, *args, emu_h2=True, **kw):
+    """svl_gemm_f32 on the descriptor gemm_desc builds from the same arguments."""
+    d = gemm_desc(a_mode, b_mode, M, N, K, A, B, Cout, *args, **kw)
     ws = None
-    if (EMU_H2 and emu_h2 and 2.0 * M * N * K >= 4.0e9 and (batch == 1 or ksplit > 0)
-            and Cout.is_cuda and get_gemm_emulation() == 6):
+    if Cout.is_cuda and wants_emu_ws(d, emu_h2):
         ws = torch.empty(2, dtype=torch.int32, device=Cout.device)      # scratch of the operand-maximum passes (fp16 x 2 form)
         d.emu_ws = _p(ws)
     e0 = _prof_begin()
@@ -162,7 +193,8 @@ def gemm(a_mode, b_mode, M, N, K, A, B, Cout, c_off=0, ldc_m=None, ldc_n=1, batc
         # (svl_last_gemm_path: 1 = bf16 split products, 4 = fp16 x 2 split products; 0 / 2 / 3 = exact fp32 MFMA, short-K
         # stream, elementwise)
         path = L.load().svl_last_gemm_path()
-        _prof_end("gemm_bf16x" if path in (1, 4) else "gemm", e0, 2.0 * M * N * K * (1 if ksplit > 0 else batch),
+        batch = d.batch
+        _prof_end("gemm_bf16x" if path in (1, 4) else "gemm", e0, 2.0 * M * N * K * (1 if d.ksplit > 0 else batch),
                   (a_mode, b_mode, M, N, K, batch) if path != 4 else ("split_h2", a_mode, b_mode, M, N, K, batch))
 
 
@@ -629,19 +661,39 @@ def matmul_nn(a, b, out=None, accumulate=False, dact=ACT_NONE, z=None, planes_on
     return out
 
 
-def _ksplit_plan(M, N, K, dense=False, emu_tiles=False):
-    bm = 32 if M <= 32 else (64 if M <= 64 else 128)
-    bn = 128 if (M <= 64 and N > 64) else (32 if N <= 32 else (64 if N <= 64 else 128))
-    tiles = math.ceil(M / bm) * math.ceil(N / bn)
-    slots = 768
-    if emu_tiles or (dense and M >= 256 and N >= 96 and get_gemm_emulation()):
-        tiles, slots = math.ceil(M / 128) * math.ceil(N / 128), 512   # the emulated kernel keeps 2 blocks per CU
-    # slices so that tiles x slices fills, but does not exceed, ONE round of resident blocks (256 CUs x 3): 36 tiles x 29
+CUS = 256      # compute units of the MI355X: a launch's resident blocks = CUS x the blocks of its kernel a CU holds
+
+
+@functools.lru_cache(maxsize=None)
+def _ksplit_plan(a_mode, b_mode, M, N, K, lda, ldb, aligned=True, geom=None):
+    """(slices, K per slice) of a deterministic split-K launch.  The tile shape and the residency are those of the kernel the
+    library routes the UNSPLIT descriptor to (svl_gemm_route; a split into multiples of 16 lands on the same kernel).  Cached
+    on its integer arguments: a steady-state step asks nothing.  The arithmetic mode changes only through
+    set_gemm_emulation, which drops the cache.  `aligned`: every operand pointer is 16-byte aligned; `geom`: the
+    conv_geom arguments (H, W, C1, KH, KW, dil, pad, sign, C2, rep, ld2, stride, Ho, Wo) of a B_CONVW launch."""
+    ptr = C.c_void_p(16 if aligned else 4)
+    d = L.GemmDesc()
+    d.a_mode, d.b_mode, d.M, d.N, d.K = a_mode, b_mode, M, N, K
+    d.batch = d.batch_inner = 1
+    d.A, d.B, d.C = L.Operand(ptr, lda, 0, 0), L.Operand(ptr, ldb, 0, 0), ptr
+    d.ldc_m, d.ldc_n, d.alpha = N, 1, 1.0
+    if geom is not None:
+        H, W, C1, KH, KW, dil, pad, sign, C2, rep, ld2, stride, Ho, Wo = geom
+        d.conv = conv_geom(H, W, C1, KH, KW, dil, pad, sign, C2, rep, None, ld2, stride=stride, Ho=Ho, Wo=Wo)
+        if C2:
+            d.conv.src2 = ptr
+    r = gemm_route(d)
+    tiles, slots = math.ceil(M / r.tile_m) * math.ceil(N / r.tile_n), CUS * r.blocks_per_cu
+    # slices so that tiles x slices fills, but does not exceed, ONE round of resident blocks: 36 tiles x 29
     # slices = 1044 blocks was 1.36 rounds, i.e. a second, mostly idle round
     s = max(1, min(slots // tiles if tiles <= slots else 1, K // 512 if K >= 1024 else 1, 512))
     ks = math.ceil(math.ceil(K / s) / 16) * 16
     s = math.ceil(K / ks)
     return s, ks
+
+
+def _al16(*ts):
+    return all(t.data_ptr() % 16 == 0 for t in ts)
 
 
 def matmul_tn(a, b, out=None, accumulate=False, a_amax=None, b_amax=None):
@@ -654,7 +706,7 @@ def matmul_tn(a, b, out=None, accumulate=False, a_amax=None, b_amax=None):
         out = empty(M, N, device=a.device)
         accumulate = False
     assert out.is_contiguous()
-    s, ks = _ksplit_plan(M, N, K, dense=True)
+    s, ks = _ksplit_plan(A_MC, B_NC, M, N, K, a.stride(0), b.stride(0), _al16(a, b))
     if s == 1:
         gemm(A_MC, B_NC, M, N, K, Op(a, a.stride(0)), Op(b, b.stride(0)), out, accumulate=accumulate, amax=(a_amax, b_amax))
         return out
@@ -674,7 +726,7 @@ def _matmul_tn_prod(a, N, b_op, b_mode, out, accumulate, conv=None, b_aux=None, 
         out = empty(M, N, device=a.device)
         accumulate = False
     assert out.is_contiguous() and out.numel() == M * N
-    s, ks = _ksplit_plan(M, N, K, dense=True)
+    s, ks = _ksplit_plan(A_MC, B_NC, M, N, K, a.stride(0), N, _al16(a))     # matmul_tn's, whatever the producer
     if s == 1:
         gemm(A_MC, b_mode, M, N, K, Op(a, a.stride(0)), b_op, out, accumulate=accumulate, conv=conv, b_aux=b_aux,
              amax=(a_amax, None))
@@ -1021,7 +1073,7 @@ def conv3x3_gn(x, ldx, imgs, H, W, C1, wf, Co, eps, src2=None, ld2=0, C2=0, rep=
     """3x3 / pad 1 convolution fused with the statistics of the following GroupNorm (groups of 16 channels): returns
     (pre [imgs*H*W, Co], stats [imgs, Co/16, 2]), or None when the tiled kernel does not take the shape (the caller then
     runs conv_fwd + groupnorm_fwd)."""
-    if not (CONV_TILED and Co % 16 == 0):
+    if not (switches() & SW_CONV_TILED and Co % 16 == 0):
         return None
     lib = L.load()
     ws = torch.empty(max(1, lib.svl_conv3x3_gn_ws_doubles(imgs, H, W, Co)), dtype=torch.float64, device=x.device)
@@ -1034,9 +1086,8 @@ def conv3x3_gn(x, ldx, imgs, H, W, C1, wf, Co, eps, src2=None, ld2=0, C2=0, rep=
         return None
     L.check(rc, "svl_conv3x3_gn_f32")
     if e0 is not None:
-        x6 = get_gemm_emulation() == 6 and not os.environ.get("SVL_CONV_TILED_NO_EMU")
         K = 9 * (C1 + C2)
-        _prof_end("gemm_bf16x" if x6 else "gemm", e0, 2.0 * imgs * H * W * Co * K, (A_CONV, B_KC, imgs * H * W, Co, K, 1))
+        _prof_end("gemm_bf16x" if lib.svl_last_gemm_path() in (1, 4) else "gemm", e0, 2.0 * imgs * H * W * Co * K, (A_CONV, B_KC, imgs * H * W, Co, K, 1))
     return pre, stats
 
 
@@ -1069,7 +1120,7 @@ def conv3x3_dgrad_gnb(dy, lddy, imgs, H, W, Co, wd, Ci, gn_x, gn_stats, gn_gamma
     """Input gradient dx [pix, Ci] of a narrow 3x3 convolution (dgrad pack wd [Ci, 9 Co]) TOGETHER with the backward channel
     sums of the GroupNorm + ReLU (over gn_x [pix, Ci], G groups of 16 channels) whose output gradient dx is: returns
     (dx, chan_sums [imgs, 2, Ci]) or None when the fused kernel does not take the launch (callers: conv_dgrad + groupnorm_bwd)."""
-    if not (GN_BWD_FUSED and CONV_TILED and Ci % 16 == 0 and G * 16 == Ci and dy.is_cuda and get_gemm_emulation() == 6):
+    if not (GN_BWD_FUSED and switches() & SW_CONV_TILED and Ci % 16 == 0 and G * 16 == Ci and dy.is_cuda and get_gemm_emulation() == 6):
         return None
     lib = L.load()
     table = groupnorm_scale_shift(gn_stats, gn_gamma, gn_beta, imgs, Ci, G)
@@ -1322,9 +1373,6 @@ def unpack_conv_wgrad(dwf, Co, Ci, kh, kw):
     return permute4(dwf, (Co, Ci, kh, kw), (kh * kw * Ci, 1, kw * Ci, Ci))     # [Co, kh, kw, Ci] -> [Co, Ci, kh, kw]
 
 
-CONV_TILED = not os.environ.get("SVL_CONV_NO_TILED")   # narrow 3x3 weight gradients on conv_tiled.hip
-
-
 def conv_out_size(H, W, KH, KW, dil, pad, stride):
     return (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
 
@@ -1357,11 +1405,32 @@ def conv_dgrad(dy, lddy, imgs, H, W, Co, wd, Ci, KH, KW, dil, pad, out=None, ldo
     return out
 
 
+def conv_tiled_emu():
+    """The tiled 3x3 kernels run on the split pipe (mode 6, unless SVL_CONV_TILED_NO_EMU)."""
+    return get_gemm_emulation() == 6 and bool(switches() & SW_CONV_TILED_EMU)
+
+
 def conv_wgrad_tiled_ok(imgs, H, W, C1, C2, Co, lddy, ldx, ld2=0):
-    """The spatially tiled 3x3 weight-gradient kernels (conv_tiled.hip) take this layer (they also accept `gn_in`)."""
-    co_ok = Co in (32, 64) or (Co == 128 and get_gemm_emulation() == 6 and not os.environ.get("SVL_CONV_TILED_NO_EMU"))
-    return (CONV_TILED and co_ok and C1 % 4 == 0 and C2 % 4 == 0 and (C1 + C2) % 32 == 0 and H >= 8 and W >= 16 and
-            imgs * H * W >= 16384 and lddy % 4 == 0 and ldx % 4 == 0 and (C2 == 0 or ld2 % 4 == 0))
+    """The spatially tiled 3x3 weight-gradient kernels (conv_tiled.hip) take this layer (they also accept `gn_in`).
+    Cout = 128 exists on the split kernel only."""
+    return bool(switches() & SW_CONV_TILED and C1 % 4 == 0 and C2 % 4 == 0 and (C1 + C2) % 32 == 0 and H >= 8 and W >= 16 and
+                imgs * H * W >= 16384 and lddy % 4 == 0 and ldx % 4 == 0 and (C2 == 0 or ld2 % 4 == 0) and
+                (Co in (32, 64) or (Co == 128 and conv_tiled_emu())))
+
+
+def _wgrad_splitk(M, N, Kpix, a, lda, b, ldb, geom, src2=None):
+    """out[M, N] = a^T im2col(b)^T (A_MC x B_CONVW) with deterministic split-K over the pixels; `geom`: _ksplit_plan's."""
+    H, W, C1, KH, KW, dil, pad, sign, C2, rep, ld2, stride, Ho, Wo = geom
+    g = conv_geom(H, W, C1, KH, KW, dil, pad, sign, C2, rep, src2, ld2, stride=stride, Ho=Ho, Wo=Wo)
+    s, ks = _ksplit_plan(A_MC, B_CONVW, M, N, Kpix, lda, ldb, _al16(a, b) and (src2 is None or _al16(src2)), geom)
+    out = empty(M, N, device=a.device)
+    if s == 1:
+        gemm(A_MC, B_CONVW, M, N, Kpix, Op(a, lda), Op(b, ldb), out, conv=g)
+        return out
+    slabs = empty(s, M, N, device=a.device)
+    gemm(A_MC, B_CONVW, M, N, Kpix, Op(a, lda), Op(b, ldb), slabs, batch=s, ksplit=ks, c_bso=M * N, conv=g)
+    reduce_slabs(out, slabs)
+    return out
 
 
 def conv_wgrad(dy, lddy, x, ldx, imgs, H, W, C1, Co, KH, KW, dil, pad, src2=None, ld2=0, C2=0, rep=1, stride=1, gn_in=None):
@@ -1370,10 +1439,7 @@ def conv_wgrad(dy, lddy, x, ldx, imgs, H, W, C1, Co, KH, KW, dil, pad, src2=None
     Ho, Wo = conv_out_size(H, W, KH, KW, dil, pad, stride) if stride != 1 else (H, W)
     Kpix = imgs * Ho * Wo
     N = KH * KW * (C1 + C2)
-    co_ok = Co in (32, 64) or (Co == 128 and get_gemm_emulation() == 6 and not os.environ.get("SVL_CONV_TILED_NO_EMU"))
-    if (CONV_TILED and KH == 3 and KW == 3 and dil == 1 and pad == 1 and stride == 1 and co_ok and
-            C1 % 4 == 0 and C2 % 4 == 0 and (C1 + C2) % 32 == 0 and H >= 8 and W >= 16 and Kpix >= 16384 and lddy % 4 == 0 and ldx % 4 == 0 and
-            (C2 == 0 or ld2 % 4 == 0)):
+    if (KH, KW, dil, pad, stride) == (3, 3, 1, 1, 1) and conv_wgrad_tiled_ok(imgs, H, W, C1, C2, Co, lddy, ldx, ld2):
         # narrow layers: spatially tiled weight-gradient kernel (conv_tiled.hip), slabs reduced in fixed order
         lib = L.load()
         groups = lib.svl_conv3x3_wgrad_tiled_groups(imgs, H, W, C1 + C2, Co)
@@ -1381,26 +1447,14 @@ def conv_wgrad(dy, lddy, x, ldx, imgs, H, W, C1, Co, KH, KW, dil, pad, src2=None
         e0 = _prof_begin()
         L.check(lib.svl_conv3x3_wgrad_tiled(_p(dy), lddy, Co, _p(x), ldx, C1, _p(src2), ld2, C2, rep, imgs, H, W,
                                             _p(slabs), groups, _p(gn_in), _st()), "svl_conv3x3_wgrad_tiled")
-        x6 = (get_gemm_emulation() == 6 and not os.environ.get("SVL_CONV_TILED_NO_EMU") and
-              (Co >= 64 or (C1 + C2) % 64 == 0 or (C1 + C2 == 32 and H >= 8 and groups >= 2)))   # the dispatch rule of svl_conv3x3_wgrad_tiled
-        _prof_end("gemm_bf16x" if x6 else "gemm", e0, 2.0 * Co * N * Kpix, ("wgrad3x3_tiled", Co, N, Kpix, 1))
+        if e0 is not None:
+            _prof_end("gemm_bf16x" if lib.svl_last_gemm_path() in (1, 4) else "gemm", e0, 2.0 * Co * N * Kpix,
+                      ("wgrad3x3_tiled", Co, N, Kpix, 1))
         out = empty(Co, N, device=dy.device)
         reduce_slabs(out, slabs)
         return out
     assert gn_in is None, "gn_in needs the tiled weight-gradient kernel (conv_wgrad_tiled_ok)"
-    g = conv_geom(H, W, C1, KH, KW, dil, pad, 1, C2, rep, src2, ld2, stride=stride, Ho=Ho, Wo=Wo)
-    # (the split-emulation kernel serves this launch when Cout >= 96, N >= 96 and the output rows are whole 8-pixel groups:
-    # 128-row tiles, two resident blocks per CU)
-    x6 = (get_gemm_emulation() in (3, 6) and Co >= 96 and N >= 96 and Wo % 8 == 0 and Kpix >= 1024 and Kpix % 16 == 0)
-    s, ks = _ksplit_plan(Co, N, Kpix, emu_tiles=x6)
-    out = empty(Co, N, device=dy.device)
-    if s == 1:
-        gemm(A_MC, B_CONVW, Co, N, Kpix, Op(dy, lddy), Op(x, ldx), out, conv=g)
-        return out
-    slabs = empty(s, Co, N, device=dy.device)
-    gemm(A_MC, B_CONVW, Co, N, Kpix, Op(dy, lddy), Op(x, ldx), slabs, batch=s, ksplit=ks, c_bso=Co * N, conv=g)
-    reduce_slabs(out, slabs)
-    return out
+    return _wgrad_splitk(Co, N, Kpix, dy, lddy, x, ldx, (H, W, C1, KH, KW, dil, pad, 1, C2, rep, ld2, stride, Ho, Wo), src2)
 
 
 def conv_cout1_gn_ok(H, W, Cc, KH=3, KW=3, dil=1, pad=1):
@@ -1471,19 +1525,7 @@ def convT2x_dgrad(du, lddu, imgs, H, W, Co, wb, Ci):
 
 def convT2x_wgrad(x, ldx, du, lddu, imgs, H, W, Ci, Co):
     """dWb[Ci, (a,b,co)] = sum_m x[m,ci] * du[pix(m;a,b), co]."""
-    Kpix = imgs * H * W
-    N = 4 * Co
-    g = conv_geom(2 * H, 2 * W, Co, 2, 2, 1, 0, 1, stride=2, Ho=H, Wo=W)
-    x6 = (get_gemm_emulation() in (3, 6) and Ci >= 96 and N >= 96 and W % 8 == 0 and Kpix >= 1024 and Kpix % 16 == 0)
-    s, ks = _ksplit_plan(Ci, N, Kpix, emu_tiles=x6)
-    out = empty(Ci, N, device=x.device)
-    if s == 1:
-        gemm(A_MC, B_CONVW, Ci, N, Kpix, Op(x, ldx), Op(du, lddu), out, conv=g)
-        return out
-    slabs = empty(s, Ci, N, device=x.device)
-    gemm(A_MC, B_CONVW, Ci, N, Kpix, Op(x, ldx), Op(du, lddu), slabs, batch=s, ksplit=ks, c_bso=Ci * N, conv=g)
-    reduce_slabs(out, slabs)
-    return out
+    return _wgrad_splitk(Ci, 4 * Co, imgs * H * W, x, ldx, du, lddu, (2 * H, 2 * W, Co, 2, 2, 1, 0, 1, 0, 1, 0, 2, H, W))
 
 
 # ------------------------------------------------------------------------------------------------ resampling
@@ -2103,6 +2145,7 @@ def panel_label(label, palette, canvas, y0, x0):
 def set_gemm_emulation(mode):
     """0: exact fp32 MFMA (default); 6 / 3: bf16 split emulation for the large dense GEMMs (include/semivl_hip.h)."""
     L.check(L.load().svl_set_gemm_emulation(int(mode)), "svl_set_gemm_emulation")
+    _ksplit_plan.cache_clear()
 
 
 def get_gemm_emulation():
