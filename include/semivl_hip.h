@@ -1126,6 +1126,33 @@ int svl_quickgelu_f32(const float* x, float* y, int64_t count, svl_stream_t stre
 int svl_gather_rows_f32(const float* x, const int* idx, int n, int L, int E, float* out, svl_stream_t stream);
 int svl_segment_mean_f32(const float* x, int64_t m, int E, const int* offsets, int N, float* out, svl_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * MaskCLIP's training-free refinements of a dense zero-shot prediction (maskclip_head.py:129-155), the passes around the two
+ * svl_gemm_f32 products of key smoothing.  x [B * HW, N] are cosine logits (token rows, leading dimension ldx), k [B * HW, E]
+ * the last block's keys.  With P = softmax(100 x') over the classes, x' = x with every class c of image b whose peak
+ * max_i softmax(100 x)[b, i, c] is < pd_thresh set to -100, the smoothed rows are O = k^ (k^^T P) per image, k^ = k scaled per
+ * CHANNEL over the HW tokens of its image (F.normalize's default dim = 1 on [B, HW, E]); W = k^ k^^T is never formed.
+ * fp32; 16-byte accesses where the pointers and strides allow them, scalar otherwise; grids are capped and walked
+ * grid-stride.  A null pointer, B, HW, N or E < 1, a leading dimension below the width or a negative threshold is
+ * SVL_ERR_INVALID_ARG, named in svl_last_error(), and nothing is written.  No atomics: two runs agree bit for bit.
+ *   svl_mc_class_peak_f32  peak[b, c] = max_i P[b * HW + i, c] for P [B * HW, N] with leading dimension ld.  A NaN in a
+ *                          column gives NaN (torch.max): NaN < pd_thresh is false, so such a class is kept.  The rows of a
+ *                          column are folded in one fixed order.
+ *   svl_col_invsq_f32      s[b, c] = 1 / max(sqrt(sum_i k[b * HW + i, c]^2), eps)^2: the squares are accumulated in double, in
+ *                          one fixed order per column, and the quotient is rounded to fp32 once.
+ *   svl_mc_softmax_f32     P[r, :] = softmax(100 x'[r, :]) as exp(z - max z) / sum exp(z - max z), z = 100 x', and
+ *                          rowmax[r] = max_c P[r, c] (NaN if the row holds one; rowmax may be null).  peak null: nothing is
+ *                          dropped (x' = x).  fill_only != 0: P receives x' itself (x, or exactly -100.0), rowmax must be null.
+ *   svl_mc_select_f32      out[b, c, i] = rowmax[b * HW + i] < ks_thresh ? O[b * HW + i, c] : P[b * HW + i, c], written straight
+ *                          into the class-planes layout [B, N, HW] (svl_bilinear_planes_fwd, svl_maskclip_labels).  A NaN
+ *                          rowmax keeps P.  O and rowmax both null: the transpose of P alone, bit for bit. */
+int svl_mc_class_peak_f32(const float* P, int64_t ld, int B, int HW, int N, float* peak, svl_stream_t stream);
+int svl_col_invsq_f32(const float* k, int64_t ld, int B, int HW, int E, float eps, float* s, svl_stream_t stream);
+int svl_mc_softmax_f32(const float* x, int64_t ldx, const float* peak, float pd_thresh, int B, int HW, int N, int fill_only,
+                       float* P, int64_t ldp, float* rowmax, svl_stream_t stream);
+int svl_mc_select_f32(const float* P, int64_t ldp, const float* O, int64_t ldo, const float* rowmax, float ks_thresh, int B,
+                      int HW, int N, float* out, svl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

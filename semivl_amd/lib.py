@@ -240,6 +240,10 @@ SIGNATURES = {
     "svl_quickgelu_f32": (_I, [_P, _P, _L, _P]),
     "svl_gather_rows_f32": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "svl_segment_mean_f32": (_I, [_P, _L, _I, _P, _I, _P, _P]),
+    "svl_mc_class_peak_f32": (_I, [_P, _L, _I, _I, _I, _P, _P]),
+    "svl_col_invsq_f32": (_I, [_P, _L, _I, _I, _I, _F, _P, _P]),
+    "svl_mc_softmax_f32": (_I, [_P, _L, _P, _F, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "svl_mc_select_f32": (_I, [_P, _L, _P, _L, _P, _F, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -21,11 +21,12 @@ from .resnet import ResNetV1c
 from .vit import MaskClipVisionTransformer
 from .vlg_head import VLGHead
 from .dlv3p_head import DLV3PHead
+from .maskclip_head import MaskClip2Head
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 BACKBONES = {"MaskClipVisionTransformer": MaskClipVisionTransformer, "ResNetV1c": ResNetV1c}
-HEADS = {"VLGHead": VLGHead, "DLV3PHead": DLV3PHead}
+HEADS = {"VLGHead": VLGHead, "DLV3PHead": DLV3PHead, "MaskClip2Head": MaskClip2Head}
 SEGMENTORS = {}
 
 
@@ -50,7 +51,9 @@ def _vit_cfg(img_size, out_indices):
 
 def builtin_model_cfg(name):
     """Own restatement of the hyper-parameters of configs/_base_/models/{vlm-vlg-aspp-s2p4-sk04-ftap-mcvitb,
-    vlm-vlg-aspp-s2p4-skr04-ftap-mcvitb,vlm-dlv3p-bn12-sk4-ft-mcvitb,vlm-dlv3p-bn12-sk4-ftap-mcvitb,mcvit16}.py."""
+    vlm-vlg-aspp-s2p4-skr04-ftap-mcvitb,vlm-dlv3p-bn12-sk4-ft-mcvitb,vlm-dlv3p-bn12-sk4-ftap-mcvitb,mcvit16}.py, and
+    vlm-maskclip2-mcvitb: the frozen CLIP ViT under the parameter-free MaskClip2Head (no reference file of that name; the head
+    is the one model/builder.py:30 registers)."""
     if name == "vlm-vlg-aspp-s2p4-sk04-ftap-mcvitb":
         return dict(img_size=512, model=dict(
             type="VLM", pretrained="pretrained/clip2mmseg_ViT16_clip_backbone.pth",
@@ -78,6 +81,13 @@ def builtin_model_cfg(name):
                              dilations=(6, 12, 18), c1_in_channels=768, c1_channels=48, dropout_ratio=0, num_classes=19,
                              norm_cfg=dict(type="SyncBN", requires_grad=True), align_corners=False, init_cfg=None),
             freeze_backbone=ftap, exclude_keys=["attn", "pos_embed"] if ftap else None))
+    if name == "vlm-maskclip2-mcvitb":    # zero-shot MaskCLIP: dense embedding x text rows, nothing trained
+        return dict(img_size=512, model=dict(
+            type="VLM", pretrained="pretrained/clip2mmseg_ViT16_clip_backbone.pth",
+            backbone=_vit_cfg(512, None),
+            decode_head=dict(type="MaskClip2Head", img_size=512, in_channels=512, channels=512, num_classes=19,
+                             align_corners=False, in_index=-1, pd_thresh=0., ks_thresh=0.),
+            freeze_backbone=True))
     if name == "mcvit16":
         bb = _vit_cfg(512, None)
         bb["pretrained"] = "pretrained/clip2mmseg_ViT16_clip_backbone.pth"
@@ -216,8 +226,8 @@ class VLM(nn.Module):
     def head_res_size(self, in_size):
         """(h, w) of the decode head's own logit map for an input of `in_size`, when forward(head_res=True) would return
         it un-resized (the input is the training crop: ONE resize separates it from the loss), else None."""
-        if isinstance(self.decode_head, DLV3PHead):
-            return None     # its logits are at crop / 16, not crop / 4: the losses take the resized logits
+        if isinstance(self.decode_head, (DLV3PHead, MaskClip2Head)):
+            return None     # their maps are at crop / 16, not crop / 4: the losses take the resized logits
         S_ = self.decode_head.image_size
         if tuple(in_size) != (S_, S_):
             return None
@@ -238,6 +248,8 @@ class VLM(nn.Module):
             raise ValueError(forward_mode)
         if isinstance(self.decode_head, DLV3PHead):
             return self._forward_dlv3p(img, need_fp, only_fp, fp_masks, split_fp)
+        if isinstance(self.decode_head, MaskClip2Head):
+            return self._forward_maskclip2(img, need_fp, only_fp)
         S_ = self.decode_head.image_size
         in_size = tuple(img.shape[2:])
         feats, _ = self.backbone.forward_tokens(self.renormalize_img_for_clip(img), need_global=False)
@@ -314,6 +326,46 @@ def _forward_dlv3p(self, img, need_fp, only_fp, fp_masks, split_fp):
 
 
 VLM._forward_dlv3p = _forward_dlv3p
+
+
+def _forward_maskclip2(self, img, need_fp, only_fp):
+    """forward_wrapper (builder.py:56-102) for MaskClip2Head: cosine logits of the dense embedding against the text rows
+    (maskclip2_head.py:29-33), concept rows aggregated per class as forward_maskclip does (vlm.py:99-101), the head's two
+    refinements in eval mode (ops.mc_refine), the head's resize to (img_size, img_size) (maskclip2_head.py:23) and the
+    wrapper's to the input size (builder.py:93-97).  Gradient-free: nothing here trains (maskclip2_head.py:35-36)."""
+    for name, v in (("need_fp", need_fp), ("only_fp", only_fp)):
+        if v:
+            raise NotImplementedError(f"VLM.forward({name}=True) with MaskClip2Head: feature perturbation of a head without "
+                                      f"a training step is not implemented")
+    head = self.decode_head
+    S_ = head.image_size
+    in_size = tuple(img.shape[2:])
+    with torch.no_grad():
+        if head.wants_keys():
+            feats, _, k = self.backbone.forward_tokens(self.renormalize_img_for_clip(img), need_global=False, need_k=True)
+        else:
+            (feats, _), k = self.backbone.forward_tokens(self.renormalize_img_for_clip(img), need_global=False), None
+        emb = feats[head.in_index]      # [b, hw, 512], unit rows
+        b, HW, Ce = emb.shape
+        ps = self.backbone.patch_size
+        hp, wp = (img.shape[2] + ps - 1) // ps, (img.shape[3] + ps - 1) // ps
+        text = self.text_feat_f32(img.device)
+        NC = text.shape[0]
+        x = ops.empty(b * HW, NC, device=img.device)        # token rows: F.conv2d(feat, text[:, :, None, None]) transposed
+        ops.gemm(ops.A_KC, ops.B_KC, HW, NC, Ce, ops.Op(emb, Ce, 0, HW * Ce, 0), ops.Op(text, Ce), x, ldc_m=NC, ldc_n=1,
+                 batch=b, c_bso=HW * NC)
+        if NC != self.num_classes:      # every token row is an "image" of one pixel to the per-class concept maximum
+            x = aggregate_concept_predictions(x.view(b * HW, NC, 1, 1),
+                                              get_class_to_concept_idxs(self.load_text_embedding)).view(b * HW, -1)
+        assert x.shape[1] == self.num_classes
+        out = head.forward_tokens(x, k.view(b * HW, -1) if k is not None else None, b, (hp, wp))
+        out = _PlanesResizeFn.apply(out, (S_, S_), self.align_corners)
+        if in_size != (S_, S_):
+            out = _PlanesResizeFn.apply(out, in_size, self.align_corners)
+    return out
+
+
+VLM._forward_maskclip2 = _forward_maskclip2
 
 
 class _ChanMaskFn(torch.autograd.Function):

@@ -136,8 +136,10 @@ def sink_grad(param, grad_fn, shape=None):
 DROP_PATH_SITES = ("attn", "ffn", "ffn_v")   # x + dp(out_proj(attention)), x2 + dp(FFN(ln2 x2)), vo + dp(FFN(ln2 vo))
 
 
-def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save, dp=None):
+def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save, dp=None, k_out=None):
     """x [Bn*T, E] -> (x_out or None, v or None).  `save` is a dict to stash what backward needs (or None).
+    `k_out`: None, or a list that receives the block's MaskCLIP keys out_proj(in_proj_k(ln1 x)) [Bn*T, E] (forward_qkv,
+    maskclip_vit.py:110-118: both biases, no residual): two E x E GEMMs on the ln1 output the block forms anyway.
     `dp`: None, or the block's live stochastic-depth sites: dict(keep=1 - p_i, <site>=mask [Bn] fp32 ...) over DROP_PATH_SITES.
     At a live site the branch's GEMM runs without its residual operand and ops.droppath_add forms identity + (mask_b / keep) *
     branch in place in the branch's buffer.
@@ -158,6 +160,9 @@ def block_forward(x, p, heads, eps, Bn, T, want_v, skip_x, save, dp=None):
     else:
         qkv = ops.linear(y1a, p["win"], p["bin"])
         vproj = qkv[:, 2 * E:]
+    if k_out is not None:
+        kproj = ops.linear(y1a, p["win"][E:2 * E], p["bin"][E:2 * E])
+        k_out.append(ops.linear(ops.split_planes(kproj) if pp else kproj, p["wout"], p["bout"]))
     v = None
     if save is not None:
         save.update(x=x, y1=y1, st1=st1, qkv=qkv, vproj=vproj, want_v=want_v, skip_x=skip_x, eps=eps,
@@ -643,9 +648,14 @@ class MaskClipVisionTransformer(nn.Module):
                     F.interpolate(eye, size=hw, mode="bicubic", align_corners=False).view(ph * pw, -1).t().contiguous())
         return cache[key].get()
 
-    def forward_tokens(self, img, need_global=False):
-        """Returns (feat_tokens list of [B, P, C] tensors, global or None) on the autograd graph."""
+    def forward_tokens(self, img, need_global=False, need_k=False):
+        """Returns (feat_tokens list of [B, P, C] tensors, global or None) on the autograd graph.
+        need_k: a third element, the LAST block's keys [B, P, E] without the class-token row (forward_qkv's k,
+        maskclip_vit.py:110-118, 568-570), from the same encoder pass.  Gradient-free only."""
         tr = self._trainable()
+        if need_k and self.num_prompt_tokens is not None:
+            raise ValueError("MaskClipVisionTransformer.forward_tokens(need_k=True): num_prompt_tokens is set; the reference's "
+                             "k[:, 1:] leaves the prompt rows among the keys, which no consumer here is defined on")
         Pz = self.patch_size
         hp, wp = (img.shape[2] + Pz - 1) // Pz, (img.shape[3] + Pz - 1) // Pz
         pos_in = None
@@ -658,10 +668,15 @@ class MaskClipVisionTransformer(nn.Module):
             pos_in = _PosResizeFn.apply(self.pos_embed, self._pos_resize_matrix((hp, wp)))
             tr = [p for p in tr if p is not self.pos_embed]
         if torch.is_grad_enabled() and (tr or (pos_in is not None and pos_in.requires_grad)):
+            if need_k:
+                raise ValueError("MaskClipVisionTransformer.forward_tokens(need_k=True): autograd is enabled and the encoder "
+                                 "has trainable tensors; the keys are gradient-free (call it under torch.no_grad())")
             outs = _EncoderFn.apply(self, img, need_global, pos_in, *tr)
         else:
             with ops.prof_scope("vit"):
-                outs = _encoder_forward(self, img, need_global, None, pos_in)
+                outs = _encoder_forward(self, img, need_global, None, pos_in, need_k=need_k)
+        if need_k:
+            return list(outs[:-2]), outs[-2], outs[-1]
         n = len(outs) - 1
         return list(outs[:n]), outs[n]
 
@@ -692,7 +707,7 @@ def _drop_path_masks(m, i, B, want_v, skip_x, dev):
     return dp
 
 
-def _encoder_forward(m, img, need_global, saved, pos_in=None):
+def _encoder_forward(m, img, need_global, saved, pos_in=None, need_k=False):
     assert img.is_cuda and img.dtype == torch.float32
     img = img.contiguous()
     B, Cin, H, W = img.shape
@@ -744,7 +759,9 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         pl = layer.plist() if layer.lora is None else layer.merged_plist()
         if P and i > 0:     # in place on the block above's output (no block keeps its own output for its backward)
             ops.prompt_rows_fwd(pemb[i * P:(i + 1) * P], B, P, x, mask=pmasks[i], scale=pscale)
-        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, TT, want_v, skip_x, sv, dp=_drop_path_masks(m, i, B, want_v, skip_x, dev))
+        k_out = [] if need_k and last else None
+        xo, v = block_forward(x, pl, m.num_heads, m.eps, B, TT, want_v, skip_x, sv, dp=_drop_path_masks(m, i, B, want_v, skip_x, dev),
+                              k_out=k_out)
         if saved is not None:
             if layer.lora is not None:
                 sv["plist"] = pl      # the backward's input-gradient GEMMs run on the same effective weights
@@ -776,6 +793,8 @@ def _encoder_forward(m, img, need_global, saved, pos_in=None):
         ops.copy2d(xn, 0, 1, TT * E, 0, c, 0, 1, E, 0, B, E)
         gp = ops.linear(c, wproj)
         glob, _ = ops.l2norm_fwd(gp, 0.0)
+    if need_k:      # k[:, 1:] (maskclip_vit.py:570); P == 0 here (forward_tokens refuses prompts)
+        return tuple(feats) + (glob, ops.group_rows(k_out[0], B, TT, 1, NP).view(B, NP, E))
     return tuple(feats) + (glob,)
 
 

@@ -629,6 +629,16 @@ def copy2d(src, s_off, sgrp, src_go, src_ld, dst, d_off, dgrp, dst_go, dst_ld, r
                                     1 if accumulate else 0, _st()), "svl_copy2d_f32")
 
 
+def group_rows(src, groups, rows_per_group, first, count):
+    """Rows [first, first + count) of every group of `rows_per_group` rows of src [groups * rows_per_group, C], gathered into a
+    contiguous [groups * count, C] (t.view(g, r, C)[:, first:first + count] on svl_copy2d_f32: the class-token row dropped)."""
+    Cc = src.shape[1]
+    assert src.is_contiguous() and src.shape[0] == groups * rows_per_group and 0 <= first and first + count <= rows_per_group
+    out = empty(groups * count, Cc, device=src.device)
+    copy2d(src, first * Cc, count, rows_per_group * Cc, Cc, out, 0, count, count * Cc, Cc, groups * count, Cc)
+    return out
+
+
 def matmul_nn(a, b, out=None, accumulate=False, dact=ACT_NONE, z=None, planes_only=False):
     """out[M,N] = a[M,K] @ b[K,N]  (dgrad: dY @ W with W [out,in]).  `dact` = ACT_MUL_DGELU / ACT_MUL_DRELU multiplies
     the result by the activation derivative at the saved pre-activation `z` [M,N] in the epilogue.  `a` may be Planes;
@@ -1830,6 +1840,97 @@ def concept_max(pred, offsets_i32, N):
     out = empty(Bn, N, *pred.shape[2:], device=pred.device)
     L.check(L.load().svl_concept_max_f32(_p(pred), Bn, NC, HW, _p(offsets_i32), N, _p(out), _st()),
             "svl_concept_max_f32")
+    return out
+
+
+def _mc_rows(t, B, HW, what):
+    _chk(t)
+    assert t.dim() == 2 and t.shape[0] == B * HW and t.stride(1) == 1 and t.stride(0) >= t.shape[1], (what, t.shape, t.stride())
+    return t
+
+
+def mc_class_peak(p, B, HW):
+    """peak [B, N] = per-image column maxima of p [B * HW, N] (row stride p.stride(0)); a NaN in a column gives NaN."""
+    _mc_rows(p, B, HW, "p")
+    peak = empty(B, p.shape[1], device=p.device)
+    L.check(L.load().svl_mc_class_peak_f32(_p(p), p.stride(0), B, HW, p.shape[1], _p(peak), _st()), "svl_mc_class_peak_f32")
+    return peak
+
+
+def col_invsq(k, B, HW, eps=1e-12):
+    """s [B, E] = 1 / max(||k[b, :, c]||_2, eps)^2 for k [B * HW, E]: the square of the column scale F.normalize(k, p=2)
+    applies to k [B, HW, E] with torch's default dim = 1."""
+    _mc_rows(k, B, HW, "k")
+    s = empty(B, k.shape[1], device=k.device)
+    L.check(L.load().svl_col_invsq_f32(_p(k), k.stride(0), B, HW, k.shape[1], float(eps), _p(s), _st()), "svl_col_invsq_f32")
+    return s
+
+
+def mc_softmax(x, B, HW, peak=None, pd_thresh=0.0, fill_only=False, want_rowmax=True, out=None):
+    """(P, rowmax): P = softmax(100 x') over the classes of x [B * HW, N], x' = x with the classes whose peak [B, N] is below
+    pd_thresh at -100, rowmax [B * HW] = max_c P.  fill_only: P = x' itself, rowmax None."""
+    _mc_rows(x, B, HW, "x")
+    N = x.shape[1]
+    P = out if out is not None else empty(B * HW, N, device=x.device)
+    _mc_rows(P, B, HW, "P")
+    rowmax = empty(B * HW, device=x.device) if want_rowmax and not fill_only else None
+    L.check(L.load().svl_mc_softmax_f32(_p(x), x.stride(0), _p(peak), float(pd_thresh), B, HW, N, 1 if fill_only else 0,
+                                        _p(P), P.stride(0), _p(rowmax), _st()), "svl_mc_softmax_f32")
+    return P, rowmax
+
+
+def mc_select(P, B, HW, O=None, rowmax=None, ks_thresh=0.0, out=None):
+    """out [B, N, HW] (class planes) = rowmax < ks_thresh ? O : P, row by row; O = rowmax = None: P's transpose alone."""
+    _mc_rows(P, B, HW, "P")
+    N = P.shape[1]
+    if out is None:
+        out = empty(B, N, HW, device=P.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * N * HW
+    L.check(L.load().svl_mc_select_f32(_p(P), P.stride(0), _p(O), O.stride(0) if O is not None else 0, _p(rowmax),
+                                       float(ks_thresh), B, HW, N, _p(out), _st()), "svl_mc_select_f32")
+    return out
+
+
+def mc_smooth(P, k, s, B, HW):
+    """O [B * HW, N] = k^ (k^^T P) per image on two svl_gemm_f32 launches (batch = B), k^ = k sqrt(s): (k^ k^^T) P without the
+    HW x HW matrix.  The scale s [B, E] goes onto the N x E intermediate (svl_chanmask_f32), the smallest tensor in sight."""
+    N, E = P.shape[1], k.shape[1]
+    tt = empty(B * N, E, device=P.device)           # (P^T k)[b]: [N, E]
+    gemm(A_MC, B_NC, N, E, HW, Op(P, P.stride(0), 0, HW * P.stride(0)), Op(k, k.stride(0), 0, HW * k.stride(0)), tt, batch=B,
+         c_bso=N * E)
+    ts = chanmask(tt, s, 1.0, N)
+    O = empty(B * HW, N, device=P.device)
+    gemm(A_KC, B_KC, HW, N, E, Op(k, k.stride(0), 0, HW * k.stride(0)), Op(ts, E, 0, N * E), O, batch=B, c_bso=HW * N)
+    return O
+
+
+def mc_refine(x, k, B, HW, pd_thresh, ks_thresh, out=None, return_parts=False):
+    """MaskCLIP's prompt denoising and key smoothing (maskclip_head.py:129-155) on cosine logits x [B * HW, N] and the last
+    block's keys k [B * HW, E] or None -> class planes [B, N, HW]:
+      pd_thresh > 0: every class whose peak softmax(100 x) probability over the image's tokens is < pd_thresh is set to -100;
+      ks_thresh > 0 and k given: P = softmax(100 x'); rows with max_c P < ks_thresh become (k^ k^^T P), k^ = F.normalize(k, p=2)
+      on [B, HW, E] with torch's default dim = 1 (each channel over the tokens of its image).  The output is then P, not logits.
+    Both off: x's bits; pd_thresh alone: x with the -100 columns.  The two products run in the process's GEMM arithmetic mode.
+    return_parts: also dict(P, rowmax, peak, s, selected) (None for a stage that did not run)."""
+    for name, v in (("pd_thresh", pd_thresh), ("ks_thresh", ks_thresh)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v >= 0:
+            raise ValueError(f"ops.mc_refine: {name} must be a real number >= 0, got {v!r}")
+    _mc_rows(x, B, HW, "x")
+    smooth = ks_thresh > 0 and k is not None
+    P, rowmax, peak, s, O = x, None, None, None, None
+    if pd_thresh > 0:
+        P, _ = mc_softmax(x, B, HW, want_rowmax=False)
+        peak = mc_class_peak(P, B, HW)
+    if smooth:
+        _mc_rows(k, B, HW, "k")
+        P, rowmax = mc_softmax(x, B, HW, peak, pd_thresh, out=P if P is not x else None)
+        s = col_invsq(k, B, HW)
+        O = mc_smooth(P, k, s, B, HW)
+    elif pd_thresh > 0:
+        P, _ = mc_softmax(x, B, HW, peak, pd_thresh, fill_only=True, out=P)
+    out = mc_select(P, B, HW, O, rowmax, ks_thresh, out)
+    if return_parts:
+        return out, dict(P=P, rowmax=rowmax, peak=peak, s=s, selected=rowmax < ks_thresh if smooth else None)
     return out
 
 

@@ -213,6 +213,15 @@ _HEAD_RESTORE_SEMIVL = ("remat", "chunk_class_images")
 _HEAD_RESTORE_SUPERVISED = _HEAD_RESTORE_SEMIVL + ("act_limit_bytes",)
 
 
+def _refuse_untrainable_head(model, step):
+    """A head that declares `trainable = False` (MaskClip2Head; the reference's forward_train raises, maskclip2_head.py:35-36)
+    is refused before the step touches the model, the optimizer or the batch."""
+    head = getattr(model, "decode_head", None)
+    if head is not None and getattr(head, "trainable", True) is False:
+        raise ValueError(f"{step}: the decode head {type(head).__name__} is not trainable (zero-shot MaskCLIP has no training "
+                         f"step; evaluate it with evaluate / tools.eval)")
+
+
 @contextlib.contextmanager
 def _step_scope(model, head_attrs):
     """The per-step overrides of a training step (ops.WGRAD_STREAM, the decode head's `head_attrs` and its per-step memory
@@ -270,6 +279,7 @@ def semivl_train_step(model, batch, iters, total_iters, cfg, optimizer=None, red
     four images after CutMix, the label maps of the logits of x, s1, s2 and w_fp through the step's own _smax(pred, s.up)
     (the kernel that makes mask_w: a tile shows what the step would train on), mask_x, the two mixed pseudo-label maps and
     mask_w, and when guided the two mixed guidance maps and mclip.  Nothing the step computes reads the canvas."""
+    _refuse_untrainable_head(model, "semivl_train_step")
     with _step_scope(model, _HEAD_RESTORE_SEMIVL):
         return _semivl_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, fp_masks, return_aux,
                                   teacher, monitor, panel)
@@ -292,6 +302,7 @@ def supervised_train_step(model, batch, iters, total_iters, cfg, optimizer=None,
     `head_remat`, `head_chunk_class_images`, `act_mem_fraction`) are set up for one decode of B samples and undone when
     the step ends -- also when it raises -- as in semivl_train_step.  `teacher` (ema.EmaTeacher or None): there are no
     pseudo-labels here, the step only maintains it -- teacher.update_buffers after optimizer.step()."""
+    _refuse_untrainable_head(model, "supervised_train_step")
     with _step_scope(model, _HEAD_RESTORE_SUPERVISED):
         return _supervised_train_step(model, batch, iters, total_iters, cfg, optimizer, reducer, return_aux, teacher)
 
