@@ -2,6 +2,7 @@
 // Reference math: semivl.py:232,252 (softmax-max), utils/train_utils.py:19-49 (cutmix, confidence weighting),
 // semivl.py:52-58 (mc loss), semivl.py:267-323 (loss assembly), vlm.py:100-109 (MaskCLIP label tail).
 #include "svl_common.h"
+#include "bilinear_index.h"
 
 namespace {
 
@@ -32,15 +33,7 @@ __global__ __launch_bounds__(256) void softmax_max_kernel(const float* __restric
         x[0] = base[(long)c * HW];
       }
 #pragma unroll
-      for (int j = 0; j < PX; ++j) {
-        if (x[j] > m[j]) {
-          s[j] = s[j] * expf(m[j] - x[j]) + 1.f;
-          m[j] = x[j];
-          idx[j] = c;
-        } else {
-          s[j] += expf(x[j] - m[j]);
-        }
-      }
+      for (int j = 0; j < PX; ++j) softmax_max_step(x[j], c, m[j], s[j], idx[j]);
     }
     const long o = b * HW + p;
     if constexpr (VEC) {
@@ -481,21 +474,11 @@ __global__ void semivl_loss_kernel(const double* sums, double numel_u, float lam
 // ------------------------------------------------------------------------------------------------
 // MaskCLIP label tail: upsample (align_corners=False) -> softmax(scale*x) -> max -> threshold -> ignore.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, bool align, int& i0, int& i1, float& l0,
-                                          float& l1) {
-  float s = align ? scale * dst : scale * (dst + 0.5f) - 0.5f;
-  if (!align && s < 0.f) s = 0.f;
-  i0 = min((int)s, in_size - 1);
-  i1 = min(i0 + 1, in_size - 1);
-  l1 = fminf(fmaxf(s - i0, 0.f), 1.f);
-  l0 = 1.f - l1;
-}
-
 __global__ __launch_bounds__(256) void maskclip_labels_kernel(const float* __restrict__ dense, int B, int N, int h,
                                                               int w, int H, int W, float lscale, float thresh,
                                                               const int64_t* __restrict__ ign,
                                                               int64_t* __restrict__ out) {
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  const float sh = area_scale(h, H, false), sw = area_scale(w, W, false);
   const long total = (long)B * H * W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int ox = (int)(i % W);
@@ -513,14 +496,7 @@ __global__ __launch_bounds__(256) void maskclip_labels_kernel(const float* __res
       const float* pl = base + (long)c * h * w;
       const float v = ly0 * (lx0 * pl[y0 * w + x0] + lx1 * pl[y0 * w + x1]) +
                       ly1 * (lx0 * pl[y1 * w + x0] + lx1 * pl[y1 * w + x1]);
-      const float x = lscale * v;
-      if (x > m) {
-        s = s * expf(m - x) + 1.f;
-        m = x;
-        idx = c;
-      } else {
-        s += expf(x - m);
-      }
+      softmax_max_step(lscale * v, c, m, s, idx);
     }
     const float conf = 1.f / s;
     int64_t lab = (conf < thresh) ? 255 : idx;
@@ -591,6 +567,39 @@ inline int ce_tile_pixels(int N) {     // 256, 128 or 64 pixels: the [N][P] tile
   return P >= 256 ? 256 : (P >= 128 ? 128 : (P >= 64 ? 64 : 0));
 }
 
+// The argument checks of svl_ce_fused_f32 and, with `eps` (its label_smoothing), of svl_ce_fused_lsw_f32, in one order and
+// under the entry point's name.
+int ce_check(const char* fn, const svl_ce_desc* d, const float* eps) {
+  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "%s: null args", fn);
+  SVL_CHECK_ARG(d->B > 0 && d->N > 0 && d->HW > 0, "%s: bad sizes", fn);
+  if (eps) {
+    const int rc = svl_ce_lsw_check(fn, d, *eps);
+    if (rc) return rc;
+  } else {
+    SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "%s: conf and ign go together", fn);
+  }
+  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "%s: gscale required with dlogits", fn);
+  SVL_CHECK_ARG(ce_tile_pixels(d->N) >= 64, "%s: N=%d too large for the LDS tile", fn, d->N);
+  return SVL_OK;
+}
+// descriptor -> kernel parameters, with the tiling of its N
+void ce_fill(CeP& p, const svl_ce_desc* d) {
+  p.logits = d->logits; p.B = d->B; p.N = d->N; p.HW = d->HW;
+  p.target = d->target; p.use_ignore_t = d->use_ignore_t;
+  p.conf = d->conf; p.ign = d->ign; p.conf_thresh = d->conf_thresh; p.all_pixels = d->all_pixels;
+  p.mc = d->mc_target; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
+  p.img_weight = d->img_weight;
+  p.P = ce_tile_pixels(d->N);
+  p.blocks_per_img = (d->HW + p.P - 1) / p.P;
+}
+template <bool LSW>
+int ce_launch(const char* fn, const typename ce_param<LSW>::type& p, svl_stream_t stream) {
+  hipLaunchKernelGGL(ce_fused_kernel<LSW>, dim3((unsigned)((long)p.B * p.blocks_per_img)), dim3(256),
+                     (size_t)p.N * p.P * sizeof(float), (hipStream_t)stream, p);
+  SVL_LAUNCH_CHECK(fn);
+  return SVL_OK;
+}
+
 }  // namespace
 
 extern "C" int svl_softmax_max_f32(const float* logits, int B, int N, int64_t HW, float* conf, int64_t* label,
@@ -641,57 +650,21 @@ extern "C" int64_t svl_ce_num_blocks(int B, int N, int64_t HW) {
 }
 
 extern "C" int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t stream) {
-  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_fused_f32: null args");
-  SVL_CHECK_ARG(d->B > 0 && d->N > 0 && d->HW > 0, "svl_ce_fused_f32: bad sizes");
-  SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "svl_ce_fused_f32: conf and ign go together");
-  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_fused_f32: gscale required with dlogits");
-  const int P = ce_tile_pixels(d->N);
-  SVL_CHECK_ARG(P >= 64, "svl_ce_fused_f32: N=%d too large for the LDS tile", d->N);
+  const int rc = ce_check("svl_ce_fused_f32", d, nullptr);
+  if (rc) return rc;
   CeP p;
-  p.logits = d->logits; p.B = d->B; p.N = d->N; p.HW = d->HW;
-  p.target = d->target; p.use_ignore_t = d->use_ignore_t;
-  p.conf = d->conf; p.ign = d->ign; p.conf_thresh = d->conf_thresh; p.all_pixels = d->all_pixels;
-  p.mc = d->mc_target; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
-  p.img_weight = d->img_weight;
-  p.P = P;
-  p.blocks_per_img = (d->HW + P - 1) / P;
-  const long nblk = (long)d->B * p.blocks_per_img;
-  const size_t lds = (size_t)d->N * P * sizeof(float);
-  hipLaunchKernelGGL(ce_fused_kernel<false>, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
-  SVL_LAUNCH_CHECK("svl_ce_fused_f32");
-  return SVL_OK;
+  ce_fill(p, d);
+  return ce_launch<false>("svl_ce_fused_f32", p, stream);
 }
 
 extern "C" int svl_ce_fused_lsw_f32(const svl_ce_desc* d, float label_smoothing, const float* class_weight,
                                     svl_stream_t stream) {
-  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_fused_lsw_f32: null args");
-  SVL_CHECK_ARG(d->B > 0 && d->N > 0 && d->HW > 0, "svl_ce_fused_lsw_f32: bad sizes");
-  SVL_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "svl_ce_fused_lsw_f32: label_smoothing=%g outside [0, 1]",
-                (double)label_smoothing);
-  // labelled branch only
-  SVL_CHECK_ARG(d->conf == nullptr, "svl_ce_fused_lsw_f32: conf must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->ign == nullptr, "svl_ce_fused_lsw_f32: ign must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->mc_target == nullptr, "svl_ce_fused_lsw_f32: mc_target must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->img_weight == nullptr, "svl_ce_fused_lsw_f32: img_weight must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->all_pixels == 0, "svl_ce_fused_lsw_f32: all_pixels must be 0 (labelled branch only)");
-  SVL_CHECK_ARG(d->use_ignore_t != 0, "svl_ce_fused_lsw_f32: use_ignore_t must be 1 (labelled branch only)");
-  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_fused_lsw_f32: gscale required with dlogits");
-  const int P = ce_tile_pixels(d->N);
-  SVL_CHECK_ARG(P >= 64, "svl_ce_fused_lsw_f32: N=%d too large for the LDS tile", d->N);
+  const int rc = ce_check("svl_ce_fused_lsw_f32", d, &label_smoothing);
+  if (rc) return rc;
   CeLswP p;
-  p.logits = d->logits; p.B = d->B; p.N = d->N; p.HW = d->HW;
-  p.target = d->target; p.use_ignore_t = 1;
-  p.conf = nullptr; p.ign = nullptr; p.conf_thresh = 0.f; p.all_pixels = 0;
-  p.mc = nullptr; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
-  p.img_weight = nullptr;
-  p.P = P;
-  p.blocks_per_img = (d->HW + P - 1) / P;
+  ce_fill(p, d);
   p.eps = label_smoothing; p.cw = class_weight;
-  const long nblk = (long)d->B * p.blocks_per_img;
-  const size_t lds = (size_t)d->N * P * sizeof(float);
-  hipLaunchKernelGGL(ce_fused_kernel<true>, dim3((unsigned)nblk), dim3(256), lds, (hipStream_t)stream, p);
-  SVL_LAUNCH_CHECK("svl_ce_fused_lsw_f32");
-  return SVL_OK;
+  return ce_launch<true>("svl_ce_fused_lsw_f32", p, stream);
 }
 
 extern "C" int64_t svl_class_weight_sum_ws_doubles(int64_t n) { return n > 0 ? CW_CHUNKS : 0; }

@@ -13,6 +13,7 @@
 // gradient is ONE thread's sum over the pixels of its footprint in fixed (row, column) order -- halo pixels are evaluated
 // by each block that needs them instead of being exchanged through atomics.
 #include "svl_common.h"
+#include "bilinear_index.h"
 #include <atomic>
 #include <stdlib.h>
 
@@ -56,21 +57,8 @@ template <bool LSW> struct up_param { using type = UpP; };
 template <> struct up_param<true> { using type = UpLswP; };
 constexpr int UP_MAX_N = 160;   // class counts the resize-fused kernels take (up_ok)
 
-__device__ __host__ inline float up_scale(int in, int out, bool align) {
-  if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  return (float)in / (float)out;
-}
 __device__ __host__ inline int imin_(int a, int b) { return a < b ? a : b; }
 __device__ __host__ inline int imax_(int a, int b) { return a > b ? a : b; }
-// ATen: area_pixel_compute_source_index + guard_index_and_lambda (the same function as resample.hip's)
-__device__ __host__ inline void up_src(int dst, float scale, int in_size, bool align, int& i0, int& i1, float& l0, float& l1) {
-  float s = align ? scale * dst : scale * (dst + 0.5f) - 0.5f;
-  if (!align && s < 0.f) s = 0.f;
-  i0 = imin_((int)s, in_size - 1);
-  i1 = imin_(i0 + 1, in_size - 1);
-  l1 = fminf(fmaxf(s - i0, 0.f), 1.f);
-  l0 = 1.f - l1;
-}
 // One axis of a block: owned cells [c0, c1), staged cells [s0, s0 + ns), evaluated destination indices [r0, r0 + nr).
 // HALO: every destination index one of whose taps is an owned cell (gradient gather); else: those whose FIRST tap is.
 // (host + device: svl_ce_up_num_blocks runs the same function over all tiles to check nr <= RMAX)
@@ -87,7 +75,7 @@ __device__ __host__ inline void up_axis(int tile, int in, int out, float scale, 
   for (; lo < out - 1; ++lo) {
     int i0, i1;
     float l0, l1;
-    up_src(lo, scale, in, align, i0, i1, l0, l1);
+    src_index(lo, scale, in, align, i0, i1, l0, l1);
     if ((HALO ? i1 : i0) >= c0) break;
   }
   int hi = (int)ceilf((float)(c1 + off) / scale - off) + 2;
@@ -95,7 +83,7 @@ __device__ __host__ inline void up_axis(int tile, int in, int out, float scale, 
   for (; hi > lo; --hi) {
     int i0, i1;
     float l0, l1;
-    up_src(hi, scale, in, align, i0, i1, l0, l1);
+    src_index(hi, scale, in, align, i0, i1, l0, l1);
     if (i0 <= c1 - 1) break;
   }
   r0 = lo;
@@ -120,23 +108,35 @@ __device__ __forceinline__ void up_online(float x, float& m, float& s) {
   m = fmaxf(m, x);
 }
 
-// ------------------------------------------------------------------------------------------------
-// softmax-max of the resized logits: conf = 1 / sum_c exp(x_c - max), label = first argmax.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_max_up_kernel(const UpP p) {
-  extern __shared__ __attribute__((aligned(16))) float tile[];   // [N][CSTR]
+// A block after up_prologue: its image b; per axis the owned cells [c0, c1), the first staged cell s0 and the evaluated
+// destination indices [r0, r0 + nr); the tap tables (LDS) of evaluated row r / column q: both source taps and their weights.
+struct UpBlock {
+  int b, c0y, c1y, s0y, r0y, nry, c0x, c1x, s0x, r0x, nrx;
+  const int *ry0, *ry1, *cx0, *cx1;
+  const float *rl0, *rl1, *cl0, *cl1;
+  // whether the pixel with upper-left tap (y0, x0) is counted by this block (else: by a neighbour)
+  __device__ __forceinline__ bool owns(int y0, int x0) const { return y0 >= c0y && y0 < c1y && x0 >= c0x && x0 < c1x; }
+  // index of evaluated pixel (r, q) in a [B, H, W] map
+  __device__ __forceinline__ long pixel(const UpP& p, int r, int q) const {
+    return (long)b * p.H * p.W + (long)(r0y + r) * p.W + (r0x + q);
+  }
+};
+// What every kernel here starts with: block -> (image, tile), up_axis on both axes, the tap tables, and the block's cells of
+// all N classes staged as tile[N][CSTR] (BASE2: multiplied by log2(e)).  THREADS = blockDim.x; the caller places the barrier.
+template <bool HALO, int THREADS, bool BASE2>
+__device__ __forceinline__ UpBlock up_prologue(const UpP& p, float* __restrict__ tile) {
   __shared__ int ry0[RMAX], ry1[RMAX], cx0[RMAX], cx1[RMAX];
   __shared__ float rl0[RMAX], rl1[RMAX], cl0[RMAX], cl1[RMAX];
   const int tid = threadIdx.x;
   const int per = p.ncy * p.ncx;
   const int b = blockIdx.x / per, rem = blockIdx.x - b * per;
   const int ty = rem / p.ncx, tx = rem - ty * p.ncx;
-  const float sh = up_scale(p.h, p.H, p.align), sw = up_scale(p.w, p.W, p.align);
+  const float sh = area_scale(p.h, p.H, p.align), sw = area_scale(p.w, p.W, p.align);
   int c0y, c1y, s0y, nsy, r0y, nry, c0x, c1x, s0x, nsx, r0x, nrx;
-  up_axis<false>(ty, p.h, p.H, sh, p.align, c0y, c1y, s0y, nsy, r0y, nry);
-  up_axis<false>(tx, p.w, p.W, sw, p.align, c0x, c1x, s0x, nsx, r0x, nrx);
-  if (tid < nry) up_src(r0y + tid, sh, p.h, p.align, ry0[tid], ry1[tid], rl0[tid], rl1[tid]);
-  else if (tid >= 64 && tid < 64 + nrx) up_src(r0x + tid - 64, sw, p.w, p.align, cx0[tid - 64], cx1[tid - 64], cl0[tid - 64], cl1[tid - 64]);
+  up_axis<HALO>(ty, p.h, p.H, sh, p.align, c0y, c1y, s0y, nsy, r0y, nry);
+  up_axis<HALO>(tx, p.w, p.W, sw, p.align, c0x, c1x, s0x, nsx, r0x, nrx);
+  if (tid < nry) src_index(r0y + tid, sh, p.h, p.align, ry0[tid], ry1[tid], rl0[tid], rl1[tid]);
+  else if (tid >= 64 && tid < 64 + nrx) src_index(r0x + tid - 64, sw, p.w, p.align, cx0[tid - 64], cx1[tid - 64], cl0[tid - 64], cl1[tid - 64]);
   {
     const int cell = tid & 127, cl = tid >> 7;
     if (cell < (nsy + 1) * (nsx + 1)) {
@@ -144,32 +144,35 @@ __global__ __launch_bounds__(256) void softmax_max_up_kernel(const UpP p) {
       const float* g = p.logits + (long)b * p.N * p.h * p.w + (long)imin_(s0y + cr, p.h - 1) * p.w + imin_(s0x + cc, p.w - 1);
       float* d = tile + cr * LR + cc;
       const long hw = (long)p.h * p.w;
-      for (int c = cl; c < p.N; c += 2) d[c * CSTR] = g[c * hw];
+      for (int c = cl; c < p.N; c += THREADS / 128) d[c * CSTR] = BASE2 ? g[c * hw] * LOG2E : g[c * hw];
     }
   }
+  return {b, c0y, c1y, s0y, r0y, nry, c0x, c1x, s0x, r0x, nrx, ry0, ry1, cx0, cx1, rl0, rl1, cl0, cl1};
+}
+__device__ __forceinline__ Taps up_taps(const UpBlock& g, int r, int q) {
+  Taps k;
+  k.o00 = (g.ry0[r] - g.s0y) * LR + (g.cx0[q] - g.s0x);
+  k.o10 = (g.ry1[r] - g.s0y) * LR + (g.cx0[q] - g.s0x);
+  k.ly0 = g.rl0[r]; k.ly1 = g.rl1[r]; k.lx0 = g.cl0[q]; k.lx1 = g.cl1[q];
+  return k;
+}
+
+// ------------------------------------------------------------------------------------------------
+// softmax-max of the resized logits: conf = 1 / sum_c exp(x_c - max), label = first argmax.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void softmax_max_up_kernel(const UpP p) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];   // [N][CSTR]
+  const UpBlock g = up_prologue<false, 256, false>(p, tile);
   __syncthreads();
-  const int npx = nry * nrx;
-  for (int px = tid; px < npx; px += 256) {
-    const int r = px / nrx, q = px - r * nrx;
-    const int y0 = ry0[r], x0 = cx0[q];
-    if (y0 < c0y || y0 >= c1y || x0 < c0x || x0 >= c1x) continue;   // (owned by a neighbour)
-    Taps k;
-    k.o00 = (y0 - s0y) * LR + (x0 - s0x);
-    k.o10 = (ry1[r] - s0y) * LR + (x0 - s0x);
-    k.ly0 = rl0[r]; k.ly1 = rl1[r]; k.lx0 = cl0[q]; k.lx1 = cl1[q];
+  const int npx = g.nry * g.nrx;
+  for (int px = threadIdx.x; px < npx; px += 256) {
+    const int r = px / g.nrx, q = px - r * g.nrx;
+    if (!g.owns(g.ry0[r], g.cx0[q])) continue;   // (owned by a neighbour)
+    const Taps k = up_taps(g, r, q);
     float m = -INFINITY, s = 0.f;
     int idx = 0;
-    for (int c = 0; c < p.N; ++c) {
-      const float x = up_interp(tile + c * CSTR, k);
-      if (x > m) {
-        s = s * expf(m - x) + 1.f;
-        m = x;
-        idx = c;
-      } else {
-        s += expf(x - m);
-      }
-    }
-    const long o = (long)b * p.H * p.W + (long)(r0y + r) * p.W + (r0x + q);
+    for (int c = 0; c < p.N; ++c) softmax_max_step(up_interp(tile + c * CSTR, k), c, m, s, idx);
+    const long o = g.pixel(p, r, q);
     p.conf_out[o] = 1.f / s;
     p.label_out[o] = idx;
   }
@@ -183,42 +186,17 @@ __global__ __launch_bounds__(256) void softmax_max_up_kernel(const UpP p) {
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void target_prob_up_kernel(const UpP p, float* __restrict__ prob) {
   extern __shared__ __attribute__((aligned(16))) float tile[];   // [N][CSTR]
-  __shared__ int ry0[RMAX], ry1[RMAX], cx0[RMAX], cx1[RMAX];
-  __shared__ float rl0[RMAX], rl1[RMAX], cl0[RMAX], cl1[RMAX];
-  const int tid = threadIdx.x;
-  const int per = p.ncy * p.ncx;
-  const int b = blockIdx.x / per, rem = blockIdx.x - b * per;
-  const int ty = rem / p.ncx, tx = rem - ty * p.ncx;
-  const float sh = up_scale(p.h, p.H, p.align), sw = up_scale(p.w, p.W, p.align);
-  int c0y, c1y, s0y, nsy, r0y, nry, c0x, c1x, s0x, nsx, r0x, nrx;
-  up_axis<false>(ty, p.h, p.H, sh, p.align, c0y, c1y, s0y, nsy, r0y, nry);
-  up_axis<false>(tx, p.w, p.W, sw, p.align, c0x, c1x, s0x, nsx, r0x, nrx);
-  if (tid < nry) up_src(r0y + tid, sh, p.h, p.align, ry0[tid], ry1[tid], rl0[tid], rl1[tid]);
-  else if (tid >= 64 && tid < 64 + nrx) up_src(r0x + tid - 64, sw, p.w, p.align, cx0[tid - 64], cx1[tid - 64], cl0[tid - 64], cl1[tid - 64]);
-  {
-    const int cell = tid & 127, cl = tid >> 7;
-    if (cell < (nsy + 1) * (nsx + 1)) {
-      const int cr = cell / (nsx + 1), cc = cell - cr * (nsx + 1);
-      const float* g = p.logits + (long)b * p.N * p.h * p.w + (long)imin_(s0y + cr, p.h - 1) * p.w + imin_(s0x + cc, p.w - 1);
-      float* d = tile + cr * LR + cc;
-      const long hw = (long)p.h * p.w;
-      for (int c = cl; c < p.N; c += 2) d[c * CSTR] = g[c * hw] * LOG2E;
-    }
-  }
+  const UpBlock g = up_prologue<false, 256, true>(p, tile);
   __syncthreads();
-  const int npx = nry * nrx;
-  for (int px = tid; px < npx; px += 256) {
-    const int r = px / nrx, q = px - r * nrx;
-    const int y0 = ry0[r], x0 = cx0[q];
-    if (y0 < c0y || y0 >= c1y || x0 < c0x || x0 >= c1x) continue;   // (owned by a neighbour)
-    const long o = (long)b * p.H * p.W + (long)(r0y + r) * p.W + (r0x + q);
+  const int npx = g.nry * g.nrx;
+  for (int px = threadIdx.x; px < npx; px += 256) {
+    const int r = px / g.nrx, q = px - r * g.nrx;
+    if (!g.owns(g.ry0[r], g.cx0[q])) continue;   // (owned by a neighbour)
+    const long o = g.pixel(p, r, q);
     const long t = p.target[o];
     float pr = 1.f;
     if (t != 255) {
-      Taps k;
-      k.o00 = (y0 - s0y) * LR + (x0 - s0x);
-      k.o10 = (ry1[r] - s0y) * LR + (x0 - s0x);
-      k.ly0 = rl0[r]; k.ly1 = rl1[r]; k.lx0 = cl0[q]; k.lx1 = cl1[q];
+      const Taps k = up_taps(g, r, q);
       float m = -INFINITY, s = 0.f;
       for (int c = 0; c < p.N; ++c) up_online(up_interp(tile + c * CSTR, k), m, s);
       const float lse = m + log2f(s);
@@ -241,11 +219,80 @@ __global__ __launch_bounds__(256) void target_prob_up_kernel(const UpP p, float*
 // The pixel arrays hold a and b where the plain kernel holds g_t and g_m; e is one number per launch and applies exactly where
 // the stored target index is >= 0, so no further per-pixel state is needed.  partials = { sum numerator, 0, 0, sum [t != 255] w_t }.
 // ------------------------------------------------------------------------------------------------
+// Phase A's pixel body, one per instantiation: px's log-sum-exp, its two gradient coefficients and its (target | guidance
+// << 16) indices into the pixel arrays, and -- where the block owns the pixel -- its terms into the four block sums.
+struct UpPix {
+  float *lse, *gt, *gm;   // [pstr] each
+  int* ix;
+};
+struct UpSums {
+  float s_t = 0.f, s_m = 0.f, s_c = 0.f, n_v = 0.f;
+};
+// per launch: the two gradient scales (0 without dlogits); plain: the image's weight; LSW: 1 - eps, eps / N, W
+struct UpConsts {
+  float g0, g1, iw, om, en, wsum;
+};
+// the pixel's maps: target t; with p.conf its confidence cf and ignore label ig, with p.mc its guidance label mm
+__device__ __forceinline__ void ce_up_pixel(const UpP& p, const float* tile, const Taps& k, bool owned, long t, long ig,
+                                            float cf, long mm, int px, const UpConsts& u, const UpPix& st, UpSums& a) {
+  float m = -INFINITY, s = 0.f;
+  for (int c = 0; c < p.N; ++c) {
+    up_online(up_interp(tile + c * CSTR, k), m, s);
+  }
+  const float lse = m + log2f(s);                 // (base 2, like the staged logits)
+  const bool t_ok = !(p.use_ignore_t && t == 255);
+  const int ti = t_ok ? (int)t : -1;
+  const int mi = mm != 255 ? (int)mm : -1;        // (255 without a guidance map)
+  float w = 1.f;
+  bool valid = t_ok;
+  float sc = 0.f;
+  if (p.conf) {
+    const bool v = ig != 255;
+    w = p.all_pixels ? 1.f : ((cf >= p.conf_thresh && v) ? 1.f : 0.f);
+    w *= u.iw;
+    valid = v;
+    sc = v ? cf : 0.f;
+  }
+  if (owned) {
+    const float xt = (ti >= 0 && ti < p.N) ? up_interp(tile + ti * CSTR, k) : 0.f;
+    const float xm = (mi >= 0 && mi < p.N) ? up_interp(tile + mi * CSTR, k) : 0.f;
+    a.n_v += valid ? 1.f : 0.f;
+    a.s_t += t_ok ? w * (LN2 * (lse - xt)) : 0.f;
+    a.s_m += mi >= 0 ? LN2 * (lse - xm) : 0.f;
+    a.s_c += sc;
+  }
+  st.lse[px] = lse;
+  st.gt[px] = t_ok ? u.g0 * w : 0.f;
+  st.gm[px] = mi >= 0 ? u.g1 : 0.f;
+  st.ix[px] = (int)((unsigned)(ti & 0xffff) | ((unsigned)mi << 16));
+}
+// LSW: the pixel arrays hold a and b; wsh = the staged class weights
+__device__ __forceinline__ void ce_up_pixel_lsw(const UpP& p, const float* tile, const float* wsh, const Taps& k, bool owned,
+                                                long t, int px, const UpConsts& u, const UpPix& st, UpSums& a) {
+  float m = -INFINITY, s = 0.f, swx = 0.f;
+  for (int c = 0; c < p.N; ++c) {
+    const float x = up_interp(tile + c * CSTR, k);
+    up_online(x, m, s);
+    swx = fmaf(wsh[c], x, swx);
+  }
+  const float lse = m + log2f(s);               // (base 2, like the staged logits and swx)
+  const bool t_ok = t != 255, in = t_ok && t >= 0 && t < p.N;
+  const float wt = in ? wsh[(int)t] : 0.f;      // (a label outside [0, N) reads no logit and no weight)
+  if (t_ok && owned) {
+    const float xt = in ? up_interp(tile + (int)t * CSTR, k) : 0.f;
+    a.n_v += wt;
+    a.s_t += LN2 * (u.om * wt * (lse - xt) + u.en * (u.wsum * lse - swx));
+  }
+  // (selected, not multiplied: with every target 255 the scale g0 is 1 / 0)
+  st.lse[px] = lse;
+  st.gt[px] = t_ok ? u.g0 * (u.om * wt + u.en * u.wsum) : 0.f;
+  st.gm[px] = t_ok ? u.g0 * (u.om * wt) : 0.f;
+  st.ix[px] = (int)((unsigned)((t_ok ? (int)t : -1) & 0xffff) | 0xffff0000u);
+}
+
 template <bool LSW>
 __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>::type p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int ry0[RMAX], ry1[RMAX], cx0[RMAX], cx1[RMAX];
-  __shared__ float rl0[RMAX], rl1[RMAX], cl0[RMAX], cl1[RMAX];
   __shared__ int cr_lo[TC], cr_hi[TC], cc_lo[TC], cc_hi[TC];
   __shared__ float red[NT / 64][4];
   float* wsh = nullptr;                     // LSW: the class weights
@@ -260,29 +307,11 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
   float* st_lse = smem + p.N * CSTR;        // per evaluated pixel: log-sum-exp, g_t, g_m, (target | guidance << 16)
   float* st_gt = st_lse + PS;
   float* st_gm = st_gt + PS;
-  int* st_ix = reinterpret_cast<int*>(st_gm + PS);
+  const UpPix st = {st_lse, st_gt, st_gm, reinterpret_cast<int*>(st_gm + PS)};
   float* dbuf = st_gm + 2 * PS;             // [CG][PS]: d(loss)/d(resized logit) of one class round
 
   const int tid = threadIdx.x;
-  const int per = p.ncy * p.ncx;
-  const int b = blockIdx.x / per, rem = blockIdx.x - b * per;
-  const int ty = rem / p.ncx, tx = rem - ty * p.ncx;
-  const float sh = up_scale(p.h, p.H, p.align), sw = up_scale(p.w, p.W, p.align);
-  int c0y, c1y, s0y, nsy, r0y, nry, c0x, c1x, s0x, nsx, r0x, nrx;
-  up_axis<true>(ty, p.h, p.H, sh, p.align, c0y, c1y, s0y, nsy, r0y, nry);
-  up_axis<true>(tx, p.w, p.W, sw, p.align, c0x, c1x, s0x, nsx, r0x, nrx);
-  if (tid < nry) up_src(r0y + tid, sh, p.h, p.align, ry0[tid], ry1[tid], rl0[tid], rl1[tid]);
-  else if (tid >= 64 && tid < 64 + nrx) up_src(r0x + tid - 64, sw, p.w, p.align, cx0[tid - 64], cx1[tid - 64], cl0[tid - 64], cl1[tid - 64]);
-  {
-    const int cell = tid & 127, cl = tid >> 7;
-    if (cell < (nsy + 1) * (nsx + 1)) {
-      const int cr = cell / (nsx + 1), cc = cell - cr * (nsx + 1);
-      const float* g = p.logits + (long)b * p.N * p.h * p.w + (long)imin_(s0y + cr, p.h - 1) * p.w + imin_(s0x + cc, p.w - 1);
-      float* d = tile + cr * LR + cc;
-      const long hw = (long)p.h * p.w;
-      for (int c = cl; c < p.N; c += NT / 128) d[c * CSTR] = g[c * hw] * LOG2E;
-    }
-  }
+  const UpBlock g = up_prologue<true, NT, true>(p, tile);
   if constexpr (LSW) {
     if (tid < p.N) wsh[tid] = p.cw ? p.cw[tid] : 1.f;     // (N <= UP_MAX_N < NT)
   }
@@ -291,11 +320,11 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
   if (tid < 2 * TC) {
     const bool rows = tid < TC;
     const int i = rows ? tid : tid - TC;
-    const int cell = (rows ? c0y : c0x) + i, n = rows ? nry : nrx;
-    const int* a0 = rows ? ry0 : cx0;
-    const int* a1 = rows ? ry1 : cx1;
+    const int cell = (rows ? g.c0y : g.c0x) + i, n = rows ? g.nry : g.nrx;
+    const int* a0 = rows ? g.ry0 : g.cx0;
+    const int* a1 = rows ? g.ry1 : g.cx1;
     int lo = 0, hi = -1;
-    if (cell < (rows ? c1y : c1x)) {
+    if (cell < (rows ? g.c1y : g.c1x)) {
       lo = n;
       for (int r = 0; r < n; ++r)
         if (a0[r] == cell || a1[r] == cell) {
@@ -308,88 +337,31 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
   }
 
   // ---- phase A: per evaluated pixel log-sum-exp, loss terms (owned pixels), gradient coefficients ----------------
-  const int npx = nry * nrx;
-  const float g0 = p.dlogits ? p.gscale[0] : 0.f, g1 = p.dlogits ? p.gscale[1] : 0.f;
-  const float iw = p.img_weight ? p.img_weight[b] : 1.f;
-  float s_t = 0.f, s_m = 0.f, s_c = 0.f, n_v = 0.f;
-  float om = 1.f, en = 0.f, wsum = 0.f;             // LSW: 1 - eps, eps / N, W (class order: the same in every thread)
+  const int npx = g.nry * g.nrx, nrx = g.nrx;
+  UpConsts u = {p.dlogits ? p.gscale[0] : 0.f, p.dlogits ? p.gscale[1] : 0.f, p.img_weight ? p.img_weight[g.b] : 1.f,
+                1.f, 0.f, 0.f};
   if constexpr (LSW) {
-    om = 1.f - p.eps;
-    en = p.eps / (float)p.N;
-    for (int c = 0; c < p.N; ++c) wsum += wsh[c];
+    u.om = 1.f - p.eps;
+    u.en = p.eps / (float)p.N;
+    for (int c = 0; c < p.N; ++c) u.wsum += wsh[c];   // (class order: the same in every thread)
   }
+  UpSums a;
   for (int px = tid; px < npx; px += NT) {
     const int r = px / nrx, q = px - r * nrx;
-    const int y0 = ry0[r], x0 = cx0[q];
-    Taps k;
-    k.o00 = (y0 - s0y) * LR + (x0 - s0x);
-    k.o10 = (ry1[r] - s0y) * LR + (x0 - s0x);
-    k.ly0 = rl0[r]; k.ly1 = rl1[r]; k.lx0 = cl0[q]; k.lx1 = cl1[q];
-    const long o = (long)b * p.H * p.W + (long)(r0y + r) * p.W + (r0x + q);
+    const Taps k = up_taps(g, r, q);
+    const bool owned = g.owns(g.ry0[r], g.cx0[q]);
+    const long o = g.pixel(p, r, q);
     const long t = p.target[o];
     long ig = 0, mm = 255;
     float cf = 0.f;
     if (p.conf) { ig = p.ign[o]; cf = p.conf[o]; }
     if (p.mc) mm = p.mc[o];
-    if constexpr (LSW) {
-      float m = -INFINITY, s = 0.f, swx = 0.f;
-      for (int c = 0; c < p.N; ++c) {
-        const float x = up_interp(tile + c * CSTR, k);
-        up_online(x, m, s);
-        swx = fmaf(wsh[c], x, swx);
-      }
-      const float lse = m + log2f(s);               // (base 2, like the staged logits and swx)
-      const bool t_ok = t != 255, in = t_ok && t >= 0 && t < p.N;
-      const float wt = in ? wsh[(int)t] : 0.f;      // (a label outside [0, N) reads no logit and no weight)
-      if (t_ok && y0 >= c0y && y0 < c1y && x0 >= c0x && x0 < c1x) {      // owned
-        const float xt = in ? up_interp(tile + (int)t * CSTR, k) : 0.f;
-        n_v += wt;
-        s_t += LN2 * (om * wt * (lse - xt) + en * (wsum * lse - swx));
-      }
-      // (selected, not multiplied: with every target 255 the scale g0 is 1 / 0)
-      st_lse[px] = lse;
-      st_gt[px] = t_ok ? g0 * (om * wt + en * wsum) : 0.f;
-      st_gm[px] = t_ok ? g0 * (om * wt) : 0.f;
-      st_ix[px] = (int)((unsigned)((t_ok ? (int)t : -1) & 0xffff) | 0xffff0000u);
-      continue;                                     // (the plain kernel's pixel body follows)
-    }
-    float m = -INFINITY, s = 0.f;
-    for (int c = 0; c < p.N; ++c) {
-      up_online(up_interp(tile + c * CSTR, k), m, s);
-    }
-    const float lse = m + log2f(s);                 // (base 2, like the staged logits)
-    const bool t_ok = !(p.use_ignore_t && t == 255);
-    const int ti = t_ok ? (int)t : -1;
-    const int mi = (p.mc && mm != 255) ? (int)mm : -1;
-    float w = 1.f;
-    bool valid = t_ok;
-    float sc = 0.f;
-    if (p.conf) {
-      const bool v = ig != 255;
-      w = p.all_pixels ? 1.f : ((cf >= p.conf_thresh && v) ? 1.f : 0.f);
-      w *= iw;
-      valid = v;
-      sc = v ? cf : 0.f;
-    }
-    const bool owned = y0 >= c0y && y0 < c1y && x0 >= c0x && x0 < c1x;
-    if (owned) {
-      const float xt = (ti >= 0 && ti < p.N) ? up_interp(tile + ti * CSTR, k) : 0.f;
-      const float xm = (mi >= 0 && mi < p.N) ? up_interp(tile + mi * CSTR, k) : 0.f;
-      n_v += valid ? 1.f : 0.f;
-      s_t += t_ok ? w * (LN2 * (lse - xt)) : 0.f;
-      s_m += mi >= 0 ? LN2 * (lse - xm) : 0.f;
-      s_c += sc;
-    }
-    const float gt = t_ok ? g0 * w : 0.f;
-    const float gm = mi >= 0 ? g1 : 0.f;
-    st_lse[px] = lse;
-    st_gt[px] = gt;
-    st_gm[px] = gm;
-    st_ix[px] = (int)((unsigned)(ti & 0xffff) | ((unsigned)mi << 16));
+    if constexpr (LSW) ce_up_pixel_lsw(p, tile, wsh, k, owned, t, px, u, st, a);
+    else ce_up_pixel(p, tile, k, owned, t, ig, cf, mm, px, u, st, a);
   }
   // block partial sums: fixed shuffle tree per wave, waves in order
   {
-    float a0 = s_t, a1 = s_m, a2 = s_c, a3 = n_v;
+    float a0 = a.s_t, a1 = a.s_m, a2 = a.s_c, a3 = a.n_v;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       a0 += __shfl_xor(a0, off, 64);
@@ -413,8 +385,8 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
   // ---- phase B: rounds of CG classes -- B1: d(loss)/d(resized logit) of every evaluated pixel into LDS; B2: thread
   //      (class of the round, owned cell) gathers its footprint with the resize's own weights --------------------------
   const int bj = tid >> 6, bcell = tid & 63, cyi = bcell >> 3, cxi = bcell & 7;
-  const int yl = c0y + cyi, xl = c0x + cxi;
-  const bool cell_ok = yl < c1y && xl < c1x;
+  const int yl = g.c0y + cyi, xl = g.c0x + cxi;
+  const bool cell_ok = yl < g.c1y && xl < g.c1x;
   const int rlo = cr_lo[cyi], rhi = cr_hi[cyi], clo = cc_lo[cxi];
   float wx[MAXF];
   {
@@ -422,21 +394,17 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
 #pragma unroll
     for (int f = 0; f < MAXF; ++f) {
       const int cc = min(clo + f, nrx - 1);
-      wx[f] = (cell_ok && clo + f <= chi) ? ((cx0[cc] == xl ? cl0[cc] : 0.f) + (cx1[cc] == xl ? cl1[cc] : 0.f)) : 0.f;
+      wx[f] = (cell_ok && clo + f <= chi) ? ((g.cx0[cc] == xl ? g.cl0[cc] : 0.f) + (g.cx1[cc] == xl ? g.cl1[cc] : 0.f)) : 0.f;
     }
   }
-  const float ge = en > 0.f ? g0 * en : 0.f;        // LSW: e = g eps / N (0 in the plain kernel)
-  float* dl = p.dlogits + (long)b * p.N * p.h * p.w + (long)yl * p.w + xl;
+  const float ge = u.en > 0.f ? u.g0 * u.en : 0.f;  // LSW: e = g eps / N (0 in the plain kernel)
+  float* dl = p.dlogits + (long)g.b * p.N * p.h * p.w + (long)yl * p.w + xl;
   for (int cg0 = 0; cg0 < p.N; cg0 += CG) {
     for (int px = tid; px < npx; px += NT) {
       const int r = px / nrx, q = px - r * nrx;
-      const int y0 = ry0[r], x0 = cx0[q];
-      Taps k;
-      k.o00 = (y0 - s0y) * LR + (x0 - s0x);
-      k.o10 = (ry1[r] - s0y) * LR + (x0 - s0x);
-      k.ly0 = rl0[r]; k.ly1 = rl1[r]; k.lx0 = cl0[q]; k.lx1 = cl1[q];
-      const float lse = st_lse[px], gt = st_gt[px], gm = st_gm[px], gs = gt + gm;
-      const int ix = st_ix[px];
+      const Taps k = up_taps(g, r, q);
+      const float lse = st.lse[px], gt = st.gt[px], gm = st.gm[px], gs = gt + gm;
+      const int ix = st.ix[px];
       const int ti = (int)(short)(ix & 0xffff), mi = ix >> 16;
 #pragma unroll
       for (int j = 0; j < CG; ++j) {
@@ -460,7 +428,7 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
       const float* dj = dbuf + bj * PS;
       float acc = 0.f;
       for (int r = rlo; r <= rhi; ++r) {
-        const float wy = (ry0[r] == yl ? rl0[r] : 0.f) + (ry1[r] == yl ? rl1[r] : 0.f);
+        const float wy = (g.ry0[r] == yl ? g.rl0[r] : 0.f) + (g.ry1[r] == yl ? g.rl1[r] : 0.f);
         const float* row = dj + r * nrx;
         float ra = 0.f;
 #pragma unroll
@@ -475,7 +443,7 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
 
 inline bool up_axis_ok(int in, int out, bool align, int* max_region = nullptr) {
   if (in < 2 || out < in) return false;
-  const float sc = up_scale(in, out, align);
+  const float sc = area_scale(in, out, align);
   if (!(sc >= MIN_SCALE)) return false;
   int mx = 0;
   for (int t = 0; t * TC < in; ++t) {
@@ -494,16 +462,22 @@ inline bool up_ok(int N, int h, int w, int H, int W, int align) {
 }
 inline size_t ce_up_lds(int N, int pstr) { return ((size_t)N * CSTR + (size_t)(4 + CG) * pstr) * sizeof(float); }
 
-// hipFuncSetAttribute is per device: one bit per device ordinal, set only AFTER the call succeeded (a failed or still
-// running first call must not let later launches skip the attribute; two threads racing here both set it: idempotent)
-template <typename K>
-int lds_attr_once(std::atomic<uint64_t>& mask, K kernel, int bytes) {
+// "Allow this kernel `max_lds` bytes of dynamic LDS, once; then launch it": one block per (image, tile) of p's geometry.
+// hipFuncSetAttribute is per device: one bit per device ordinal (the mask is the kernel's own), set only AFTER the call
+// succeeded (a failed or still running first call must not let later launches skip the attribute; two threads racing here
+// both set it: idempotent)
+template <auto KERNEL, typename... Args>
+int up_launch(const char* fn, int max_lds, const UpP& p, int threads, size_t lds, svl_stream_t stream, const Args&... args) {
+  static std::atomic<uint64_t> mask{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   const uint64_t bit = 1ull << (dev & 63);
-  if (mask.load(std::memory_order_acquire) & bit) return SVL_OK;
-  SVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  mask.fetch_or(bit, std::memory_order_acq_rel);
+  if (!(mask.load(std::memory_order_acquire) & bit)) {
+    SVL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    mask.fetch_or(bit, std::memory_order_acq_rel);
+  }
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)((long)p.B * p.ncy * p.ncx)), dim3(threads), lds, (hipStream_t)stream, args...);
+  SVL_LAUNCH_CHECK(fn);
   return SVL_OK;
 }
 // LDS a workgroup may allocate on the current device (gfx950: 160 KB); without a device (host-only geometry queries in the
@@ -528,124 +502,97 @@ inline bool up_fits(int N, int h, int w, int H, int W, int align, size_t fixed =
 constexpr size_t UP_LSW_FIXED = 3 * 1024;
 static_assert(1536 + UP_MAX_N * sizeof(float) <= UP_LSW_FIXED, "static LDS of ce_up_kernel<true>");
 
+
+int64_t up_num_blocks(int B, int N, int h, int w, int H, int W, int align, size_t fixed) {
+  if (B <= 0 || !up_ok(N, h, w, H, W, align) || !up_fits(N, h, w, H, W, align, fixed)) return -1;
+  return (int64_t)B * ((h + TC - 1) / TC) * ((w + TC - 1) / TC);
+}
+// kernel parameters of a launch on logits [B, N, h, w] -> [H, W]: everything else zero
+UpP up_geom(const float* logits, int B, int N, int h, int w, int H, int W, int align) {
+  UpP p = {};
+  p.logits = logits; p.B = B; p.N = N; p.h = h; p.w = w; p.H = H; p.W = W; p.align = align != 0;
+  p.ncy = (h + TC - 1) / TC; p.ncx = (w + TC - 1) / TC;
+  return p;
+}
+// descriptor -> kernel parameters, with the stride of the pixel arrays (geometry checked before: up_ok)
+void up_fill(UpP& p, const svl_ce_up_desc* d) {
+  p = up_geom(d->logits, d->B, d->N, d->h, d->w, d->H, d->W, d->align_corners);
+  p.target = d->target; p.use_ignore_t = d->use_ignore_t;
+  p.conf = d->conf; p.ign = d->ign; p.conf_thresh = d->conf_thresh; p.all_pixels = d->all_pixels;
+  p.mc = d->mc_target; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
+  p.img_weight = d->img_weight;
+  int my = 0, mx = 0;
+  (void)up_axis_ok(d->h, d->H, p.align != 0, &my);
+  (void)up_axis_ok(d->w, d->W, p.align != 0, &mx);
+  p.pstr = ((my * mx + 31) / 32) * 32;
+}
+// `query`: the function whose negative result announces the refusal
+int up_geom_check(const char* fn, bool ok, const char* query, int N, int h, int w, int H, int W) {
+  SVL_CHECK_ARG(ok, "%s: unsupported geometry N=%d %dx%d -> %dx%d (%s < 0)", fn, N, h, w, H, W, query);
+  return SVL_OK;
+}
+// The argument checks of svl_ce_up_fused_f32 and, with `eps` (its label_smoothing), of svl_ce_up_fused_lsw_f32, in one order
+// and under the entry point's name.
+int up_check(const char* fn, const svl_ce_up_desc* d, const float* eps) {
+  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "%s: null args", fn);
+  if (eps) {
+    const int rc = svl_ce_lsw_check(fn, d, *eps);
+    if (rc) return rc;
+  }
+  const bool ok = d->B > 0 && up_ok(d->N, d->h, d->w, d->H, d->W, d->align_corners) &&
+                  (!eps || up_fits(d->N, d->h, d->w, d->H, d->W, d->align_corners, UP_LSW_FIXED));
+  const int rc = up_geom_check(fn, ok, eps ? "svl_ce_up_lsw_num_blocks" : "svl_ce_up_num_blocks", d->N, d->h, d->w, d->H, d->W);
+  if (rc) return rc;
+  if (!eps) SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "%s: conf and ign go together", fn);
+  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "%s: gscale required with dlogits", fn);
+  return SVL_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t svl_ce_up_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners) {
-  if (B <= 0 || !up_ok(N, h, w, H, W, align_corners) || !up_fits(N, h, w, H, W, align_corners)) return -1;
-  return (int64_t)B * ((h + TC - 1) / TC) * ((w + TC - 1) / TC);
+  return up_num_blocks(B, N, h, w, H, W, align_corners, 1024);
 }
 
 extern "C" int svl_softmax_max_up_f32(const float* logits, int B, int N, int h, int w, int H, int W, int align_corners,
                                       float* conf, int64_t* label, svl_stream_t stream) {
   SVL_CHECK_ARG(logits && conf && label && B > 0, "svl_softmax_max_up_f32: bad args");
-  SVL_CHECK_ARG(up_ok(N, h, w, H, W, align_corners),
-                "svl_softmax_max_up_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_num_blocks < 0)", N, h, w, H, W);
-  UpP p = {};
-  p.logits = logits; p.B = B; p.N = N; p.h = h; p.w = w; p.H = H; p.W = W; p.align = align_corners != 0;
+  const int rc = up_geom_check("svl_softmax_max_up_f32", up_ok(N, h, w, H, W, align_corners), "svl_ce_up_num_blocks", N, h, w, H, W);
+  if (rc) return rc;
+  UpP p = up_geom(logits, B, N, h, w, H, W, align_corners);
   p.conf_out = conf; p.label_out = label;
-  p.ncy = (h + TC - 1) / TC; p.ncx = (w + TC - 1) / TC;
-  const size_t lds = (size_t)N * CSTR * sizeof(float);
-  static std::atomic<uint64_t> mask{0};
-  {
-    const int rc = lds_attr_once(mask, softmax_max_up_kernel, 96 * 1024);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(softmax_max_up_kernel, dim3((unsigned)((long)B * p.ncy * p.ncx)), dim3(256), lds, (hipStream_t)stream, p);
-  SVL_LAUNCH_CHECK("svl_softmax_max_up_f32");
-  return SVL_OK;
+  return up_launch<softmax_max_up_kernel>("svl_softmax_max_up_f32", 96 * 1024, p, 256, (size_t)N * CSTR * sizeof(float), stream, p);
 }
 
 extern "C" int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t stream) {
-  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_up_fused_f32: null args");
-  SVL_CHECK_ARG(d->B > 0 && up_ok(d->N, d->h, d->w, d->H, d->W, d->align_corners),
-                "svl_ce_up_fused_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_num_blocks < 0)", d->N, d->h, d->w,
-                d->H, d->W);
-  SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "svl_ce_up_fused_f32: conf and ign go together");
-  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_up_fused_f32: gscale required with dlogits");
-  UpP p = {};
-  p.logits = d->logits; p.B = d->B; p.N = d->N; p.h = d->h; p.w = d->w; p.H = d->H; p.W = d->W;
-  p.align = d->align_corners != 0;
-  p.target = d->target; p.use_ignore_t = d->use_ignore_t;
-  p.conf = d->conf; p.ign = d->ign; p.conf_thresh = d->conf_thresh; p.all_pixels = d->all_pixels;
-  p.mc = d->mc_target; p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
-  p.img_weight = d->img_weight;
-  p.ncy = (d->h + TC - 1) / TC; p.ncx = (d->w + TC - 1) / TC;
-  int my = 0, mx = 0;
-  (void)up_axis_ok(d->h, d->H, p.align != 0, &my);
-  (void)up_axis_ok(d->w, d->W, p.align != 0, &mx);
-  p.pstr = ((my * mx + 31) / 32) * 32;
-  static std::atomic<uint64_t> mask{0};
-  {
-    const int rc = lds_attr_once(mask, ce_up_kernel<false>, 158 * 1024);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(ce_up_kernel<false>, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
-                     (hipStream_t)stream, p);
-  SVL_LAUNCH_CHECK("svl_ce_up_fused_f32");
-  return SVL_OK;
+  const int rc = up_check("svl_ce_up_fused_f32", d, nullptr);
+  if (rc) return rc;
+  UpP p;
+  up_fill(p, d);
+  return up_launch<ce_up_kernel<false>>("svl_ce_up_fused_f32", 158 * 1024, p, NT, ce_up_lds(p.N, p.pstr), stream, p);
 }
 
 extern "C" int64_t svl_ce_up_lsw_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners) {
-  if (B <= 0 || !up_ok(N, h, w, H, W, align_corners) || !up_fits(N, h, w, H, W, align_corners, UP_LSW_FIXED)) return -1;
-  return (int64_t)B * ((h + TC - 1) / TC) * ((w + TC - 1) / TC);
+  return up_num_blocks(B, N, h, w, H, W, align_corners, UP_LSW_FIXED);
 }
 
 extern "C" int svl_ce_up_fused_lsw_f32(const svl_ce_up_desc* d, float label_smoothing, const float* class_weight,
                                        svl_stream_t stream) {
-  SVL_CHECK_ARG(d && d->logits && d->target && d->partials, "svl_ce_up_fused_lsw_f32: null args");
-  SVL_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "svl_ce_up_fused_lsw_f32: label_smoothing=%g outside [0, 1]",
-                (double)label_smoothing);
-  // labelled branch only
-  SVL_CHECK_ARG(d->conf == nullptr, "svl_ce_up_fused_lsw_f32: conf must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->ign == nullptr, "svl_ce_up_fused_lsw_f32: ign must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->mc_target == nullptr, "svl_ce_up_fused_lsw_f32: mc_target must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->img_weight == nullptr, "svl_ce_up_fused_lsw_f32: img_weight must be NULL (labelled branch only)");
-  SVL_CHECK_ARG(d->all_pixels == 0, "svl_ce_up_fused_lsw_f32: all_pixels must be 0 (labelled branch only)");
-  SVL_CHECK_ARG(d->use_ignore_t != 0, "svl_ce_up_fused_lsw_f32: use_ignore_t must be 1 (labelled branch only)");
-  SVL_CHECK_ARG(d->B > 0 && up_ok(d->N, d->h, d->w, d->H, d->W, d->align_corners) &&
-                    up_fits(d->N, d->h, d->w, d->H, d->W, d->align_corners, UP_LSW_FIXED),
-                "svl_ce_up_fused_lsw_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_lsw_num_blocks < 0)", d->N, d->h,
-                d->w, d->H, d->W);
-  SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "svl_ce_up_fused_lsw_f32: gscale required with dlogits");
-  UpLswP p = {};
-  p.logits = d->logits; p.B = d->B; p.N = d->N; p.h = d->h; p.w = d->w; p.H = d->H; p.W = d->W;
-  p.align = d->align_corners != 0;
-  p.target = d->target; p.use_ignore_t = 1;
-  p.partials = d->partials; p.dlogits = d->dlogits; p.gscale = d->gscale;
-  p.ncy = (d->h + TC - 1) / TC; p.ncx = (d->w + TC - 1) / TC;
+  const int rc = up_check("svl_ce_up_fused_lsw_f32", d, &label_smoothing);
+  if (rc) return rc;
+  UpLswP p;
+  up_fill(p, d);
   p.eps = label_smoothing; p.cw = class_weight;
-  int my = 0, mx = 0;
-  (void)up_axis_ok(d->h, d->H, p.align != 0, &my);
-  (void)up_axis_ok(d->w, d->W, p.align != 0, &mx);
-  p.pstr = ((my * mx + 31) / 32) * 32;
-  static std::atomic<uint64_t> mask{0};
-  {
-    const int rc = lds_attr_once(mask, ce_up_kernel<true>, 157 * 1024);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(ce_up_kernel<true>, dim3((unsigned)((long)d->B * p.ncy * p.ncx)), dim3(NT), ce_up_lds(d->N, p.pstr),
-                     (hipStream_t)stream, p);
-  SVL_LAUNCH_CHECK("svl_ce_up_fused_lsw_f32");
-  return SVL_OK;
+  return up_launch<ce_up_kernel<true>>("svl_ce_up_fused_lsw_f32", 157 * 1024, p, NT, ce_up_lds(p.N, p.pstr), stream, p);
 }
 
 extern "C" int svl_target_prob_up_f32(const float* logits, int B, int N, int h, int w, int H, int W, int align_corners,
                                       const int64_t* target, float* prob, svl_stream_t stream) {
   SVL_CHECK_ARG(logits && target && prob && B > 0, "svl_target_prob_up_f32: bad args");
-  SVL_CHECK_ARG(up_ok(N, h, w, H, W, align_corners),
-                "svl_target_prob_up_f32: unsupported geometry N=%d %dx%d -> %dx%d (svl_ce_up_num_blocks < 0)", N, h, w, H, W);
-  UpP p = {};
-  p.logits = logits; p.B = B; p.N = N; p.h = h; p.w = w; p.H = H; p.W = W; p.align = align_corners != 0;
+  const int rc = up_geom_check("svl_target_prob_up_f32", up_ok(N, h, w, H, W, align_corners), "svl_ce_up_num_blocks", N, h, w, H, W);
+  if (rc) return rc;
+  UpP p = up_geom(logits, B, N, h, w, H, W, align_corners);
   p.target = target;
-  p.ncy = (h + TC - 1) / TC; p.ncx = (w + TC - 1) / TC;
-  const size_t lds = (size_t)N * CSTR * sizeof(float);
-  static std::atomic<uint64_t> mask{0};
-  {
-    const int rc = lds_attr_once(mask, target_prob_up_kernel, 96 * 1024);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(target_prob_up_kernel, dim3((unsigned)((long)B * p.ncy * p.ncx)), dim3(256), lds, (hipStream_t)stream,
-                     p, prob);
-  SVL_LAUNCH_CHECK("svl_target_prob_up_f32");
-  return SVL_OK;
+  return up_launch<target_prob_up_kernel>("svl_target_prob_up_f32", 96 * 1024, p, 256, (size_t)N * CSTR * sizeof(float), stream, p,
+                                          prob);
 }

@@ -1,8 +1,8 @@
 // Resampling kernels: bilinear resize (both corner conventions) on channels-last class-images and on NCHW logit
-// planes, AvgPool + text concat for the SemanticTransformer.  Index math follows ATen's upsample_bilinear2d
-// (area_pixel_compute_source_index + guard_index_and_lambda), which is what F.interpolate / mmseg.ops.resize call
-// in the reference (vlg_head.py:61,81,132,247; builder.py:93-97; vlm.py:103).
+// planes, AvgPool + text concat for the SemanticTransformer.  Index math: bilinear_index.h, for the resizes of
+// vlg_head.py:61,81,132,247; builder.py:93-97; vlm.py:103.
 #include "svl_common.h"
+#include "bilinear_index.h"
 
 namespace {
 
@@ -13,19 +13,6 @@ inline int grid_for(long n) {
   return (int)g;
 }
 
-__device__ __forceinline__ float area_scale(int in, int out, bool align) {
-  if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  return (float)in / (float)out;
-}
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, bool align, int& i0, int& i1, float& l0,
-                                          float& l1) {
-  float s = align ? scale * dst : scale * (dst + 0.5f) - 0.5f;
-  if (!align && s < 0.f) s = 0.f;
-  i0 = min((int)s, in_size - 1);
-  i1 = min(i0 + 1, in_size - 1);
-  l1 = fminf(fmaxf(s - i0, 0.f), 1.f);
-  l0 = 1.f - l1;
-}
 // Conservative range of destination indices whose taps can touch source index `i`.
 __device__ __forceinline__ void dst_range(int i, float scale, int out_size, bool align, int& lo, int& hi) {
   if (scale <= 0.f) {

@@ -40,6 +40,22 @@ void svl_set_error(const char* fmt, ...);
     }                                                                 \
   } while (0)
 
+// The label-smoothing / class-weight cross entropies (svl_ce_fused_lsw_f32, svl_ce_up_fused_lsw_f32) are the labelled
+// criterion only: label_smoothing in [0, 1] and a descriptor (svl_ce_desc / svl_ce_up_desc) none of whose unlabelled-branch
+// fields is set, each refused under the entry point's name `fn`.
+template <typename Desc>
+static int svl_ce_lsw_check(const char* fn, const Desc* d, float label_smoothing) {
+  SVL_CHECK_ARG(label_smoothing >= 0.f && label_smoothing <= 1.f, "%s: label_smoothing=%g outside [0, 1]", fn,
+                (double)label_smoothing);
+  SVL_CHECK_ARG(d->conf == nullptr, "%s: conf must be NULL (labelled branch only)", fn);
+  SVL_CHECK_ARG(d->ign == nullptr, "%s: ign must be NULL (labelled branch only)", fn);
+  SVL_CHECK_ARG(d->mc_target == nullptr, "%s: mc_target must be NULL (labelled branch only)", fn);
+  SVL_CHECK_ARG(d->img_weight == nullptr, "%s: img_weight must be NULL (labelled branch only)", fn);
+  SVL_CHECK_ARG(d->all_pixels == 0, "%s: all_pixels must be 0 (labelled branch only)", fn);
+  SVL_CHECK_ARG(d->use_ignore_t != 0, "%s: use_ignore_t must be 1 (labelled branch only)", fn);
+  return SVL_OK;
+}
+
 // Fork/join onto the library's helper stream (api.hip): independent, disjoint-output launches of one entry point run
 // concurrently with the caller's stream.  svl_fork orders the helper stream after everything queued on `st`; svl_join
 // makes `st` wait for everything queued on the helper stream.  Capture-legal (events only).
@@ -79,6 +95,18 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// One class of the online softmax-max (m = -inf, s = 0, idx = 0 at the start): a new maximum rescales the running sum, the
+// FIRST maximum wins like torch.max; conf = 1 / s afterwards.
+__device__ __forceinline__ void softmax_max_step(float x, int c, float& m, float& s, int& idx) {
+  if (x > m) {
+    s = s * expf(m - x) + 1.f;
+    m = x;
+    idx = c;
+  } else {
+    s += expf(x - m);
+  }
 }
 
 __device__ __forceinline__ float gelu_erf(float x) {

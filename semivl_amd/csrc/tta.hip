@@ -1,9 +1,9 @@
 // Test-time augmentation of the evaluator (mmseg 0.x MultiScaleFlipAug + EncoderDecoder.aug_test): svl_tta_view_f32 builds a
 // resized / mirrored view of the image planes, svl_tta_accum_f32 forms the class scores of one view at the target
 // resolution (bilinear resize, softmax or normalised probability sums, horizontal un-flip) and adds them, scaled, to the
-// running mean in ONE pass over the [B, N, H, W] destination.  Index math is ATen's upsample_bilinear2d
-// (area_pixel_compute_source_index + guard_index_and_lambda), the same arithmetic as csrc/resample.hip.
+// running mean in ONE pass over the [B, N, H, W] destination.  Index math: bilinear_index.h.
 #include "svl_common.h"
+#include "bilinear_index.h"
 
 namespace {
 
@@ -15,20 +15,6 @@ inline int grid_for(long n, int threads = 256) {
   if (g < 1) g = 1;
   if (g > TTA_GRID_THREADS / threads) g = TTA_GRID_THREADS / threads;
   return (int)g;
-}
-
-__device__ __forceinline__ float area_scale(int in, int out, bool align) {
-  if (align) return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  return (float)in / (float)out;
-}
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, bool align, int& i0, int& i1, float& l0,
-                                          float& l1) {
-  float s = align ? scale * dst : scale * (dst + 0.5f) - 0.5f;
-  if (!align && s < 0.f) s = 0.f;
-  i0 = min((int)s, in_size - 1);
-  i1 = min(i0 + 1, in_size - 1);
-  l1 = fminf(fmaxf(s - i0, 0.f), 1.f);
-  l0 = 1.f - l1;
 }
 
 // V = 4: four consecutive output columns per thread, one 16 B store.  `same` (h == H && w == W, wave-uniform): the resize
