@@ -343,6 +343,11 @@ int svl_cutmix_i64(int64_t* out, const int64_t* a, const int64_t* b, const float
  * svl_ce_finalize() reduces the partials in double, in a fixed order, to sums[4].
  * If dlogits != NULL: dlogits = gscale_t * w_t * (softmax - onehot(target)) + gscale_m * [mc valid] * (softmax - onehot(mc))
  * where gscale_* are read from DEVICE memory (gscale[0], gscale[1]) so no host sync is needed.
+ * A label (target or mc_target) that is not ignored and lies outside [0, N) -- 254, or 255 with use_ignore_t == 0 -- reads
+ * no logit: the pixel's term is log-sum-exp - 0 and its gradient is the scale times softmax, without a one-hot term.
+ * svl_ce_fused_f32 and svl_ce_up_fused_f32 agree on this, like their label-smoothing variants.
+ * img_weight multiplies w_t of the confidence-weighted forms only: a descriptor with img_weight but without conf is
+ * refused (status -1, the message names the field) by both entry points.
  *
  * svl_ce_fused_lsw_f32 / svl_ce_up_fused_lsw_f32 (the labelled criterion with label_smoothing eps and class weights w,
  * below) fill the same four slots with another meaning: partials[blk] = {
@@ -366,7 +371,8 @@ typedef struct svl_ce_desc {
   float* dlogits;        /* [B, N, HW] or NULL */
   const float* gscale;   /* [2] device scalars, required when dlogits != NULL */
   const float* img_weight; /* [B] device or NULL: per-image factor on w_t -- conf_mode 'pixelratio' (train_utils.py:39-42:
-                              the whole CE map of image b times its share of confident valid pixels; with all_pixels = 1) */
+                              the whole CE map of image b times its share of confident valid pixels; with all_pixels = 1).
+                              Needs conf: refused without it */
 } svl_ce_desc;
 int64_t svl_ce_num_blocks(int B, int N, int64_t HW); /* -1 if N is unsupported (N > 256) */
 int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t stream);
@@ -405,7 +411,7 @@ typedef struct svl_ce_up_desc {
   float* partials;
   float* dlogits;        /* [B, N, h, w] or NULL: d(loss)/d(logits) at the head's resolution */
   const float* gscale;   /* [2] device scalars, required when dlogits != NULL */
-  const float* img_weight; /* [B] device or NULL */
+  const float* img_weight; /* [B] device or NULL; refused without conf, as in svl_ce_desc */
 } svl_ce_up_desc;
 int64_t svl_ce_up_num_blocks(int B, int N, int h, int w, int H, int W, int align_corners);
 int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t stream);

@@ -107,6 +107,7 @@ int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t s) {
   CHECK(d && d->logits && d->target && d->partials, "svl_ce_fused_f32: null args");
   CHECK(d->B > 0 && d->N > 0 && d->HW > 0, "svl_ce_fused_f32: bad sizes");
   CHECK((d->conf == NULL) == (d->ign == NULL), "svl_ce_fused_f32: conf and ign go together");
+  CHECK(d->img_weight == NULL || d->conf != NULL, "svl_ce_fused_f32: img_weight must be NULL without conf");
   CHECK(d->dlogits == NULL || d->gscale != NULL, "svl_ce_fused_f32: gscale required with dlogits");
   const int N = d->N;
   const int64_t HW = d->HW;
@@ -134,8 +135,12 @@ int svl_ce_fused_f32(const svl_ce_desc* d, svl_stream_t s) {
       }
       nv += valid;
       int ti = -1, mi = -1;
-      if (t_ok) { ti = (int)t; st += w * (lse - x[(int64_t)ti * HW]); }
-      if (d->mc_target && d->mc_target[o] != 255) { mi = (int)d->mc_target[o]; sm += lse - x[(int64_t)mi * HW]; }
+      /* a label outside [0, N) reads no logit (x_t = 0) and has no one-hot term (include/semivl_hip.h) */
+      if (t_ok) { ti = (int)t; st += w * (lse - ((ti >= 0 && ti < N) ? x[(int64_t)ti * HW] : 0.f)); }
+      if (d->mc_target && d->mc_target[o] != 255) {
+        mi = (int)d->mc_target[o];
+        sm += lse - ((mi >= 0 && mi < N) ? x[(int64_t)mi * HW] : 0.f);
+      }
       if (d->dlogits) {
         const float gt = t_ok ? d->gscale[0] * w : 0.f, gm = mi >= 0 ? d->gscale[1] : 0.f;
         float* dl = d->dlogits + (int64_t)b * N * HW + p;
@@ -215,6 +220,7 @@ int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t s) {
   CHECK(d && d->logits && d->target && d->partials, "svl_ce_up_fused_f32: null args");
   CHECK(d->B > 0 && up_ok(d->N, d->h, d->w, d->H, d->W, d->align_corners), "svl_ce_up_fused_f32: unsupported geometry");
   CHECK((d->conf == NULL) == (d->ign == NULL), "svl_ce_up_fused_f32: conf and ign go together");
+  CHECK(d->img_weight == NULL || d->conf != NULL, "svl_ce_up_fused_f32: img_weight must be NULL without conf");
   CHECK(d->dlogits == NULL || d->gscale != NULL, "svl_ce_up_fused_f32: gscale required with dlogits");
   const int N = d->N, h = d->h, w = d->w, H = d->H, W = d->W, al = d->align_corners;
   const float sh = up_scale(h, H, al), sw = up_scale(w, W, al);
@@ -252,8 +258,11 @@ int svl_ce_up_fused_f32(const svl_ce_up_desc* d, svl_stream_t s) {
         }
         nv += valid;
         int ti = -1, mi = -1;
-        if (t_ok) { ti = (int)t; st += wt * (lse - v[ti]); }
-        if (d->mc_target && d->mc_target[o] != 255) { mi = (int)d->mc_target[o]; sm += lse - v[mi]; }
+        if (t_ok) { ti = (int)t; st += wt * (lse - ((ti >= 0 && ti < N) ? v[ti] : 0.f)); }
+        if (d->mc_target && d->mc_target[o] != 255) {
+          mi = (int)d->mc_target[o];
+          sm += lse - ((mi >= 0 && mi < N) ? v[mi] : 0.f);
+        }
         if (acc) {
           const float gt = t_ok ? d->gscale[0] * wt : 0.f, gm = mi >= 0 ? d->gscale[1] : 0.f;
           for (int c = 0; c < N; ++c) {

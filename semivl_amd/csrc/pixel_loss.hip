@@ -207,8 +207,9 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const typename ce_param<L
     }
   } else if (act) {
     for (int c = prt; c < p.N; c += K) m = fmaxf(m, tile[c * P + pix]);
-    xt = ti >= 0 ? tile[ti * P + pix] : 0.f;      // (read before the exp pass overwrites the tile)
-    xm = mi >= 0 ? tile[mi * P + pix] : 0.f;
+    // (read before the exp pass overwrites the tile; a label outside [0, N) reads no logit, as in ce_up_pixel)
+    xt = (ti >= 0 && ti < p.N) ? tile[ti * P + pix] : 0.f;
+    xm = (mi >= 0 && mi < p.N) ? tile[mi * P + pix] : 0.f;
   }
   if (K > 1) {                                    // (block-uniform)
     part[0][tid] = m;
@@ -577,6 +578,7 @@ int ce_check(const char* fn, const svl_ce_desc* d, const float* eps) {
     if (rc) return rc;
   } else {
     SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "%s: conf and ign go together", fn);
+    SVL_CHECK_ARG(d->img_weight == nullptr || d->conf != nullptr, "%s: img_weight must be NULL without conf", fn);
   }
   SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "%s: gscale required with dlogits", fn);
   SVL_CHECK_ARG(ce_tile_pixels(d->N) >= 64, "%s: N=%d too large for the LDS tile", fn, d->N);

@@ -27,7 +27,8 @@ constexpr int RMAX = 40;         // full-resolution rows / columns a block evalu
 constexpr int CG = 8;            // classes per gradient round
 constexpr int NT = 512;          // threads of the cross-entropy kernel (CG x TC x TC)
 constexpr int MAXF = 10;         // full-resolution columns in one cell's footprint
-constexpr float MIN_SCALE = 2.f / (MAXF - 1);   // a cell's footprint (2 / scale + 1 destination columns) fits MAXF
+constexpr float MIN_SCALE = 2.f / (MAXF - 1);   // a cell's footprint (at most 2 / scale + 1 destination columns with a tap of
+                                                // non-zero weight on it) fits MAXF
 
 struct UpP {
   const float* logits;   // [B, N, h, w]
@@ -323,11 +324,15 @@ __global__ __launch_bounds__(NT) void ce_up_kernel(const typename up_param<LSW>:
     const int cell = (rows ? g.c0y : g.c0x) + i, n = rows ? g.nry : g.nrx;
     const int* a0 = rows ? g.ry0 : g.cx0;
     const int* a1 = rows ? g.ry1 : g.cx1;
+    const float* w0 = rows ? g.rl0 : g.cl0;
+    const float* w1 = rows ? g.rl1 : g.cl1;
     int lo = 0, hi = -1;
     if (cell < (rows ? g.c1y : g.c1x)) {
       lo = n;
+      // (taps of weight 0 do not count: the destination indices clamped at the low border all name cell 1 as their second
+      //  tap with weight 0, and at ratios above 4 they stretched cell 1's columns past MAXF -- its last column was dropped)
       for (int r = 0; r < n; ++r)
-        if (a0[r] == cell || a1[r] == cell) {
+        if ((a0[r] == cell && w0[r] != 0.f) || (a1[r] == cell && w1[r] != 0.f)) {
           lo = min(lo, r);
           hi = r;
         }
@@ -543,7 +548,10 @@ int up_check(const char* fn, const svl_ce_up_desc* d, const float* eps) {
                   (!eps || up_fits(d->N, d->h, d->w, d->H, d->W, d->align_corners, UP_LSW_FIXED));
   const int rc = up_geom_check(fn, ok, eps ? "svl_ce_up_lsw_num_blocks" : "svl_ce_up_num_blocks", d->N, d->h, d->w, d->H, d->W);
   if (rc) return rc;
-  if (!eps) SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "%s: conf and ign go together", fn);
+  if (!eps) {
+    SVL_CHECK_ARG((d->conf == nullptr) == (d->ign == nullptr), "%s: conf and ign go together", fn);
+    SVL_CHECK_ARG(d->img_weight == nullptr || d->conf != nullptr, "%s: img_weight must be NULL without conf", fn);
+  }
   SVL_CHECK_ARG(d->dlogits == nullptr || d->gscale != nullptr, "%s: gscale required with dlogits", fn);
   return SVL_OK;
 }

@@ -1,7 +1,8 @@
 """Pixel losses on head-resolution logits (svl_softmax_max_up_f32 / svl_ce_up_fused_f32): the kernels evaluate the
 bilinear resize of vlg_head.py:247 / builder.py:93-97 themselves.  Checked against F.interpolate + the plain PyTorch
 loss of semivl.py:232,252,267-323 (autograd through the resize gives the low-resolution gradient), against the unfused
-kernels of the same library, and at step level against the step that writes the resized tensors."""
+kernels of the same library, and at step level against the step that writes the resized tensors.
+(The float64 comparison under derived limits, on hostile values and at the geometry's edges: tests/test_pixel_loss_kernels_gpu.py.)"""
 import pytest
 import torch
 import torch.nn.functional as F
