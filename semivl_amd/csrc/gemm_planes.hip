@@ -21,27 +21,7 @@ __global__ __launch_bounds__(256) void pack_planes_kernel(const float* __restric
     const long t = i >> 6;
     const long kg = t % nkg, rb = t / nkg;
     const long r = rb * 32 + r31;
-    float v[8];
-    if (r < rows) {
-      const float* src = x + r * ld + (kg * 16 + 4 * h) * ks;
-      if (fast) {
-        const float4 f0 = *reinterpret_cast<const float4*>(src), f1 = *reinterpret_cast<const float4*>(src + 8);
-        v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w; v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[q] = src[q * ks]; v[4 + q] = src[(8 + q) * ks]; }
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = 0.f;
-    }
-    bf16x8 h0, h1, h2;
-    split3x8(v, h0, h1, h2);
-    const long rr = row_off + r;
-    char* q = planes + kg * p_ks + (rr >> 5) * (3 * CH) + (h * 32 + (int)(rr & 31)) * 16;
-    *reinterpret_cast<bf16x8*>(q) = h0;
-    *reinterpret_cast<bf16x8*>(q + CH) = h1;
-    *reinterpret_cast<bf16x8*>(q + 2 * CH) = h2;
+    pack8<3>(x + r * ld + (kg * 16 + 4 * h) * ks, ks, fast, r < rows, 0, plane_chunk<3>(planes, p_ks, kg, row_off + r, h));
   }
 }
 

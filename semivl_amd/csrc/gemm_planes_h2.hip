@@ -42,11 +42,7 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
     if (r < rows) {
       const float* src = x + r * ld;
       if (fast) {
-        for (int k = sub * 4; k < K; k += 32) {
-          const float4 f = *reinterpret_cast<const float4*>(src + k);
-          amax = fmaxf(fmaxf(amax, fabsf(f.x)), fmaxf(fabsf(f.y), fmaxf(fabsf(f.z), fabsf(f.w))));
-          sq += (double)f.x * f.x + (double)f.y * f.y + ((double)f.z * f.z + (double)f.w * f.w);
-        }
+        row_scan16(src, K, sub, amax, sq);
       } else {
         for (int k = sub; k < K; k += 8) {
           const float f = src[k];
@@ -55,11 +51,7 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
         }
       }
     }
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-      amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-      sq += __shfl_xor(sq, o, 64);
-    }
+    row_combine8(amax, sq);
     if (sub == 0) { s_max[0][row] = amax; s_sq[0][row] = sq; }
   } else {              // transposed source (ld == 1 for a row-major matrix read as its transpose): lanes run along the rows
     const int r31 = tid & 31, part = tid >> 5;
@@ -82,11 +74,11 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
     if (!rowmajor)
       for (int q = 1; q < 8; ++q) { amax = fmaxf(amax, s_max[q][tid]); sq += s_sq[q][tid]; }
     const long r = rb * 32 + tid;
-    const int e = r < rows ? scale_exp_of(amax) : 0;
+    const int e = pack_exp(r < rows, amax);
     s_e[tid] = e;
     const long rr = row_off + rb * 32 + tid;
     sexp[rr] = e;
-    if (rnorm) rnorm[rr] = r < rows ? (float)(sqrt(sq) * (1.0 + 1e-6)) : 0.f;     // (rounded up: it is used as a bound)
+    if (rnorm) rnorm[rr] = pack_rnorm(r < rows, sq);
     if (tensor_amax && blockIdx.y == 0) {     // the matrix's largest |x| as a by-product (absmax_kernel's convention, gemm.hip:
       float m = r < rows ? amax : 0.f;         // bit pattern of a non-negative float, NaNs take no part, the word zeroed beforehand)
 #pragma unroll
@@ -100,26 +92,7 @@ __global__ __launch_bounds__(256) void pack_planes_h2_kernel(const float* __rest
   for (int idx = kg_lo * 64 + tid; idx < kg_hi * 64; idx += 256) {
     const int r31 = idx & 31, h = (idx >> 5) & 1, kg = idx >> 6;
     const long r = rb * 32 + r31;
-    float v[8];
-    if (r < rows) {
-      const float* src = x + r * ld + (long)(kg * 16 + 4 * h) * ks;
-      if (fast) {
-        const float4 f0 = *reinterpret_cast<const float4*>(src), f1 = *reinterpret_cast<const float4*>(src + 8);
-        v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w; v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[q] = src[q * ks]; v[4 + q] = src[(8 + q) * ks]; }
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = 0.f;
-    }
-    f16x8 h0, h1;
-    split2x8(v, s_e[r31], h0, h1);
-    const long rr = row_off + r;
-    char* q = planes + (long)kg * p_ks + (rr >> 5) * (2 * CH) + (h * 32 + (int)(rr & 31)) * 16;
-    *reinterpret_cast<f16x8*>(q) = h0;
-    *reinterpret_cast<f16x8*>(q + CH) = h1;
+    pack8<2>(x + r * ld + (long)(kg * 16 + 4 * h) * ks, ks, fast, r < rows, s_e[r31], plane_chunk<2>(planes, p_ks, kg, row_off + r, h));
   }
 }
 

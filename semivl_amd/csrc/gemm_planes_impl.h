@@ -50,7 +50,7 @@
 // for (vmcnt) before B_{2kg-1} / B_{2kg}, i.e. at least one barrier before the first read (RAW safe).
 #pragma once
 #include "svl_common.h"
-#include "planes_split_h2.h"
+#include "planes_split.h"
 #include <atomic>
 #include <type_traits>
 
@@ -101,12 +101,10 @@ struct PlanesP {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 is a class: not promoted to registers)
 
 constexpr int BM = 256;
-constexpr int CH = 1024;        // bytes of one (k-group, row block, plane) chunk
 constexpr int NSTAGE = 3;
 
 template <int I, int N_, typename F>
@@ -156,20 +154,7 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
 }
 
-// x = x0 + x1 + x2: the three bf16 planes of 8 values
-__device__ __forceinline__ void split3x8(const float (&x)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = x[j];
-    h0[j] = (__bf16)v;
-    v -= (float)h0[j];
-    h1[j] = (__bf16)v;
-    v -= (float)h1[j];
-    h2[j] = (__bf16)v;
-  }
-}
-
-// (split2x8, scale_exp_of: planes_split_h2.h)
+// (split3x8, split2x8, scale_exp_of, CH: planes_split.h)
 
 // Block -> tile.  Blocks go to XCD (id % 8) and, inside an XCD, to CUs in id order as CUs free up.  Every XCD first takes
 // its share of the RAGGED row band's tiles (M % 256 rows), then a contiguous chunk of the full tiles in n-fastest order:

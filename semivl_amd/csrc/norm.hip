@@ -3,7 +3,7 @@
 // row softmax (inside nn.MultiheadAttention), L2 normalise (maskclip_vit.py:555, vlg_head.py:215-216),
 // GroupNorm+ReLU (vlg_head.py:74-137), bias-gradient column sums, F.dropout2d channel masks (builder.py:79-85).
 #include "svl_common.h"
-#include "planes_split_h2.h"
+#include "planes_split.h"
 
 namespace {
 
@@ -18,92 +18,63 @@ inline int grid_for(long n, int per_thread = 1) {
 // LayerNorm: one wave per row, 4 rows per block. C % 4 == 0. Two-pass (mean, then centred variance)
 // like ATen's RowwiseMoments result to fp32 rounding.
 // ---------------------------------------------------------------------------------------------
-// Packed-planes output of a 32-row block (the A operand of the following svl_gemm_planes_f32; layout: svl_common.h /
-// gemm_planes.hip).  Thread = (row r31, lane half h) of k-group kg: 2 x 16 B read from `src` rows (just written / just
-// read by this block: L1 / L2 hits), 3 x 16 B written -- the 32 rows of the block give 512 contiguous bytes per (k-group,
-// half, plane), which is what makes this 4x faster than emitting 8-byte pieces from the row-per-wave loops (measured:
-// 1.7 TB/s vs 6.6 TB/s on the plane stores).  src = x, normalised on the fly with the block's row statistics.
-__device__ __forceinline__ void ln_emit_planes(const float* __restrict__ src, long r0, long rows, int C,
-                                               const float* __restrict__ gamma, const float* __restrict__ beta,
-                                               const float* st /* LDS [32][2] */, char* __restrict__ planes, long p_ks) {
-  const int t = threadIdx.x, r31 = t & 31, h = (t >> 5) & 1, kg0 = t >> 6;
-  const long r = r0 + r31;
-  const int nkg = C >> 4;
-  float mean = 0.f, rstd = 0.f;
-  mean = st[2 * r31]; rstd = st[2 * r31 + 1];
-  for (int kg = kg0; kg < nkg; kg += 4) {
-    float v[8];
-    const int k = kg * 16 + 4 * h;
-    if (r < rows) {
-      const float4 f0 = *reinterpret_cast<const float4*>(src + r * C + k), f1 = *reinterpret_cast<const float4*>(src + r * C + k + 8);
-      v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w; v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
-      {
-        const float4 g0 = *reinterpret_cast<const float4*>(gamma + k), g1 = *reinterpret_cast<const float4*>(gamma + k + 8);
-        const float4 b0 = *reinterpret_cast<const float4*>(beta + k), b1 = *reinterpret_cast<const float4*>(beta + k + 8);
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (v[q] - mean) * rstd * gg[q] + bb[q];     // (the row loop's expression, bit for bit)
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = 0.f;
-    }
-    typedef __bf16 bf16x8_ __attribute__((ext_vector_type(8)));
-    bf16x8_ h0, h1, h2;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      float u = v[q];
-      h0[q] = (__bf16)u;
-      u -= (float)h0[q];
-      h1[q] = (__bf16)u;
-      u -= (float)h1[q];
-      h2[q] = (__bf16)u;
-    }
-    char* q_ = planes + (long)kg * p_ks + (r >> 5) * 3072 + (h * 32 + (int)(r & 31)) * 16;
-    *reinterpret_cast<bf16x8_*>(q_) = h0;
-    *reinterpret_cast<bf16x8_*>(q_ + 1024) = h1;
-    *reinterpret_cast<bf16x8_*>(q_ + 2048) = h2;
-  }
+// The quad-level steps of a row, each defined once: every kernel below that normalises a row (from registers, by
+// streaming it, or 8 values at a time for the planes) runs these expressions and no others.  The loops around them stay in
+// the kernels: one row-pass function for layernorm_fwd_kernel and layernorm_fwd_pack_kernel cost both kernels time
+// (profiles/layernorm_refactor.md).
+__device__ __forceinline__ float ln_sum4(const float4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float ln_sqsum4(const float4 v, float mean) {
+  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
+  return (a * a + b * b) + (c * c + d * d);
 }
+__device__ __forceinline__ float4 ln_affine4(const float4 v, float mean, float rstd, const float4 g, const float4 b) {
+  float4 o;
+  o.x = (v.x - mean) * rstd * g.x + b.x;
+  o.y = (v.y - mean) * rstd * g.y + b.y;
+  o.z = (v.z - mean) * rstd * g.z + b.z;
+  o.w = (v.w - mean) * rstd * g.w + b.w;
+  return o;
+}
+__device__ __forceinline__ void ln_bound4(const float4 o, float& amax, float& sq) {
+  amax = fmaxf(fmaxf(amax, fabsf(o.x)), fmaxf(fabsf(o.y), fmaxf(fabsf(o.z), fabsf(o.w))));
+  sq += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
+}
+// The row pass's scale exponent and norm bound of a finished row (fp32; the pack pass's own: pack_exp / pack_rnorm)
+__device__ __forceinline__ int ln_row_exp(float amax) { return amax > 0.f ? scale_exp_of(amax) : -15; }
+__device__ __forceinline__ float ln_row_rnorm(float sq) { return sqrtf(sq) * (1.f + 2e-5f); }  // (an upper bound: fp32 sum of C squares, rounded up)
 
-// The same for the fp16 x 2 operand format (csrc/gemm_planes_impl.h, NP = 2): two planes per chunk, x 2^-e[row] = h0 + h1
-// with the row exponents of the block in LDS (found by the row loop from the row's largest |y|, exactly as the generic pack
-// pass svl_split_planes_f16x2 finds them: the planes are bit-identical to that pass over the fp32 result).
-__device__ __forceinline__ void ln_emit_planes_h2(const float* __restrict__ src, long r0, long rows, int C,
-                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                  const float* st /* LDS [32][2] */, const int* se /* LDS [32] */,
-                                                  char* __restrict__ planes, long p_ks) {
-  typedef _Float16 f16x8_ __attribute__((ext_vector_type(8)));
+// Packed-planes output of a 32-row block (the A operand of the following svl_gemm_planes_f32; layout: planes_split.h).
+// Thread = (row r31, lane half h) of k-group kg: 2 x 16 B read from x rows (just read by this block: L1 / L2 hits), NP x
+// 16 B written -- the 32 rows of the block give 512 contiguous bytes per (k-group, half, plane), which is what makes this
+// 4x faster than emitting 8-byte pieces from the row-per-wave loops (measured: 1.7 TB/s vs 6.6 TB/s on the plane stores).
+// x is normalised on the fly with the block's row statistics.  NP = 2: x 2^-e[row] = h0 + h1 with the row exponents of
+// the block in LDS (found by the row loop from the row's largest |y|, as the generic pack pass svl_split_planes_f16x2
+// finds them: the planes are those of that pass over the fp32 result).
+template <int NP>
+__device__ __forceinline__ void ln_emit_planes(const float* __restrict__ x, long r0, long rows, int C,
+                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                               const float* st /* LDS [32][2] */, const int* se /* LDS [32], NP = 2 */,
+                                               char* __restrict__ planes, long p_ks) {
   const int t = threadIdx.x, r31 = t & 31, h = (t >> 5) & 1, kg0 = t >> 6;
   const long r = r0 + r31;
   const int nkg = C >> 4;
   const float mean = st[2 * r31], rstd = st[2 * r31 + 1];
-  const int e = se[r31];
+  const int e = NP == 2 ? se[r31] : 0;
   for (int kg = kg0; kg < nkg; kg += 4) {
     float v[8];
     const int k = kg * 16 + 4 * h;
     if (r < rows) {
-      const float4 f0 = *reinterpret_cast<const float4*>(src + r * C + k), f1 = *reinterpret_cast<const float4*>(src + r * C + k + 8);
-      v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w; v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
-      const float4 g0 = *reinterpret_cast<const float4*>(gamma + k), g1 = *reinterpret_cast<const float4*>(gamma + k + 8);
-      const float4 b0 = *reinterpret_cast<const float4*>(beta + k), b1 = *reinterpret_cast<const float4*>(beta + k + 8);
-      const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w}, bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = (v[q] - mean) * rstd * gg[q] + bb[q];     // (the row loop's expression, bit for bit)
+      load8(x + r * C + k, v);
+      const float4 o0 = ln_affine4(make_float4(v[0], v[1], v[2], v[3]), mean, rstd, *reinterpret_cast<const float4*>(gamma + k),
+                                   *reinterpret_cast<const float4*>(beta + k));
+      const float4 o1 = ln_affine4(make_float4(v[4], v[5], v[6], v[7]), mean, rstd, *reinterpret_cast<const float4*>(gamma + k + 8),
+                                   *reinterpret_cast<const float4*>(beta + k + 8));
+      v[0] = o0.x; v[1] = o0.y; v[2] = o0.z; v[3] = o0.w; v[4] = o1.x; v[5] = o1.y; v[6] = o1.z; v[7] = o1.w;
     } else {
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = 0.f;
     }
-    f16x8_ h0, h1;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const float u = __builtin_amdgcn_ldexpf(v[q], -e);
-      h0[q] = (_Float16)u;
-      h1[q] = (_Float16)(u - (float)h0[q]);
-    }
-    char* q_ = planes + (long)kg * p_ks + (r >> 5) * 2048 + (h * 32 + (int)(r & 31)) * 16;
-    *reinterpret_cast<f16x8*>(q_) = h0;
-    *reinterpret_cast<f16x8*>(q_ + 1024) = h1;
+    split_store<NP>(v, e, plane_chunk<NP>(planes, p_ks, kg, r, h));
   }
 }
 
@@ -122,45 +93,32 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
   for (long r0 = (long)blockIdx.x * rpb; r0 < rows; r0 += (long)gridDim.x * rpb) {
     for (long r = r0 + wave; r < min(rows, r0 + rpb); r += 4) {
       const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+      float4* yr = reinterpret_cast<float4*>(y + r * C);
       float mean, rstd, amax = 0.f, sq = 0.f;
       if (C4 <= 4 * 64) {
         // the row lives in registers (<= 4 float4 per lane): ONE read instead of three dependent load -> reduce rounds per row
-        // (the same operations in the same order as the streaming form below: identical bits)
         float4 v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = (lane + 64 * j < C4) ? xr[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (lane + 64 * j < C4) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+          if (lane + 64 * j < C4) s += ln_sum4(v[j]);
         mean = wave_sum(s) / C;
         float q = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (lane + 64 * j < C4) {
-            const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-          }
+          if (lane + 64 * j < C4) q += ln_sqsum4(v[j], mean);
         const float var = wave_sum(q) / C;
         rstd = 1.0f / sqrtf(var + eps);
         if (y || h2) {
-          float4* yr = reinterpret_cast<float4*>(y + r * C);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int i = lane + 64 * j;
             if (i < C4) {
-              const float4 g = reinterpret_cast<const float4*>(gamma)[i];
-              const float4 b = reinterpret_cast<const float4*>(beta)[i];
-              float4 o;
-              o.x = (v[j].x - mean) * rstd * g.x + b.x;
-              o.y = (v[j].y - mean) * rstd * g.y + b.y;
-              o.z = (v[j].z - mean) * rstd * g.z + b.z;
-              o.w = (v[j].w - mean) * rstd * g.w + b.w;
+              const float4 o = ln_affine4(v[j], mean, rstd, reinterpret_cast<const float4*>(gamma)[i], reinterpret_cast<const float4*>(beta)[i]);
               if (y) yr[i] = o;
-              if (h2) {
-                amax = fmaxf(fmaxf(amax, fabsf(o.x)), fmaxf(fabsf(o.y), fmaxf(fabsf(o.z), fabsf(o.w))));
-                sq += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
-              }
+              if (h2) ln_bound4(o, amax, sq);
             }
           }
           if (h2) {
@@ -168,67 +126,95 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
             sq = wave_sum(sq);
           }
         }
-      } else {
-      float s = 0.f;
-      for (int i = lane; i < C4; i += 64) {
-        const float4 v = xr[i];
-        s += (v.x + v.y) + (v.z + v.w);
-      }
-      mean = wave_sum(s) / C;
-      float q = 0.f;
-      for (int i = lane; i < C4; i += 64) {
-        const float4 v = xr[i];
-        const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-        q += (a * a + b * b) + (c * c + d * d);
-      }
-      const float var = wave_sum(q) / C;
-      rstd = 1.0f / sqrtf(var + eps);
-      if (y || h2) {
-        float4* yr = reinterpret_cast<float4*>(y + r * C);
-        for (int i = lane; i < C4; i += 64) {
-          const float4 v = xr[i];
-          const float4 g = reinterpret_cast<const float4*>(gamma)[i];
-          const float4 b = reinterpret_cast<const float4*>(beta)[i];
-          float4 o;
-          o.x = (v.x - mean) * rstd * g.x + b.x;
-          o.y = (v.y - mean) * rstd * g.y + b.y;
-          o.z = (v.z - mean) * rstd * g.z + b.z;
-          o.w = (v.w - mean) * rstd * g.w + b.w;
-          if (y) yr[i] = o;
+      } else {   // the row is streamed three times: the same operations in the same order, identical bits
+        float s = 0.f;
+        for (int i = lane; i < C4; i += 64) s += ln_sum4(xr[i]);
+        mean = wave_sum(s) / C;
+        float q = 0.f;
+        for (int i = lane; i < C4; i += 64) q += ln_sqsum4(xr[i], mean);
+        const float var = wave_sum(q) / C;
+        rstd = 1.0f / sqrtf(var + eps);
+        if (y || h2) {
+          for (int i = lane; i < C4; i += 64) {
+            const float4 o = ln_affine4(xr[i], mean, rstd, reinterpret_cast<const float4*>(gamma)[i], reinterpret_cast<const float4*>(beta)[i]);
+            if (y) yr[i] = o;
+            if (h2) ln_bound4(o, amax, sq);
+          }
           if (h2) {
-            amax = fmaxf(fmaxf(amax, fabsf(o.x)), fmaxf(fabsf(o.y), fmaxf(fabsf(o.z), fabsf(o.w))));
-            sq += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
+            amax = wave_max(amax);
+            sq = wave_sum(sq);
           }
         }
-        if (h2) {
-          amax = wave_max(amax);
-          sq = wave_sum(sq);
-        }
-      }
       }
       if (lane == 0) {
         stats[2 * r] = mean;
         stats[2 * r + 1] = rstd;
         if (planes) { st_s[2 * (r - r0)] = mean; st_s[2 * (r - r0) + 1] = rstd; }
         if (h2) {
-          int e = amax > 0.f ? __builtin_amdgcn_frexp_expf(amax) - 15 : -15;    // (= scale_exp_of, csrc/gemm_planes_impl.h)
-          e = e < -100 ? -100 : (e > 100 ? 100 : e);
+          const int e = ln_row_exp(amax);
           se_s[r - r0] = e;
           sexp[r] = e;
-          if (rnorm) rnorm[r] = sqrtf(sq) * (1.f + 2e-5f);      // (an upper bound: fp32 sum of C squares, rounded up)
+          if (rnorm) rnorm[r] = ln_row_rnorm(sq);
         }
       }
     }
     if (planes) {
       __syncthreads();
-      if (h2) ln_emit_planes_h2(x, r0, rows, C, gamma, beta, st_s, se_s, planes, p_ks);
-      else ln_emit_planes(x, r0, rows, C, gamma, beta, st_s, planes, p_ks);
+      if (h2) ln_emit_planes<2>(x, r0, rows, C, gamma, beta, st_s, se_s, planes, p_ks);
+      else ln_emit_planes<3>(x, r0, rows, C, gamma, beta, st_s, se_s, planes, p_ks);
       __syncthreads();
     }
   }
 }
 
 constexpr int LN_MAXV = 4;  // float4 per lane
+// One row of the backward pass (C <= 1024, the row's operands re-read for the second loop: L1 hits).  acc(j, d, h0..h3):
+// what the weight gradients take from quad j (dy and the normalised x); store(i, o): where quad i of dx goes.
+struct LnNoAcc {
+  __device__ __forceinline__ void operator()(int, const float4&, float, float, float, float) const {}
+};
+template <typename Store, typename Acc = LnNoAcc>
+__device__ __forceinline__ void ln_bwd_row(const float* __restrict__ dy, const float* __restrict__ x,
+                                           const float* __restrict__ stats, const float* __restrict__ gamma, long r, int C,
+                                           int lane, const float* __restrict__ dx_add, Store&& store, Acc&& acc = Acc()) {
+  const int C4 = C >> 2;
+  const float mean = stats[2 * r], rstd = stats[2 * r + 1];
+  const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+  const float4* dr = reinterpret_cast<const float4*>(dy + r * C);
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int i = lane + 64 * j;
+    if (i < C4) {
+      const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
+      const float h0 = (v.x - mean) * rstd, h1 = (v.y - mean) * rstd, h2 = (v.z - mean) * rstd,
+                  h3 = (v.w - mean) * rstd;
+      const float g0 = d.x * g.x, g1 = d.y * g.y, g2 = d.z * g.z, g3 = d.w * g.w;
+      s1 += (g0 + g1) + (g2 + g3);
+      s2 += (g0 * h0 + g1 * h1) + (g2 * h2 + g3 * h3);
+      acc(j, d, h0, h1, h2, h3);
+    }
+  }
+  const float m1 = wave_sum(s1) / C, m2 = wave_sum(s2) / C;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int i = lane + 64 * j;
+    if (i < C4) {
+      const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
+      float4 o;
+      o.x = rstd * (d.x * g.x - m1 - (v.x - mean) * rstd * m2);
+      o.y = rstd * (d.y * g.y - m1 - (v.y - mean) * rstd * m2);
+      o.z = rstd * (d.z * g.z - m1 - (v.z - mean) * rstd * m2);
+      o.w = rstd * (d.w * g.w - m1 - (v.w - mean) * rstd * m2);
+      if (dx_add) {
+        const float4 a = reinterpret_cast<const float4*>(dx_add + r * C)[i];
+        o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
+      }
+      store(i, o);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ stats,
                                                             const float* __restrict__ gamma, long rows, int C,
@@ -244,45 +230,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   const long r0 = (long)blockIdx.x * rows_per_block;
   const long r1 = min(rows, r0 + rows_per_block);
   for (long r = r0 + wave; r < r1; r += 4) {
-    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
-    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
-    const float4* dr = reinterpret_cast<const float4*>(dy + r * C);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int i = lane + 64 * j;
-      if (i < C4) {
-        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
-        const float h0 = (v.x - mean) * rstd, h1 = (v.y - mean) * rstd, h2 = (v.z - mean) * rstd,
-                    h3 = (v.w - mean) * rstd;
-        const float g0 = d.x * g.x, g1 = d.y * g.y, g2 = d.z * g.z, g3 = d.w * g.w;
-        s1 += (g0 + g1) + (g2 + g3);
-        s2 += (g0 * h0 + g1 * h1) + (g2 * h2 + g3 * h3);
-        if (dg_part) {
-          ag[j].x += d.x * h0; ag[j].y += d.y * h1; ag[j].z += d.z * h2; ag[j].w += d.w * h3;
-          ab[j].x += d.x; ab[j].y += d.y; ab[j].z += d.z; ab[j].w += d.w;
-        }
-      }
-    }
-    const float m1 = wave_sum(s1) / C, m2 = wave_sum(s2) / C;
     float4* oxr = reinterpret_cast<float4*>(dx + r * C);
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int i = lane + 64 * j;
-      if (i < C4) {
-        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
-        float4 o;
-        o.x = rstd * (d.x * g.x - m1 - (v.x - mean) * rstd * m2);
-        o.y = rstd * (d.y * g.y - m1 - (v.y - mean) * rstd * m2);
-        o.z = rstd * (d.z * g.z - m1 - (v.z - mean) * rstd * m2);
-        o.w = rstd * (d.w * g.w - m1 - (v.w - mean) * rstd * m2);
-        if (dx_add) {
-          const float4 a = reinterpret_cast<const float4*>(dx_add + r * C)[i];
-          o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
-        }
-        oxr[i] = o;
-      }
-    }
+    ln_bwd_row(dy, x, stats, gamma, r, C, lane, dx_add, [&](int i, const float4 o) { oxr[i] = o; },
+               [&](int j, const float4& d, float h0, float h1, float h2, float h3) {
+                 if (dg_part) {
+                   ag[j].x += d.x * h0; ag[j].y += d.y * h1; ag[j].z += d.z * h2; ag[j].w += d.w * h3;
+                   ab[j].x += d.x; ab[j].y += d.y; ab[j].z += d.z; ab[j].w += d.w;
+                 }
+               });
   }
   if (dg_part) {
 #pragma unroll
@@ -772,37 +727,27 @@ struct LnPackOut {
   unsigned* tensor_amax;
 };
 
-// Phases 1 and 2 of the pack pass over tile[16][LNP_LD] (rows past `rows` hold zeros).  from_rows: the row pass already
-// left each row's exponent in s_e and its |max| in s_amax (and wrote sexp / rnorm itself): phase 1 is skipped.
+// Phases 1 and 2 of the pack pass (pack_planes_h2_kernel) over tile[16][LNP_LD] (rows past `rows` hold zeros).  from_rows:
+// the row pass already left each row's exponent in s_e and its |max| in s_amax (and wrote sexp / rnorm itself): phase 1
+// is skipped.
 __device__ __forceinline__ void lnp_pack_tile(const float* tile, int* s_e, float* s_amax, long r0, long rows,
                                               const LnPackOut& o, bool from_rows) {
   const int tid = threadIdx.x;
   __syncthreads();
-  if (!from_rows && tid < LNP_ROWS * 8) {   // 8 threads per row, 16 B each, the pack pass's strides and combine order
+  if (!from_rows && tid < LNP_ROWS * 8) {
     const int row = tid >> 3, sub = tid & 7;
     const long r = r0 + row;
     float amax = 0.f;
     double sq = 0.0;
-    if (r < rows) {
-      const float* src = tile + row * LNP_LD;
-      for (int k = sub * 4; k < LNP_C; k += 32) {
-        const float4 f = *reinterpret_cast<const float4*>(src + k);
-        amax = fmaxf(fmaxf(amax, fabsf(f.x)), fmaxf(fabsf(f.y), fmaxf(fabsf(f.z), fabsf(f.w))));
-        sq += (double)f.x * f.x + (double)f.y * f.y + ((double)f.z * f.z + (double)f.w * f.w);
-      }
-    }
-#pragma unroll
-    for (int q = 1; q < 8; q <<= 1) {
-      amax = fmaxf(amax, __shfl_xor(amax, q, 64));
-      sq += __shfl_xor(sq, q, 64);
-    }
+    if (r < rows) row_scan16(tile + row * LNP_LD, LNP_C, sub, amax, sq);
+    row_combine8(amax, sq);
     if (sub == 0) {
-      const int e = r < rows ? scale_exp_of(amax) : 0;
+      const int e = pack_exp(r < rows, amax);
       s_e[row] = e;
       s_amax[row] = amax;
       const long rr = o.row_off + r;
       o.sexp[rr] = e;
-      if (o.rnorm) o.rnorm[rr] = r < rows ? (float)(sqrt(sq) * (1.0 + 1e-6)) : 0.f;
+      if (o.rnorm) o.rnorm[rr] = pack_rnorm(r < rows, sq);
     }
   }
   if (!from_rows) __syncthreads();
@@ -813,15 +758,7 @@ __device__ __forceinline__ void lnp_pack_tile(const float* tile, int* s_e, float
   }
   for (int idx = tid; idx < (LNP_C >> 4) * 2 * LNP_ROWS; idx += LNP_NT) {
     const int r15 = idx & 15, h = (idx >> 4) & 1, kg = idx >> 5;
-    const float* src = tile + r15 * LNP_LD + kg * 16 + 4 * h;
-    const float4 f0 = *reinterpret_cast<const float4*>(src), f1 = *reinterpret_cast<const float4*>(src + 8);
-    const float v[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-    f16x8 h0, h1;
-    split2x8(v, s_e[r15], h0, h1);
-    const long rr = o.row_off + r0 + r15;
-    char* q_ = o.planes + (long)kg * o.p_ks + (rr >> 5) * 2048 + (h * 32 + (int)(rr & 31)) * 16;
-    *reinterpret_cast<f16x8*>(q_) = h0;
-    *reinterpret_cast<f16x8*>(q_ + 1024) = h1;
+    pack8<2>(tile + r15 * LNP_LD + kg * 16 + 4 * h, 1, true, true, s_e[r15], plane_chunk<2>(o.planes, o.p_ks, kg, o.row_off + r0 + r15, h));
   }
 }
 
@@ -830,12 +767,11 @@ __device__ __forceinline__ void lnp_pack_tile(const float* tile, int* s_e, float
 __global__ __launch_bounds__(LNP_NT) void layernorm_fwd_pack_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                     const float* __restrict__ beta, float eps, long rows, int C,
                                                                     float* __restrict__ y, float* __restrict__ stats,
-                                                                    LnPackOut o, int row_rnorm) {
+                                                                    int row_rnorm, LnPackOut o) {
   __shared__ __attribute__((aligned(16))) float tile[LNP_ROWS * LNP_LD];
   __shared__ int s_e[LNP_ROWS];
   __shared__ float s_amax[LNP_ROWS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int C4 = C >> 2;
   const long r0 = (long)blockIdx.x * LNP_ROWS;
 #pragma unroll
   for (int rw = 0; rw < 2; ++rw) {
@@ -848,44 +784,33 @@ __global__ __launch_bounds__(LNP_NT) void layernorm_fwd_pack_kernel(const float*
       if (lane == 0) { s_e[row] = 0; s_amax[row] = 0.f; }
       continue;
     }
-    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+    float4* yr = reinterpret_cast<float4*>(y + r * C);
     float mean, rstd, amax = 0.f, sq = 0.f;
-    // (layernorm_fwd_kernel's register-row form, operation for operation)
+    // (the register-row loop of layernorm_fwd_kernel, over the same quad-level steps)
+    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
+    const int C4 = C >> 2;
     float4 v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = (lane + 64 * j < C4) ? xr[lane + 64 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (lane + 64 * j < C4) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+      if (lane + 64 * j < C4) s += ln_sum4(v[j]);
     mean = wave_sum(s) / C;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (lane + 64 * j < C4) {
-        const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
-        q += (a * a + b * b) + (c * c + d * d);
-      }
+      if (lane + 64 * j < C4) q += ln_sqsum4(v[j], mean);
     const float var = wave_sum(q) / C;
     rstd = 1.0f / sqrtf(var + eps);
-    float4* yr = reinterpret_cast<float4*>(y + r * C);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int i = lane + 64 * j;
       if (i < C4) {
-        const float4 g = reinterpret_cast<const float4*>(gamma)[i];
-        const float4 b = reinterpret_cast<const float4*>(beta)[i];
-        float4 ov;
-        ov.x = (v[j].x - mean) * rstd * g.x + b.x;
-        ov.y = (v[j].y - mean) * rstd * g.y + b.y;
-        ov.z = (v[j].z - mean) * rstd * g.z + b.z;
-        ov.w = (v[j].w - mean) * rstd * g.w + b.w;
+        const float4 ov = ln_affine4(v[j], mean, rstd, reinterpret_cast<const float4*>(gamma)[i], reinterpret_cast<const float4*>(beta)[i]);
         if (y) yr[i] = ov;
         tr[i] = ov;
-        if (row_rnorm) {
-          amax = fmaxf(fmaxf(amax, fabsf(ov.x)), fmaxf(fabsf(ov.y), fmaxf(fabsf(ov.z), fabsf(ov.w))));
-          sq += (ov.x * ov.x + ov.y * ov.y) + (ov.z * ov.z + ov.w * ov.w);
-        }
+        if (row_rnorm) ln_bound4(ov, amax, sq);
       }
     }
     if (row_rnorm) {
@@ -896,11 +821,11 @@ __global__ __launch_bounds__(LNP_NT) void layernorm_fwd_pack_kernel(const float*
       stats[2 * r] = mean;
       stats[2 * r + 1] = rstd;
       if (row_rnorm) {
-        const int e = amax > 0.f ? scale_exp_of(amax) : -15;
+        const int e = ln_row_exp(amax);
         s_e[row] = e;
         s_amax[row] = amax;
         o.sexp[o.row_off + r] = e;
-        if (o.rnorm) o.rnorm[o.row_off + r] = sqrtf(sq) * (1.f + 2e-5f);
+        if (o.rnorm) o.rnorm[o.row_off + r] = ln_row_rnorm(sq);
       }
     }
   }
@@ -917,7 +842,6 @@ __global__ __launch_bounds__(LNP_NT) void layernorm_bwd_pack_kernel(const float*
   __shared__ int s_e[LNP_ROWS];
   __shared__ float s_amax[LNP_ROWS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int C4 = C >> 2;
   const long r0 = (long)blockIdx.x * LNP_ROWS;
 #pragma unroll
   for (int rw = 0; rw < 2; ++rw) {
@@ -929,43 +853,11 @@ __global__ __launch_bounds__(LNP_NT) void layernorm_bwd_pack_kernel(const float*
       for (int j = 0; j < 3; ++j) tr[lane + 64 * j] = make_float4(0.f, 0.f, 0.f, 0.f);
       continue;
     }
-    // (layernorm_bwd_kernel's row loop, operation for operation)
-    const float mean = stats[2 * r], rstd = stats[2 * r + 1];
-    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
-    const float4* dr = reinterpret_cast<const float4*>(dy + r * C);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int i = lane + 64 * j;
-      if (i < C4) {
-        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
-        const float h0 = (v.x - mean) * rstd, h1 = (v.y - mean) * rstd, h2 = (v.z - mean) * rstd,
-                    h3 = (v.w - mean) * rstd;
-        const float g0 = d.x * g.x, g1 = d.y * g.y, g2 = d.z * g.z, g3 = d.w * g.w;
-        s1 += (g0 + g1) + (g2 + g3);
-        s2 += (g0 * h0 + g1 * h1) + (g2 * h2 + g3 * h3);
-      }
-    }
-    const float m1 = wave_sum(s1) / C, m2 = wave_sum(s2) / C;
     float4* oxr = reinterpret_cast<float4*>(dx + r * C);
-#pragma unroll
-    for (int j = 0; j < LN_MAXV; ++j) {
-      const int i = lane + 64 * j;
-      if (i < C4) {
-        const float4 v = xr[i], d = dr[i], g = reinterpret_cast<const float4*>(gamma)[i];
-        float4 ov;
-        ov.x = rstd * (d.x * g.x - m1 - (v.x - mean) * rstd * m2);
-        ov.y = rstd * (d.y * g.y - m1 - (v.y - mean) * rstd * m2);
-        ov.z = rstd * (d.z * g.z - m1 - (v.z - mean) * rstd * m2);
-        ov.w = rstd * (d.w * g.w - m1 - (v.w - mean) * rstd * m2);
-        if (dx_add) {
-          const float4 a = reinterpret_cast<const float4*>(dx_add + r * C)[i];
-          ov.x += a.x; ov.y += a.y; ov.z += a.z; ov.w += a.w;
-        }
-        oxr[i] = ov;
-        tr[i] = ov;
-      }
-    }
+    ln_bwd_row(dy, x, stats, gamma, r, C, lane, dx_add, [&](int i, const float4 ov) {
+      oxr[i] = ov;
+      tr[i] = ov;
+    });
   }
   lnp_pack_tile(tile, s_e, s_amax, r0, rows, o, false);
 }
@@ -993,36 +885,56 @@ inline bool gn_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-extern "C" int svl_layernorm_fwd_planes(const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
-                                        int C, float* y, float* stats, void* planes, int64_t planes_rows,
-                                        svl_stream_t stream) {
-  SVL_CHECK_ARG(x && gamma && beta && (y || planes) && stats && rows > 0 && C > 0 && C % 4 == 0,
-                "svl_layernorm_fwd: bad args");
-  SVL_CHECK_ARG(!planes || (C % 16 == 0 && planes_rows >= rows && planes_rows % 256 == 0),
-                "svl_layernorm_fwd_planes: C %% 16 == 0 and planes_rows (%% 256 == 0) >= rows");
-  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
-                "svl_layernorm_fwd: x / y / gamma / beta must be 16-byte aligned");
+namespace {
+// The checks every LayerNorm entry point makes first, under its name `who` (`detail`: what follows "bad args" in its
+// message): its own argument condition, then the condition of an optional operand (`opt_ok`, reported as `opt_msg`), then
+// the 16-byte alignment of every tensor a kernel reads or writes as float4.
+int ln_fwd_check(const char* who, const char* detail, bool args_ok, bool opt_ok, const char* opt_msg, const float* x,
+                 const float* y, const float* gamma, const float* beta) {
+  SVL_CHECK_ARG(args_ok, "%s: bad args%s", who, detail);
+  SVL_CHECK_ARG(opt_ok, "%s", opt_msg);
+  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta), "%s: x / y / gamma / beta must be 16-byte aligned", who);
+  return SVL_OK;
+}
+int ln_bwd_check(const char* who, const char* detail, bool args_ok, bool opt_ok, const char* opt_msg, const float* dy,
+                 const float* x, const float* gamma, const float* dx_add, const float* dx) {
+  SVL_CHECK_ARG(args_ok, "%s: bad args%s", who, detail);
+  SVL_CHECK_ARG(opt_ok, "%s", opt_msg);
+  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(gamma) && gn_al16(dx_add) && gn_al16(dx),
+                "%s: dy / x / gamma / dx_add / dx must be 16-byte aligned", who);
+  return SVL_OK;
+}
+// layernorm_fwd_kernel on row blocks of rpb rows (4, or 32 with planes of `np` planes per chunk)
+int ln_fwd_launch(const char* who, const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C, float* y,
+                  float* stats, void* planes, int64_t planes_rows, int np, int32_t* sexp, float* rnorm, svl_stream_t stream) {
   const long rpb = planes ? 32 : 4;
   const int grid = (int)((rows + rpb - 1) / rpb > 4096 * 4 ? 4096 * 4 : (rows + rpb - 1) / rpb);
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
-                     (long)rows, C, y, stats, (char*)planes, (long)planes_rows * 96, (int*)nullptr, (float*)nullptr);
-  SVL_LAUNCH_CHECK("svl_layernorm_fwd");
+                     (long)rows, C, y, stats, (char*)planes, (long)planes_rows * 32 * np, sexp, rnorm);
+  SVL_LAUNCH_CHECK(who);
   return SVL_OK;
+}
+}  // namespace
+
+extern "C" int svl_layernorm_fwd_planes(const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
+                                        int C, float* y, float* stats, void* planes, int64_t planes_rows,
+                                        svl_stream_t stream) {
+  if (int rc = ln_fwd_check("svl_layernorm_fwd", "", x && gamma && beta && (y || planes) && stats && rows > 0 && C > 0 && C % 4 == 0,
+                            !planes || (C % 16 == 0 && planes_rows >= rows && planes_rows % 256 == 0),
+                            "svl_layernorm_fwd_planes: C % 16 == 0 and planes_rows (% 256 == 0) >= rows", x, y, gamma, beta))
+    return rc;
+  return ln_fwd_launch("svl_layernorm_fwd", x, gamma, beta, eps, rows, C, y, stats, planes, planes_rows, 3, nullptr, nullptr, stream);
 }
 extern "C" int svl_layernorm_fwd_planes_f16x2(const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
                                               int C, float* y, float* stats, void* planes, int64_t planes_rows, int32_t* sexp,
                                               float* rnorm, svl_stream_t stream) {
-  SVL_CHECK_ARG(x && gamma && beta && planes && sexp && stats && rows > 0 && C > 0 && C % 16 == 0 && planes_rows >= rows &&
-                    planes_rows % 256 == 0,
-                "svl_layernorm_fwd_planes_f16x2: bad args (C %% 16 == 0, planes_rows (%% 256 == 0) >= rows, sexp required)");
-  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
-                "svl_layernorm_fwd_planes_f16x2: x / y / gamma / beta must be 16-byte aligned");
-  const long nb = (rows + 31) / 32;
-  const int grid = (int)(nb > 4096 * 4 ? 4096 * 4 : nb);
-  hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
-                     (long)rows, C, y, stats, (char*)planes, (long)planes_rows * 64, sexp, rnorm);
-  SVL_LAUNCH_CHECK("svl_layernorm_fwd_planes_f16x2");
-  return SVL_OK;
+  if (int rc = ln_fwd_check("svl_layernorm_fwd_planes_f16x2", " (C % 16 == 0, planes_rows (% 256 == 0) >= rows, sexp required)",
+                            x && gamma && beta && planes && sexp && stats && rows > 0 && C > 0 && C % 16 == 0 &&
+                                planes_rows >= rows && planes_rows % 256 == 0,
+                            true, "", x, y, gamma, beta))
+    return rc;
+  return ln_fwd_launch("svl_layernorm_fwd_planes_f16x2", x, gamma, beta, eps, rows, C, y, stats, planes, planes_rows, 2, sexp, rnorm,
+                       stream);
 }
 extern "C" int svl_layernorm_fwd(const float* x, const float* gamma, const float* beta, float eps, int64_t rows, int C,
                                  float* y, float* stats, svl_stream_t stream) {
@@ -1040,11 +952,12 @@ extern "C" int svl_layernorm_bwd_parts(int64_t rows) {
 extern "C" int svl_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, int64_t rows,
                                  int C, const float* dx_add, float* dx, float* dgamma_part, float* dbeta_part,
                                  svl_stream_t stream) {
-  SVL_CHECK_ARG(dy && x && stats && gamma && dx && rows > 0 && C > 0 && C % 4 == 0 && C <= 1024,
-                "svl_layernorm_bwd: bad args (C=%d)", C);
-  SVL_CHECK_ARG((dgamma_part == nullptr) == (dbeta_part == nullptr), "svl_layernorm_bwd: dgamma/dbeta go together");
-  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(gamma) && gn_al16(dx_add) && gn_al16(dx),
-                "svl_layernorm_bwd: dy / x / gamma / dx_add / dx must be 16-byte aligned");
+  char detail[32];
+  snprintf(detail, sizeof detail, " (C=%d)", C);
+  if (int rc = ln_bwd_check("svl_layernorm_bwd", detail, dy && x && stats && gamma && dx && rows > 0 && C > 0 && C % 4 == 0 && C <= 1024,
+                            (dgamma_part == nullptr) == (dbeta_part == nullptr), "svl_layernorm_bwd: dgamma/dbeta go together", dy, x,
+                            gamma, dx_add, dx))
+    return rc;
   // With weight gradients a block keeps per-column partial sums over its rows (few, long blocks: nparts slabs to reduce).
   // Without them (the ViT's frozen LayerNorms: every call of the encoder's backward) nothing ties rows together: 8 rows per
   // block, i.e. two per wave -- the row loop is a load -> two wave reductions -> store chain, and only many resident waves
@@ -1068,40 +981,39 @@ int lnp_check(const char* who, int64_t rows, int C, const void* planes, int64_t 
                 "%s: bad args (planes_rows %% 256, row_off %% 32 must be 0, planes_rows >= row_off + rows; sexp required)", who);
   return SVL_OK;
 }
+// The launch of a pack kernel on `args` and the LnPackOut: one block per half row block, tensor_amax zeroed on the stream first.
+template <typename K, typename... Args>
+int lnp_launch(const char* who, K kernel, int64_t rows, void* planes, int64_t planes_rows, int64_t row_off, int32_t* sexp,
+               float* rnorm, unsigned* tensor_amax, svl_stream_t stream, Args... args) {
+  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
+  const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
+  const long nhb = (rows + 31) / 32 * 2;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nhb), dim3(LNP_NT), 0, (hipStream_t)stream, args..., o);
+  SVL_LAUNCH_CHECK(who);
+  return SVL_OK;
+}
 }  // namespace
 
 extern "C" int svl_layernorm_fwd_pack_f16x2(const float* x, const float* gamma, const float* beta, float eps, int64_t rows,
                                             int C, float* y, float* stats, void* planes, int64_t planes_rows,
                                             int64_t row_off, int32_t* sexp, float* rnorm, int row_rnorm,
                                             unsigned* tensor_amax, svl_stream_t stream) {
-  SVL_CHECK_ARG(x && gamma && beta && stats, "svl_layernorm_fwd_pack_f16x2: bad args");
-  SVL_CHECK_ARG(gn_al16(x) && gn_al16(y) && gn_al16(gamma) && gn_al16(beta),
-                "svl_layernorm_fwd_pack_f16x2: x / y / gamma / beta must be 16-byte aligned");
-  if (int rc = lnp_check("svl_layernorm_fwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
-  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
-  const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
-  const long nhb = (rows + 31) / 32 * 2;
-  hipLaunchKernelGGL(layernorm_fwd_pack_kernel, dim3((unsigned)nhb), dim3(LNP_NT), 0, (hipStream_t)stream, x, gamma, beta,
-                     eps, (long)rows, C, y, stats, o, row_rnorm ? 1 : 0);
-  SVL_LAUNCH_CHECK("svl_layernorm_fwd_pack_f16x2");
-  return SVL_OK;
+  const char* who = "svl_layernorm_fwd_pack_f16x2";
+  if (int rc = ln_fwd_check(who, "", x && gamma && beta && stats, true, "", x, y, gamma, beta)) return rc;
+  if (int rc = lnp_check(who, rows, C, planes, planes_rows, row_off, sexp)) return rc;
+  return lnp_launch(who, layernorm_fwd_pack_kernel, rows, planes, planes_rows, row_off, sexp, rnorm, tensor_amax, stream, x, gamma,
+                    beta, eps, (long)rows, C, y, stats, row_rnorm ? 1 : 0);
 }
 
 extern "C" int svl_layernorm_bwd_pack_f16x2(const float* dy, const float* x, const float* stats, const float* gamma,
                                             int64_t rows, int C, const float* dx_add, float* dx, void* planes,
                                             int64_t planes_rows, int64_t row_off, int32_t* sexp, float* rnorm,
                                             unsigned* tensor_amax, svl_stream_t stream) {
-  SVL_CHECK_ARG(dy && x && stats && gamma && dx, "svl_layernorm_bwd_pack_f16x2: bad args");
-  SVL_CHECK_ARG(gn_al16(dy) && gn_al16(x) && gn_al16(gamma) && gn_al16(dx_add) && gn_al16(dx),
-                "svl_layernorm_bwd_pack_f16x2: dy / x / gamma / dx_add / dx must be 16-byte aligned");
-  if (int rc = lnp_check("svl_layernorm_bwd_pack_f16x2", rows, C, planes, planes_rows, row_off, sexp)) return rc;
-  if (tensor_amax) SVL_HIP_CHECK(hipMemsetAsync(tensor_amax, 0, 4, (hipStream_t)stream));
-  const LnPackOut o = {(char*)planes, (long)planes_rows * 64, (long)row_off, sexp, rnorm, tensor_amax};
-  const long nhb = (rows + 31) / 32 * 2;
-  hipLaunchKernelGGL(layernorm_bwd_pack_kernel, dim3((unsigned)nhb), dim3(LNP_NT), 0, (hipStream_t)stream, dy, x, stats,
-                     gamma, (long)rows, C, dx_add, dx, o);
-  SVL_LAUNCH_CHECK("svl_layernorm_bwd_pack_f16x2");
-  return SVL_OK;
+  const char* who = "svl_layernorm_bwd_pack_f16x2";
+  if (int rc = ln_bwd_check(who, "", dy && x && stats && gamma && dx, true, "", dy, x, gamma, dx_add, dx)) return rc;
+  if (int rc = lnp_check(who, rows, C, planes, planes_rows, row_off, sexp)) return rc;
+  return lnp_launch(who, layernorm_bwd_pack_kernel, rows, planes, planes_rows, row_off, sexp, rnorm, tensor_amax, stream, dy, x, stats,
+                    gamma, (long)rows, C, dx_add, dx);
 }
 
 extern "C" int svl_softmax_rows_fwd(float* s, int64_t rows, int cols, int64_t ld, float scale, svl_stream_t stream) {

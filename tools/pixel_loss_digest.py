@@ -119,7 +119,8 @@ def compare(pa, pb):
     return 1 if bad else 0
 
 
-def main():
+def main(run=run, tool="pixel_loss_digest"):
+    """Command line of this tool and of the digest tools that import it (each with its own `run` and name)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."),
                     help="the tree whose semivl_amd (and built library) to run")
@@ -129,9 +130,9 @@ def main():
     if a.compare:
         return compare(*a.compare)
     if not torch.cuda.is_available():
-        raise SystemExit("pixel_loss_digest: needs the GPU")
+        raise SystemExit(f"{tool}: needs the GPU")
     sys.path.insert(0, os.path.abspath(a.root))
-    res = dict(tool="pixel_loss_digest", device=torch.cuda.get_device_name(0), digests=run(torch.device("cuda:0")))
+    res = dict(tool=tool, device=torch.cuda.get_device_name(0), digests=run(torch.device("cuda:0")))
     print(f"{len(res['digests'])} digests")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
