@@ -22,13 +22,11 @@
 // MFMA layout as in conv_tiled.hip: A = 32 pixels (one image row) x 16 channels, B = 16 channels x 32 outputs; an accumulator's
 // column (lane & 31) is an output channel, its rows are the pixels of the row.
 #include "conv_dil.h"
+#include "planes_split.h"
 #include <stdlib.h>
 #include <atomic>
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DW = 32, DH = 32, DPX = DW * DH, DSLAB = 16, DNB = 64;   // image, slab depth, output channels per block
 constexpr int D_XPL = DPX * 16 + 8;                    // x plane stride (16-bit elements): the image + one 16-byte zero block
@@ -122,30 +120,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto xmax = [&]() __attribute__((always_inline)) {
     float m = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(rx[i].x), fabsf(rx[i].y)), fmaxf(fabsf(rx[i].z), fabsf(rx[i].w))));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) smax[wave] = m;
+    for (int i = 0; i < 16; ++i) m = fmaxf(m, absmax4(rx[i]));
+    wave_max_to(m, smax, lane, wave);
   };
-  auto exp_of = [](float mx) {      // mx 2^-e in [2^14, 2^15)  (fp16 overflows at 65504); an all-zero slab takes the floor
-    const int e = mx > 0.f ? __builtin_amdgcn_frexp_expf(mx) - 15 : -100;
-    return e < -100 ? -100 : (e > 100 ? 100 : e);
-  };
-  auto block_exp = [&]() __attribute__((always_inline)) {
-    return exp_of(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
-  };
+  // (a plain lambda, inlined after the always-inline steps: with slab_exp_of called directly the allocator spills 68 instead of 52 B
+  //  per lane.  Before removing it compare the kernel's scratch as profiles/conv_tiled_refactor.md does.)
+  auto exp_of = [](float mx) { return slab_exp_of(mx); };
+  auto block_exp = [&]() __attribute__((always_inline)) { return exp_of(block_max4(smax)); };
   auto sstore = [&](int e) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const float v[4] = {__builtin_amdgcn_ldexpf(rx[i].x, -e), __builtin_amdgcn_ldexpf(rx[i].y, -e),
-                          __builtin_amdgcn_ldexpf(rx[i].z, -e), __builtin_amdgcn_ldexpf(rx[i].w, -e)};
       f16x4 h0, h1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        h0[j] = (_Float16)v[j];
-        h1[j] = (_Float16)(v[j] - (float)h0[j]);
-      }
+      split2x4(rx[i], e, h0, h1);
       const int o = ((tid >> 2) + 64 * i) * 16 + 4 * (tid & 3);
       *reinterpret_cast<f16x4*>(xs + o) = h0;
       *reinterpret_cast<f16x4*>(xs + D_XPL + o) = h1;

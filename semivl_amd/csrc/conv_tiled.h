@@ -23,10 +23,20 @@ struct ConvTiledP {
   const float* gnb_table;                           // [imgs][2][N] (scale, shift) of that GroupNorm (svl_groupnorm_scale_shift)
   const float* gnb_stats;                           // [imgs][N / 16][2] (mean, rstd)
   double* gnb_part;
-  const void* w_planes;                             // null, or the weights pre-split into the bf16 planes image of the split
-                                                    // kernel's LDS weight buffer (svl_conv3x3_weight_planes): staging a
-                                                    // slab's weights is then a copy instead of 9 N 16 splits per block
+  const void* w_planes;                             // null, or the weights pre-split into the fp16 x 2 planes image of the
+                                                    // split kernel's LDS weight buffer, per-channel exponents behind it
+                                                    // (svl_conv3x3_weight_planes): the launch runs on three products, and
+                                                    // staging a slab's weights is a copy instead of 9 N 16 splits per block
 };
+
+// Every optional field off (null / 0), one source, correlation taps, no activation: callers name only what they use
+inline ConvTiledP svl_conv3x3_tiled_params() {
+  ConvTiledP t = {};
+  t.rep = 1;
+  t.sign = 1;
+  t.act = SVL_ACT_NONE;
+  return t;
+}
 
 int svl_conv3x3_tiled_path();    // SVL_PATH_BF16X (mode 6, unless SVL_CONV_TILED_NO_EMU) or SVL_PATH_F32: the pipe the tiled kernels run on
 bool svl_conv3x3_tiled_eligible(const ConvTiledP& p);

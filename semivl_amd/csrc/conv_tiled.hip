@@ -5,7 +5,13 @@
 // an 8 x 16 output patch: the 10 x 18 input patch (halo included) of a 16-channel slab is staged in LDS ONCE and all 9
 // taps read it with immediate offsets, the slab's 9 x 16 x N weights sit next to it, and a wave runs 72 x N/32 MFMAs
 // between barriers.  fp32 v_mfma_f32_32x32x2_f32 as everywhere else (A = pixels x channels, B = channels x outputs).
+//
+// Structure: conv3x3_tiled_kernel<TN> (fp32), conv3x3_tiled_h2_kernel<TN, PT> (fp16 x 2 terms) and conv3x3_tiled_bf16x_kernel<TN,
+// PT> (bf16 x 3 terms) share ONE epilogue (tile_epilogue, with gn_tile_partials / gnb_tile_partials) and tile_origin; the first
+// two also share the staging steps slab_source, load_pixel_piece, operand4 (and gn_quad, xs_piece_off), which the bf16 x 3
+// kernel keeps written out (see the note above it); the weight-gradient kernels below share tile_origin and operand4.
 #include "conv_tiled.h"
+#include "planes_split.h"
 #include <stdlib.h>
 #include <atomic>
 
@@ -14,6 +20,41 @@ namespace {
 constexpr int PH = 8, PW = 16, IH = PH + 2, IW = PW + 2, SLAB = 16, XS = SLAB + 1;
 constexpr int NPIX = IH * IW;  // 180
 
+// ---- staging steps shared by the kernels of this file
+// tile index -> image and origin of its patch (`rows` patch rows per tile, PW columns)
+__device__ __forceinline__ void tile_origin(int t, int tiles_x, int tiles_y, int rows, int& img, int& y0, int& x0) {
+  const int txi = t % tiles_x;
+  t /= tiles_x;
+  const int tyi = t % tiles_y;
+  img = t / tiles_y;
+  y0 = tyi * rows;
+  x0 = txi * PW;
+}
+// slab c0 (16 channels) of image img: its channels at pixel (0, 0) and the pixel stride; true = the first concat source
+__device__ __forceinline__ bool slab_source(const ConvTiledP& p, int img, int c0, const float*& base, long& ld) {
+  const bool first = c0 < p.C1;
+  base = first ? p.src1 + ((long)img * p.H) * p.W * p.ld1 + c0 : p.src2 + ((long)(img / p.rep) * p.H) * p.W * p.ld2 + (c0 - p.C1);
+  ld = first ? p.ld1 : p.ld2;
+  return first;
+}
+// gn_in: (scale, shift) of this thread's channel quad (4 (tid & 3): the same for all of a thread's pieces)
+__device__ __forceinline__ void gn_quad(const ConvTiledP& p, int img, int c0, int tid, float4& sc, float4& sh) {
+  sc = *reinterpret_cast<const float4*>(p.gn_in + ((long)img * 2 + 0) * p.C1 + c0 + 4 * (tid & 3));
+  sh = *reinterpret_cast<const float4*>(p.gn_in + ((long)img * 2 + 1) * p.C1 + c0 + 4 * (tid & 3));
+}
+// Piece f (pixel f >> 2 of the NPX-pixel halo patch at (y0 - 1, x0 - 1), channel quad f & 3) of a slab; returns whether the
+// piece lies inside the image.  UNCONDITIONAL load from a clamped pixel, masked when the piece is stored: a load under a
+// per-lane condition becomes an exec-masked branch, and the s_waitcnt the compiler then needs before re-defining the
+// destination registers at the next piece exposed the whole HBM latency of the prefetch once per slab (round 4 counters)
+template <int NPX>
+__device__ __forceinline__ bool load_pixel_piece(const float* base, long ld, int f, int y0, int x0, int H, int W, float4& v) {
+  const int pix = min(f >> 2, NPX - 1), q = f & 3;
+  const int iy = pix / IW, ix = pix - iy * IW;
+  const int y = y0 - 1 + iy, x = x0 - 1 + ix;
+  const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), W - 1);
+  v = *reinterpret_cast<const float4*>(base + ((long)yc * W + xc) * ld + 4 * q);
+  return f < NPX * 4 && y >= 0 && y < H && x >= 0 && x < W;
+}
 // GroupNorm + ReLU of a staged operand quad (gn_in): the apply kernel's own expression, fmaxf(fma(x, sc, sh), 0).
 __device__ __forceinline__ float4 gn_relu4(const float4 v, const float4 sc, const float4 sh, unsigned in_image) {
   float4 o;
@@ -23,12 +64,18 @@ __device__ __forceinline__ float4 gn_relu4(const float4 v, const float4 sc, cons
   o.w = in_image ? fmaxf(__builtin_fmaf(v.w, sc.w, sh.w), 0.f) : 0.f;
   return o;
 }
+// The OPERAND value of a loaded piece: GroupNorm + ReLU applied when the slab is normalised (`gn`), out-of-image pixels zero
+// (the zero padding stays zero: it pads y, not pre)
+__device__ __forceinline__ float4 operand4(const float4 v, bool gn, const float4 sc, const float4 sh, unsigned in_image) {
+  return gn ? gn_relu4(v, sc, sh, in_image) : (in_image ? v : make_float4(0.f, 0.f, 0.f, 0.f));
+}
 
+// ---- the tile epilogue
 // GroupNorm statistics in the convolution's epilogue (vlg_head.py:116-137: every narrow 3x3 convolution feeds a
 // GroupNorm over groups of 16 channels).  A wave's accumulator columns are channels (lane & 31: two groups per 32-column
 // tile), its rows pixels: every lane adds up its own valid pixels in fp32 (<= 32 values), the 32 lanes of a group (16
 // channels x 2 row halves) and then the four waves are combined in DOUBLE in a fixed order, and the block leaves one (sum,
-// sum of squares) pair per group in p.gn_part[blockIdx.x] -- a statistics pass over the tensor (4 B per element of HBM
+// sum of squares) pair per group in p.gn_part[slot] -- a statistics pass over the tensor (4 B per element of HBM
 // reads) becomes ~60 instructions per wave.  gn_finalize_kernel adds an image's tiles up (fixed order: deterministic,
 // independent of how many images share the launch).
 template <int TN>
@@ -64,6 +111,130 @@ __device__ __forceinline__ void gn_tile_partials(const ConvTiledP& p, const doub
     o[1] = tq;
   }
 }
+// GroupNorm-BACKWARD channel sums of a tile (ConvTiledP::gnb_*): lanes hi = 0 / 1 hold different pixel rows of the same channel;
+// then the four waves through red [4][32 TN][2], added in a fixed order, into p.gnb_part[slot].  (wave, l31, hi are the CALLER's:
+// formed again from tid here they cost the split kernels 4 - 9 VGPRs, and <1, 2, 3> then sits at the 256 its occupancy allows --
+// profiles/conv_tiled_refactor.md)
+template <int TN>
+__device__ __forceinline__ void gnb_tile_partials(const ConvTiledP& p, const double (&a)[TN], const double (&b)[TN],
+                                                  double (*red)[32 * TN][2], int tid, long slot, int wave, int l31, int hi) {
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const double a2 = a[j] + __shfl_xor(a[j], 32, 64), b2 = b[j] + __shfl_xor(b[j], 32, 64);
+    if (hi == 0) {
+      red[wave][l31 + 32 * j][0] = a2;
+      red[wave][l31 + 32 * j][1] = b2;
+    }
+  }
+  __syncthreads();
+  if (tid < 32 * TN) {
+    double* o = p.gnb_part + (slot * (32 * TN) + tid) * 2;
+    o[0] = (red[0][tid][0] + red[1][tid][0]) + (red[2][tid][0] + red[3][tid][0]);
+    o[1] = (red[0][tid][1] + red[1][tid][1]) + (red[2][tid][1] + red[3][tid][1]);
+  }
+}
+
+// Epilogue of the tile `slot` = patch (y0, x0) of image img, written ONCE for the fp32 and the split kernels and called from ONE
+// site per kernel (a second site makes the allocator mirror every accumulator in arch registers: DESIGN.md, conv_dil.hip).
+// C layout: column = output channel (l31 + 32 j), row i = (r & 3) + 8 (r >> 2) + 4 hi = pixel (i >> 4, i & 15) of the wave's
+// pixel tile u.  Straight-line (see gemm_epilogue): uniform decisions once per 32-channel block, previous values (accumulate)
+// read before the first store, one pointer per block plus per-register pixel offsets -- formed once per pixel tile in 32 bits
+// and CLAMPED into the image, so that the loads need no condition (only the stores are masked).  In the split kernels the
+// stores drain under the next tile's first MFMA phase, and the epilogue's VALU instructions wait for gaps in the other
+// block's MFMA stream like every VALU instruction of a staging phase.  The accumulators are zero afterwards.
+//   UNDO: the accumulators hold sums of operands scaled by 2^-e_acc and weights scaled by 2^-wexp[channel] (fp16 x 2 form);
+//   GNB:  the kernel serves ConvTiledP::gnb_part (red_b [4][N][2]).   red_s: [4 TN 2 2] doubles for p.gn_part.
+template <int TN, int PT, bool UNDO, bool GNB>
+__device__ __forceinline__ void tile_epilogue(const ConvTiledP& p, f32x16 (&acc)[PT][TN], int img, int y0, int x0, int e_acc,
+                                              const int* wexp, double* red_s, double (*red_b)[32 * TN][2], int tid, long slot) {
+  constexpr int N = 32 * TN;
+  const int lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+  double gs[TN], gq[TN], ba[TN], bb[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) gs[j] = gq[j] = ba[j] = bb[j] = 0.0;
+  {
+    float* obase = p.out + (long)img * p.H * p.W * p.ldo + l31;
+    const float* xbase = GNB && p.gnb_x ? p.gnb_x + (long)img * p.H * p.W * p.ldo + l31 : nullptr;
+    const int ldo = (int)p.ldo;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+      int off[16];
+      unsigned okm = 0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int y = y0 + wave * 2 * PT + 2 * u + (i >> 4), x = x0 + (i & 15);
+        okm |= (y < p.H && x < p.W) ? (1u << r) : 0u;
+        off[r] = (min(y, p.H - 1) * p.W + min(x, p.W - 1)) * ldo;
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const float bv = p.bias ? p.bias[l31 + 32 * j] : 0.f;
+        float* ob = obase + 32 * j;
+        float v[16];
+        if constexpr (UNDO) {
+          const int es = e_acc + wexp[l31 + 32 * j];     // undo the slab scale and this output channel's weight scale (exact)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            v[r] = __builtin_amdgcn_ldexpf(acc[u][j][r], es) + bv;
+            acc[u][j][r] = 0.f;
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            v[r] = acc[u][j][r] + bv;
+            acc[u][j][r] = 0.f;
+          }
+        }
+        if (p.gn_part) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const double t = ((okm >> r) & 1u) ? (double)v[r] : 0.0;
+            gs[j] += t;
+            gq[j] += t * t;
+          }
+        }
+        if (p.act == SVL_ACT_GELU) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) v[r] = gelu_erf(v[r]);
+        } else if (p.act == SVL_ACT_RELU) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
+        }
+        if (p.accumulate) {
+          float prev[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) prev[r] = ob[off[r]];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) v[r] += prev[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if ((okm >> r) & 1u) ob[off[r]] = v[r];
+        if (GNB && p.gnb_part) {
+          // this lane's channel c = l31 + 32 j of the GroupNorm whose dy was just written: mask from the forward's own fma,
+          // sums in double from the first addition (norm.hip::groupnorm_bwd_sums_kernel's expressions)
+          const int c = l31 + 32 * j;
+          const float sc = p.gnb_table[((long)img * 2 + 0) * N + c], sh = p.gnb_table[((long)img * 2 + 1) * N + c];
+          const float mean = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2], rstd = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2 + 1];
+          const float* xb = xbase + 32 * j;
+          float xv[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) xv[r] = xb[off[r]];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const bool on = ((okm >> r) & 1u) && __builtin_fmaf(xv[r], sc, sh) > 0.f;
+            const float dm = on ? v[r] : 0.f;
+            ba[j] += (double)dm;
+            bb[j] += (double)dm * ((xv[r] - mean) * rstd);
+          }
+        }
+      }
+    }
+  }
+  if (p.gn_part) gn_tile_partials<TN>(p, gs, gq, red_s, tid, slot);   // (one barrier inside)
+  if (GNB && p.gnb_part) gnb_tile_partials<TN>(p, ba, bb, red_b, tid, slot, wave, l31, hi);
+}
 
 __global__ void gn_finalize_kernel(const double* __restrict__ part, int tiles, int G, double n, float eps, long count,
                                    float* __restrict__ stats) {
@@ -91,19 +262,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   __shared__ float xs[NPIX * XS];
   __shared__ __attribute__((aligned(16))) float ws[9 * SLAB * N];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-  int t = blockIdx.x;
-  const int txi = t % tiles_x;
-  t /= tiles_x;
-  const int tyi = t % tiles_y, img = t / tiles_y;
-  const int y0 = tyi * PH, x0 = txi * PW;
+  int img, y0, x0;
+  tile_origin(blockIdx.x, tiles_x, tiles_y, PH, img, y0, x0);
   const int Ct = p.C1 + p.C2, nslab = Ct / SLAB;
   const int nwp = 9 * N * 4;                       // weight pieces per slab
 
-  f32x16 acc[TN];
+  f32x16 acc[1][TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
 
   float4 rx[XP];
   float4 rw[(9 * N * 4 + 255) / 256];
@@ -112,30 +280,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   bool gnow = false;                                                                      // the staged slab is normalised
   auto gload = [&](int s) {
     const int c0 = s * SLAB;
-    const bool first = c0 < p.C1;
-    const float* base = first ? p.src1 + ((long)img * p.H) * p.W * p.ld1 + c0
-                              : p.src2 + ((long)(img / p.rep) * p.H) * p.W * p.ld2 + (c0 - p.C1);
-    const long ld = first ? p.ld1 : p.ld2;
-    gnow = p.gn_in != nullptr && first;
-    if (gnow) {   // (4 q = 4 (tid & 3): the quad is the same for all of a thread's pieces)
-      gsc = *reinterpret_cast<const float4*>(p.gn_in + ((long)img * 2 + 0) * p.C1 + c0 + 4 * (tid & 3));
-      gsh = *reinterpret_cast<const float4*>(p.gn_in + ((long)img * 2 + 1) * p.C1 + c0 + 4 * (tid & 3));
-    }
+    const float* base;
+    long ld;
+    gnow = slab_source(p, img, c0, base, ld) && p.gn_in != nullptr;
+    if (gnow) gn_quad(p, img, c0, tid, gsc, gsh);
     rxok = 0;
 #pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int f = tid + 256 * i;
-      const int pix = min(f >> 2, NPIX - 1), q = f & 3;
-      const int iy = pix / IW, ix = pix - iy * IW;
-      const int y = y0 - 1 + iy, x = x0 - 1 + ix;
-      const bool in = f < NPIX * 4 && y >= 0 && y < p.H && x >= 0 && x < p.W;
-      rxok |= in ? (1u << i) : 0u;
-      // UNCONDITIONAL load from a clamped pixel, masked when the piece is stored: a load under a per-lane condition
-      // becomes an exec-masked branch, and the s_waitcnt the compiler then needs before re-defining the destination
-      // registers at the next piece exposed the whole HBM latency of the prefetch once per slab (round 4 counters)
-      const int yc = min(max(y, 0), p.H - 1), xc = min(max(x, 0), p.W - 1);
-      rx[i] = *reinterpret_cast<const float4*>(base + ((long)yc * p.W + xc) * ld + 4 * q);
-    }
+    for (int i = 0; i < XP; ++i) rxok |= load_pixel_piece<NPIX>(base, ld, tid + 256 * i, y0, x0, p.H, p.W, rx[i]) ? (1u << i) : 0u;
 #pragma unroll
     for (int i = 0; i < (9 * N * 4 + 255) / 256; ++i) {
       const int f = min(tid + 256 * i, nwp - 1);    // co fastest: consecutive lanes -> consecutive LDS columns
@@ -149,8 +300,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
       const int f = tid + 256 * i;
       if (f < NPIX * 4) {
         float* d = xs + (f >> 2) * XS + 4 * (f & 3);
-        float4 v = ((rxok >> i) & 1u) ? rx[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gnow) v = gn_relu4(v, gsc, gsh, (rxok >> i) & 1u);   // zero padding stays zero: it pads y, not pre
+        const float4 v = operand4(rx[i], gnow, gsc, gsh, (rxok >> i) & 1u);
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
       }
     }
@@ -181,7 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
         const float a = xa[2 * ks];
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[2 * ks * N + 32 * j], acc[j], 0, 0, 0);
+          acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[2 * ks * N + 32 * j], acc[0][j], 0, 0, 0);
       }
     }
     __syncthreads();
@@ -190,72 +340,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
       __syncthreads();
     }
   }
-  // C layout: column = output channel (l31 + 32 j), row i = (r & 3) + 8 (r >> 2) + 4 hi = pixel (i >> 4, i & 15) of the wave
-  // Straight-line epilogue (see gemm_epilogue): uniform decisions once per 32-channel block, previous values (accumulate)
-  // read before the first store, one pointer per block plus per-register pixel offsets.
-  double gs[TN], gq[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) gs[j] = gq[j] = 0.0;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int co = l31 + 32 * j;
-    const float bv = p.bias ? p.bias[co] : 0.f;
-    float* ob = p.out + (long)img * p.H * p.W * p.ldo + co;
-    float v[16];
-    long off[16];
-    bool ok[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
-      const int y = y0 + wave * 2 + (i >> 4), x = x0 + (i & 15);
-      ok[r] = y < p.H && x < p.W;
-      off[r] = ((long)y * p.W + x) * p.ldo;
-      v[r] = acc[j][r] + bv;
-    }
-    if (p.gn_part) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const double t = ok[r] ? (double)v[r] : 0.0;
-        gs[j] += t;
-        gq[j] += t * t;
-      }
-    }
-    if (p.act == SVL_ACT_GELU) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = gelu_erf(v[r]);
-    } else if (p.act == SVL_ACT_RELU) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
-    }
-    if (p.accumulate) {
-      float prev[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) prev[r] = ok[r] ? ob[off[r]] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] += prev[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (ok[r]) ob[off[r]] = v[r];
-  }
-  if (p.gn_part) gn_tile_partials<TN>(p, gs, gq, reinterpret_cast<double*>(ws), tid, blockIdx.x);   // (the K loop ended with a barrier)
+  // (the K loop ended with a barrier: ws is free for the GroupNorm partials of the four waves)
+  tile_epilogue<TN, 1, false, false>(p, acc, img, y0, x0, 0, nullptr, reinterpret_cast<double*>(ws), nullptr, tid, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The same tiling with the bf16 split emulation of gemm.hip (svl_set_gemm_emulation(6): every fp32 value = 3 bf16 terms,
-// the 6 leading cross products on v_mfma_f32_32x32x16_bf16, fp32 accumulate -- error vs fp64 at or below the fp32 chain's).
+// conv3x3_tiled_h2_kernel<TN, PT> and conv3x3_tiled_bf16x_kernel<TN, PT>: the same tiling on the split-product pipe
+// (svl_set_gemm_emulation(6)) in the two operand formats of planes_split.h (NP = number of planes), one persistent pipeline.
+//
+// NP = 3, bf16 x 3 (the split emulation of gemm.hip: every fp32 value = 3 bf16 terms, the 6 leading cross products on
+// v_mfma_f32_32x32x16_bf16, fp32 accumulate -- error vs fp64 at or below the fp32 chain's).
 // A 16-channel slab is exactly one MFMA k-group: per tap a wave reads 3 A fragments (its 32 pixels, shifted by the tap) and
 // 3 TN B fragments (the tap's weights) and issues 6 TN MFMAs -- 54 TN per slab against 72 TN of the twice-as-long fp32
-// instruction.  Values are split ONCE when a slab is staged (the halo tile serves 9 taps, the weights 4 waves).
-// LDS rows are 32 B (16 bf16).  Weight rows: the two 16 B halves swapped on bit 3 of the row index -- the lane groups a
+// instruction.  Values are split ONCE when a slab is staged (the halo tile serves 9 taps, the weights 4 waves): the fp32
+// weights of p.w are split by every block.  Serves the launches WITHOUT a planes image.
+// LDS rows are 32 B (16 elements).  Weight rows: the two 16 B halves swapped on bit 3 of the row index -- the lane groups a
 // ds_read_b128 serves together ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of consecutive rows) then cover all 64 banks
-// once without padding; pixel rows: see XROW in the kernel.  The image is 17 + 55 KB (N = 64): two blocks per CU.
+// once without padding; pixel rows: see XROW in the kernel.  The image is 17 + 55 KB (N = 64, NP = 3): two blocks per CU.
 //
-// What bounds this kernel family (round-4 measurements: s_memtime phases with one and two blocks per CU, SQ counters).  A
-// wave issues in order, and a wave-level ds_read_b128 (1 KiB) costs it about as many cycles as an MFMA (32): alone on its
-// SIMD a wave runs the 108 MFMAs + 81 reads of a slab in 6192 cycles = 57 per MFMA = 32 (1 + 81 / 108) -- for a wave that
-// mixes the two, efficiency <= MFMAs / (MFMAs + reads): 9 reads / 12 MFMAs per tap here, 6 / 6 with one tile per wave (the
-// 119 - 133 TF of round 3), 12 / 24 for the 64 x 64 wave tiles of gemm_bf16x_kernel.  The second wave of the SIMD (the other
+// NP = 2 (round 6), fp16 x 2: THREE products per fp32 MAC instead of six, two planes instead of three in LDS (per tap 2 + 2 TN
+// fragment reads for 3 TN MFMAs where the bf16 x 3 form reads 3 + 3 TN for 6 TN).  fp16 has 5 exponent bits,
+// so every operand needs a power-of-two scale, and a convolution's sum runs over taps (pixels) and slabs (channels): everything
+// ONE accumulator adds up must share its scale.  The weights take one exponent per OUTPUT CHANNEL (a row scale of the B operand
+// factors out of the sum; svl_conv3x3_weight_planes writes them behind the planes image).  The pixel operand takes a RUNNING
+// exponent per tile, in the manner of an online softmax: the block finds the largest |value| of the slab it is about to stage
+// (after GroupNorm + ReLU when gn_in is set; a wave reduction + four floats exchanged at a barrier the loop has anyway), stages
+// it with max(exponent of that maximum, exponent the accumulators are at), and when the exponent rises the accumulators are
+// multiplied by the (exact) power of two <= 1 before the slab's MFMAs.  No maximum pass over the tensor, no exponents from the
+// producer; an element 2^-17 below the largest value its tile has seen so far keeps an absolute error of 2^-39 of that value.
+// Only with pre-split weights (ConvTiledP::w_planes): every block of a launch stages the same 9 x N x 16 weights per slab, so
+// splitting them in the kernel repeats ~8 VALU per element in every block: at N = 64 that is 9 of the 12 float4 pieces a
+// thread splits per slab, and the split instructions share the SIMD's issue slots with the 108 MFMAs of the slab (measured
+// round 4 on the bf16 x 3 form: 165 - 183 TF, the ratio MFMA / (MFMA + split) cycles predicts).  With the planes image
+// prepared once per weight version a slab's weights are 36 N 16-byte pieces copied global -> LDS verbatim.
+//
+// What bounds this kernel family (round-4 measurements on the bf16 x 3 form: s_memtime phases with one and two blocks per CU,
+// SQ counters).  A wave issues in order, and a wave-level ds_read_b128 (1 KiB) costs it about as many cycles as an MFMA (32):
+// alone on its SIMD a wave runs the 108 MFMAs + 81 reads of a slab in 6192 cycles = 57 per MFMA = 32 (1 + 81 / 108) -- for a
+// wave that mixes the two, efficiency <= MFMAs / (MFMAs + reads): 9 reads / 12 MFMAs per tap here, 6 / 6 with one tile per wave
+// (the 119 - 133 TF of round 3), 12 / 24 for the 64 x 64 wave tiles of gemm_bf16x_kernel.  The second wave of the SIMD (the other
 // block of the CU) fills the gaps only partly while it is itself a mix of reads and MFMAs: 38.5 cycles per MFMA when both
 // are in their MFMA phase, 52 - 59 % of the pipe over the whole kernel.  gemm_planes.hip shows what full overlap takes: the two
 // waves of a SIMD in STRICT alternation (one issues only MFMAs while the other only reads and copies, a barrier interval
@@ -264,7 +387,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
 // phase stretched by the same amount); only the conflict-free pixel rows moved it.  Next: either fewer reads per MFMA
 // (a 2 x 2 register tile needs 86 KB of LDS at N = 64: one block per CU) or the role split of gemm_planes.hip in one
 // 8-wave block per CU (two patches, shared weights: 90 KB).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+//
+// PT = 32-pixel tiles per wave: PT = 2 (a 16 x 16 patch per block) doubles the MFMA work per staged weight fragment and
+// per barrier -- used for N = 32, where one tile per wave left only 54 MFMAs between two barriers (119-133 TF vs 167-171
+// at N = 64).
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32q __attribute__((ext_vector_type(4)));
 
@@ -282,344 +408,24 @@ __device__ __forceinline__ void split3x4(const float4 v, bf16x4& h0, bf16x4& h1,
 }
 // element offset of channel quad q (channels 4q..4q+3) of row `row` inside a plane of 16-channel rows
 __device__ __forceinline__ int swz(int row, int q) { return row * 16 + ((((q >> 1) ^ (row >> 3)) & 1) << 3) + ((q & 1) << 2); }
+// element offset of staging piece f (load_pixel_piece) inside an x plane whose patch rows are XROW elements apart
+template <int XROW>
+__device__ __forceinline__ int xs_piece_off(int f) {
+  const int spx = f >> 2, siy = spx / IW;
+  return siy * XROW + (spx - siy * IW) * 16 + 4 * (f & 3);
+}
 
-// PT = 32-pixel tiles per wave: PT = 2 (a 16 x 16 patch per block) doubles the MFMA work per staged weight fragment and
-// per barrier -- used for N = 32, where one tile per wave left only 54 MFMAs between two barriers (119-133 TF vs 167-171
-// at N = 64).
-//
-// WPRE: the weights arrive pre-split (ConvTiledP::w_planes).  Every block of a launch stages the same 9 x N x 16 weights
-// per slab, so splitting them in the kernel repeats ~8 VALU per element in every block: at N = 64 that is 9 of the 12
-// float4 pieces a thread splits per slab, and the split instructions share the SIMD's issue slots with the 108 MFMAs of
-// the slab (measured round 4: 165 - 183 TF, the ratio MFMA / (MFMA + split) cycles predicts).  With the planes image
-// prepared once per weight version a slab's weights are 54 N 16-byte pieces copied global -> LDS verbatim.
 #ifdef SVL_CONV_PHASE_TIMING
 __device__ unsigned long long g_conv_phase[8];   // measurement build only (tools/conv_phases.py)
 #define SVL_PH(i) { const unsigned long long tn_ = __builtin_amdgcn_s_memtime(); ph[i] += tn_ - tl_; tl_ = tn_; }
 #else
 #define SVL_PH(i)
 #endif
-template <int TN, int PT, bool WPRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_tiled_bf16x_kernel(const ConvTiledP p, int tiles_x, int tiles_y) {
-  constexpr int N = 32 * TN;
-  constexpr int PHT = PH * PT, IHT = PHT + 2, NPX = IHT * IW;   // patch rows, halo rows, staged pixels
-  constexpr int XP = (NPX * 4 + 255) / 256;         // input float4 pieces per thread (3 / 6)
-  constexpr int WP = WPRE ? 1 : (9 * N * 4 + 255) / 256;   // weight float4 pieces per thread (5 / 9)
-  // x tile in LDS: 32-byte pixels, patch rows IW * 32 + 16 bytes apart and NO swizzle.  A ds_read_b128 serves lanes
-  // {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (and the same + 32) together -- 8 pixels of patch row r and the 8 OTHER
-  // columns of row r + 1: within a row the 8 pixels cover the 8 residues (mod 8) once = banks 8 k + [0, 4) for the lanes'
-  // 16-byte half, and the odd number of 16-byte units per row puts row r + 1 on banks 8 k + [4, 8): all 64 banks once,
-  // for every tap shift.  (The round-3 layout, rows 18 pixels apart with the halves swapped on bit 3 of the pixel index,
-  // was conflict-free for 16 CONSECUTIVE lanes only: 19 % of the LDS cycles of this kernel were conflict cycles.)
-  constexpr int XROW = IW * 16 + 8;                 // bf16 elements per staged patch row
-  constexpr int XPL = IHT * XROW, WPL = 9 * N * 16; // plane strides (bf16 elements)
-  constexpr int NWQ = 3 * WPL / 8;                  // 16-byte pieces of a slab's weight planes image (54 N)
-  constexpr int WQ = WPRE ? (NWQ + 255) / 256 : 1;  // of those per thread (7 / 14)
-  __shared__ __attribute__((aligned(16))) __bf16 xs[3 * XPL];
-  __shared__ __attribute__((aligned(16))) __bf16 ws[3 * WPL];
-  __shared__ double gred[4 * TN * 2 * 2];           // GroupNorm partials of the four waves (ws holds the NEXT tile's weights by then)
-  __shared__ double gbred[4][N][2];                 // GroupNorm-backward channel sums of the four waves (gnb_part)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-  // PERSISTENT blocks: a block walks tiles blockIdx.x, + gridDim.x, ... and the (tile, slab) pairs form ONE pipeline -- the
-  // first slab of the next tile is requested during the last MFMA phase of this one and the result stores drain under the
-  // next tile's work.  One tile per block cost 14 % (128 -> 64 channels) to 57 % (32 -> 32) of a block's cycles in the
-  // exposed first fetch and the store tail (s_memtime phases, round 4).
-  const int ntiles = p.imgs * tiles_x * tiles_y;
-  int tile = blockIdx.x;                             // the tile being computed
-  int img, y0, x0;                                   // ... and its image / origin
-  int limg, ly0, lx0;                                // the same of the tile whose slab is being STAGED
-  auto decode = [&](int t, int& im, int& yy, int& xx) __attribute__((always_inline)) {
-    const int txi = t % tiles_x;
-    t /= tiles_x;
-    const int tyi = t % tiles_y;
-    im = t / tiles_y;
-    yy = tyi * PHT; xx = txi * PW;
-  };
-  decode(tile, img, y0, x0);
-  limg = img; ly0 = y0; lx0 = x0;
-  const int Ct = p.C1 + p.C2, nslab = Ct / SLAB;
-  const int nwp = 9 * N * 4;
-
-  f32x16 acc[PT][TN];
-#pragma unroll
-  for (int u = 0; u < PT; ++u)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[u][j][r] = 0.f;
-
-  float4 rx[XP];
-  float4 rw[WP];
-  u32q rq[WQ];
-  float4 gsc = make_float4(1.f, 1.f, 1.f, 1.f), gsh = make_float4(0.f, 0.f, 0.f, 0.f);   // gn_in: this thread's channel quad
-  unsigned rxok = 0;                                                                      // in-image flags of rx[]
-  bool gnow = false;                                                                      // the staged slab is normalised
-  auto gload = [&](int s) __attribute__((always_inline)) {
-    const int c0 = s * SLAB;
-    const bool first = c0 < p.C1;
-    const float* base = first ? p.src1 + ((long)limg * p.H) * p.W * p.ld1 + c0
-                              : p.src2 + ((long)(limg / p.rep) * p.H) * p.W * p.ld2 + (c0 - p.C1);
-    const long ld = first ? p.ld1 : p.ld2;
-    gnow = p.gn_in != nullptr && first;
-    rxok = 0;
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int f = tid + 256 * i;
-      const int pix = min(f >> 2, NPX - 1), q = f & 3;
-      const int iy = pix / IW, ix = pix - iy * IW;
-      const int y = ly0 - 1 + iy, x = lx0 - 1 + ix;
-      const bool in = f < NPX * 4 && y >= 0 && y < p.H && x >= 0 && x < p.W;
-      rxok |= in ? (1u << i) : 0u;
-      const int yc = min(max(y, 0), p.H - 1), xc = min(max(x, 0), p.W - 1);   // (unconditional: see the fp32 kernel)
-      rx[i] = *reinterpret_cast<const float4*>(base + ((long)yc * p.W + xc) * ld + 4 * q);
-    }
-    if (WPRE) {
-      const u32q* wq = reinterpret_cast<const u32q*>(p.w_planes) + (long)s * NWQ;
-#pragma unroll
-      for (int i = 0; i < WQ; ++i) {
-        const int f = tid + 256 * i;
-        rq[i] = wq[f < NWQ ? f : NWQ - 1];         // (clamped, not conditional: the loads stay batched)
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < WP; ++i) {
-        const int f = min(tid + 256 * i, nwp - 1);   // quad fastest: 4 lanes cover the 64 contiguous bytes of one (co, tap)
-        const int q = f & 3, rest = f >> 2, co = rest % N, tap = rest / N;
-        rw[i] = *reinterpret_cast<const float4*>(p.w + (long)co * p.K + tap * Ct + c0 + 4 * q);
-      }
-    }
-    if (gnow) {   // (last: the wait that protects the table registers then sits behind the issue of the big loads)
-      gsc = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 0) * p.C1 + c0 + 4 * (tid & 3));
-      gsh = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 1) * p.C1 + c0 + 4 * (tid & 3));
-    }
-  };
-  auto sstore = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int f = tid + 256 * i;
-      if (f < NPX * 4) {
-        bf16x4 h0, h1, h2;
-        const unsigned in = (rxok >> i) & 1u;
-        split3x4(gnow ? gn_relu4(rx[i], gsc, gsh, in) : (in ? rx[i] : make_float4(0.f, 0.f, 0.f, 0.f)), h0, h1, h2);
-        const int spx = f >> 2, siy = spx / IW;
-        const int o = siy * XROW + (spx - siy * IW) * 16 + 4 * (f & 3);
-        *reinterpret_cast<bf16x4*>(xs + o) = h0;
-        *reinterpret_cast<bf16x4*>(xs + XPL + o) = h1;
-        *reinterpret_cast<bf16x4*>(xs + 2 * XPL + o) = h2;
-      }
-    }
-    if (WPRE) {
-#pragma unroll
-      for (int i = 0; i < WQ; ++i) {
-        const int f = tid + 256 * i;
-        if (f < NWQ) reinterpret_cast<u32q*>(ws)[f] = rq[i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < WP; ++i) {
-        const int f = tid + 256 * i;
-        if (f < nwp) {
-          const int q = f & 3, rest = f >> 2, co = rest % N, tap = rest / N;
-          bf16x4 h0, h1, h2;
-          split3x4(rw[i], h0, h1, h2);
-          const int o = swz(tap * N + co, q);        // (N is a multiple of 8: bit 3 of the row index is bit 3 of co)
-          *reinterpret_cast<bf16x4*>(ws + o) = h0;
-          *reinterpret_cast<bf16x4*>(ws + WPL + o) = h1;
-          *reinterpret_cast<bf16x4*>(ws + 2 * WPL + o) = h2;
-        }
-      }
-    }
-  };
-
-  const int pr = wave * 2 * PT + (l31 >> 4), pc = l31 & 15;   // this lane's A-operand pixel of its first tile
-#ifdef SVL_CONV_PHASE_TIMING
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = __builtin_amdgcn_s_memtime();
-#endif
-  gload(0);
-  sstore();
-  __syncthreads();
-  SVL_PH(0)
-  // The fragments of tap t + 1 are requested BEFORE the MFMAs of tap t and the two groups are fenced: left alone the
-  // scheduler sinks every ds_read to just above its first use (register pressure), and the wave sits in s_waitcnt for
-  // the LDS latency once per MFMA pair (round 4 counters: matrix pipe 52 % busy, a quarter of the wave cycles parked).
-  bf16x8 a[2][3][PT], b[2][3][TN];
-  auto lfrag = [&](int tap, int fb) __attribute__((always_inline)) {
-    const int dy = p.sign * (tap / 3 - 1), dx = p.sign * (tap % 3 - 1);
-#pragma unroll
-    for (int u = 0; u < PT; ++u) {
-      const int oa = (pr + 2 * u + 1 + dy) * XROW + (pc + 1 + dx) * 16 + 8 * hi;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) a[fb][pl][u] = *reinterpret_cast<const bf16x8*>(xs + pl * XPL + oa);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int rb = tap * N + 32 * j + l31;
-      const int ob = rb * 16 + (((hi ^ (rb >> 3)) & 1) << 3);
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) b[fb][pl][j] = *reinterpret_cast<const bf16x8*>(ws + pl * WPL + ob);
-    }
-  };
-  for (;;) {
-  for (int s = 0; s < nslab; ++s) {
-    // the next piece of the pipeline: this tile's next slab, or slab 0 of the block's next tile
-    const bool last = s + 1 == nslab;
-    const bool more = !last || tile + (int)gridDim.x < ntiles;
-    if (last && more) decode(tile + (int)gridDim.x, limg, ly0, lx0);
-    if (more) gload(last ? 0 : s + 1);
-    lfrag(0, 0);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int fb = tap & 1;
-      if (tap + 1 < 9) lfrag(tap + 1, fb ^ 1);
-      __builtin_amdgcn_sched_barrier(0);
-      // smallest cross terms first: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-#define SVL_CT(PA, PB)                                                                     \
-  _Pragma("unroll") for (int u = 0; u < PT; ++u) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[u][j] = \
-      __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[fb][PA][u], b[fb][PB][j], acc[u][j], 0, 0, 0);
-      SVL_CT(2, 0)
-      SVL_CT(0, 2)
-      SVL_CT(1, 1)
-      SVL_CT(1, 0)
-      SVL_CT(0, 1)
-      SVL_CT(0, 0)
-#undef SVL_CT
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    SVL_PH(1)
-    __syncthreads();
-    SVL_PH(2)
-    if (more) sstore();
-    SVL_PH(3)
-    if (!last) {
-      __syncthreads();
-      SVL_PH(4)
-    }
-  }
-  // epilogue of the tile (its stores drain under the next tile's first MFMA phase): the fp32 kernel's (column = output
-  // channel, row = pixel of the wave), with the pixel offsets formed once per pixel tile in 32 bits -- the epilogue's VALU
-  // instructions wait for gaps in the other block's MFMA stream like every VALU instruction of a staging phase
-  double gs[TN], gq[TN], ba[TN], bb[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) gs[j] = gq[j] = ba[j] = bb[j] = 0.0;
-  {
-    float* obase = p.out + (long)img * p.H * p.W * p.ldo + l31;
-    const float* xbase = p.gnb_x ? p.gnb_x + (long)img * p.H * p.W * p.ldo + l31 : nullptr;
-    const int ldo = (int)p.ldo;
-#pragma unroll
-    for (int u = 0; u < PT; ++u) {
-      int off[16];
-      unsigned okm = 0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const int y = y0 + wave * 2 * PT + 2 * u + (i >> 4), x = x0 + (i & 15);
-        okm |= (y < p.H && x < p.W) ? (1u << r) : 0u;
-        off[r] = (min(y, p.H - 1) * p.W + min(x, p.W - 1)) * ldo;
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const float bv = p.bias ? p.bias[l31 + 32 * j] : 0.f;
-        float* ob = obase + 32 * j;
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          v[r] = acc[u][j][r] + bv;
-          acc[u][j][r] = 0.f;
-        }
-        if (p.gn_part) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const double t = ((okm >> r) & 1u) ? (double)v[r] : 0.0;
-            gs[j] += t;
-            gq[j] += t * t;
-          }
-        }
-        if (p.act == SVL_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == SVL_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
-        }
-        if (p.accumulate) {
-          float prev[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) prev[r] = ob[off[r]];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] += prev[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if ((okm >> r) & 1u) ob[off[r]] = v[r];
-        if (p.gnb_part) {
-          // this lane's channel c = l31 + 32 j of the GroupNorm whose dy was just written: mask from the forward's own fma,
-          // sums in double from the first addition (norm.hip::groupnorm_bwd_sums_kernel's expressions)
-          const int c = l31 + 32 * j;
-          const float sc = p.gnb_table[((long)img * 2 + 0) * N + c], sh = p.gnb_table[((long)img * 2 + 1) * N + c];
-          const float mean = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2], rstd = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2 + 1];
-          const float* xb = xbase + 32 * j;
-          float xv[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) xv[r] = xb[off[r]];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const bool on = ((okm >> r) & 1u) && __builtin_fmaf(xv[r], sc, sh) > 0.f;
-            const float dm = on ? v[r] : 0.f;
-            ba[j] += (double)dm;
-            bb[j] += (double)dm * ((xv[r] - mean) * rstd);
-          }
-        }
-      }
-    }
-  }
-  if (p.gn_part) gn_tile_partials<TN>(p, gs, gq, gred, tid, tile);   // (one barrier inside; gred is not touched by the staging)
-  if (p.gnb_part) {       // lanes hi = 0 / 1 hold different pixel rows of the same channel; then the four waves, fixed order
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const double a2 = ba[j] + __shfl_xor(ba[j], 32, 64), b2 = bb[j] + __shfl_xor(bb[j], 32, 64);
-      if (hi == 0) {
-        gbred[wave][l31 + 32 * j][0] = a2;
-        gbred[wave][l31 + 32 * j][1] = b2;
-      }
-    }
-    __syncthreads();
-    if (tid < N) {
-      double* o = p.gnb_part + ((long)tile * N + tid) * 2;
-      o[0] = (gbred[0][tid][0] + gbred[1][tid][0]) + (gbred[2][tid][0] + gbred[3][tid][0]);
-      o[1] = (gbred[0][tid][1] + gbred[1][tid][1]) + (gbred[2][tid][1] + gbred[3][tid][1]);
-    }
-  }
-  SVL_PH(5)
-  tile += (int)gridDim.x;
-  if (tile >= ntiles) break;
-  img = limg; y0 = ly0; x0 = lx0;
-  __syncthreads();                                   // the staged slab 0 of the next tile is complete
-  }
-#ifdef SVL_CONV_PHASE_TIMING
-  if (tid == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) atomicAdd(&g_conv_phase[i], ph[i]);
-    atomicAdd(&g_conv_phase[7], 1ull);
-  }
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Round 6: the same kernel on fp16 x 2 terms -- THREE products per fp32 MAC instead of six, two planes instead of three in LDS
-// (per tap 2 + 2 TN fragment reads for 3 TN MFMAs where the bf16 x 3 form reads 3 + 3 TN for 6 TN).  fp16 has 5 exponent bits,
-// so every operand needs a power-of-two scale, and a convolution's sum runs over taps (pixels) and slabs (channels): everything
-// ONE accumulator adds up must share its scale.  The weights take one exponent per OUTPUT CHANNEL (a row scale of the B operand
-// factors out of the sum; svl_conv3x3_weight_planes writes them behind the planes image).  The pixel operand takes a RUNNING
-// exponent per tile, in the manner of an online softmax: the block finds the largest |value| of the slab it is about to stage
-// (after GroupNorm + ReLU when gn_in is set; a wave reduction + four floats exchanged at a barrier the loop has anyway), stages
-// it with max(exponent of that maximum, exponent the accumulators are at), and when the exponent rises the accumulators are
-// multiplied by the (exact) power of two <= 1 before the slab's MFMAs.  No maximum pass over the tensor, no exponents from the
-// producer; an element 2^-17 below the largest value its tile has seen so far keeps an absolute error of 2^-39 of that value.
-// Only with pre-split weights (w_planes); without them the bf16 x 3 kernel above serves the launch.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 template <int TN, int PT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_tiled_h2_kernel(const ConvTiledP p, int tiles_x, int tiles_y) {
+  typedef _Float16 elem;
+  typedef f16x8 frag;
+  constexpr int NP = 2;                             // planes
   constexpr int N = 32 * TN;
   constexpr int PHT = PH * PT, IHT = PHT + 2, NPX = IHT * IW;   // patch rows, halo rows, staged pixels
   constexpr int XP = (NPX * 4 + 255) / 256;         // input float4 pieces per thread (3 / 6)
@@ -631,10 +437,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // was conflict-free for 16 CONSECUTIVE lanes only: 19 % of the LDS cycles of this kernel were conflict cycles.)
   constexpr int XROW = IW * 16 + 8;                 // 16-bit elements per staged patch row
   constexpr int XPL = IHT * XROW, WPL = 9 * N * 16; // plane strides (16-bit elements)
-  constexpr int NWQ = 2 * WPL / 8;                  // 16-byte pieces of a slab's weight planes image (36 N)
-  constexpr int WQ = (NWQ + 255) / 256;             // of those per thread (5 / 9)
-  __shared__ __attribute__((aligned(16))) _Float16 xs[2 * XPL];
-  __shared__ __attribute__((aligned(16))) _Float16 ws[2 * WPL];
+  constexpr int NWP = NP * WPL / 8;                 // 16-byte pieces of a slab's weight planes image (36 N); per thread 5 / 9
+  constexpr int WP = (NWP + 255) / 256;
+  __shared__ __attribute__((aligned(16))) elem xs[NP * XPL];
+  __shared__ __attribute__((aligned(16))) elem ws[NP * WPL];
   __shared__ float smax[4];                         // per-wave maxima of the slab being staged (exchanged at the loop's first barrier)
   __shared__ double gred[4 * TN * 2 * 2];           // GroupNorm partials of the four waves (ws holds the NEXT tile's weights by then)
   __shared__ double gbred[4][N][2];                 // GroupNorm-backward channel sums of the four waves (gnb_part)
@@ -647,18 +453,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int tile = blockIdx.x;                             // the tile being computed
   int img, y0, x0;                                   // ... and its image / origin
   int limg, ly0, lx0;                                // the same of the tile whose slab is being STAGED
-  auto decode = [&](int t, int& im, int& yy, int& xx) __attribute__((always_inline)) {
-    const int txi = t % tiles_x;
-    t /= tiles_x;
-    const int tyi = t % tiles_y;
-    im = t / tiles_y;
-    yy = tyi * PHT; xx = txi * PW;
-  };
-  decode(tile, img, y0, x0);
+  tile_origin(tile, tiles_x, tiles_y, PHT, img, y0, x0);
   limg = img; ly0 = y0; lx0 = x0;
-  // per-output-channel exponents of the weight planes (behind the planes image: svl_conv3x3_weight_planes)
-  const int* wexp = reinterpret_cast<const int*>(reinterpret_cast<const char*>(p.w_planes) + (long)((p.C1 + p.C2) / SLAB) * NWQ * 16);
   const int Ct = p.C1 + p.C2, nslab = Ct / SLAB;
+  // per-output-channel exponents of the weight planes (behind the planes image: svl_conv3x3_weight_planes)
+  const int* wexp = reinterpret_cast<const int*>(reinterpret_cast<const char*>(p.w_planes) + (long)nslab * NWP * 16);
 
   f32x16 acc[PT][TN];
 #pragma unroll
@@ -669,86 +468,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int r = 0; r < 16; ++r) acc[u][j][r] = 0.f;
 
   float4 rx[XP];
-  u32q rq[WQ];
+  u32q rw[WP];
   float4 gsc = make_float4(1.f, 1.f, 1.f, 1.f), gsh = make_float4(0.f, 0.f, 0.f, 0.f);   // gn_in: this thread's channel quad
   unsigned rxok = 0;                                                                      // in-image flags of rx[]
   bool gnow = false;                                                                      // the staged slab is normalised
   auto gload = [&](int s) __attribute__((always_inline)) {
     const int c0 = s * SLAB;
-    const bool first = c0 < p.C1;
-    const float* base = first ? p.src1 + ((long)limg * p.H) * p.W * p.ld1 + c0
-                              : p.src2 + ((long)(limg / p.rep) * p.H) * p.W * p.ld2 + (c0 - p.C1);
-    const long ld = first ? p.ld1 : p.ld2;
-    gnow = p.gn_in != nullptr && first;
+    const float* base;
+    long ld;
+    gnow = slab_source(p, limg, c0, base, ld) && p.gn_in != nullptr;
     rxok = 0;
 #pragma unroll
-    for (int i = 0; i < XP; ++i) {
-      const int f = tid + 256 * i;
-      const int pix = min(f >> 2, NPX - 1), q = f & 3;
-      const int iy = pix / IW, ix = pix - iy * IW;
-      const int y = ly0 - 1 + iy, x = lx0 - 1 + ix;
-      const bool in = f < NPX * 4 && y >= 0 && y < p.H && x >= 0 && x < p.W;
-      rxok |= in ? (1u << i) : 0u;
-      const int yc = min(max(y, 0), p.H - 1), xc = min(max(x, 0), p.W - 1);   // (unconditional: see the fp32 kernel)
-      rx[i] = *reinterpret_cast<const float4*>(base + ((long)yc * p.W + xc) * ld + 4 * q);
-    }
-    {
-      const u32q* wq = reinterpret_cast<const u32q*>(p.w_planes) + (long)s * NWQ;
+    for (int i = 0; i < XP; ++i) rxok |= load_pixel_piece<NPX>(base, ld, tid + 256 * i, ly0, lx0, p.H, p.W, rx[i]) ? (1u << i) : 0u;
+    const u32q* wq = reinterpret_cast<const u32q*>(p.w_planes) + (long)s * NWP;
 #pragma unroll
-      for (int i = 0; i < WQ; ++i) {
-        const int f = tid + 256 * i;
-        rq[i] = wq[f < NWQ ? f : NWQ - 1];         // (clamped, not conditional: the loads stay batched)
-      }
+    for (int i = 0; i < WP; ++i) {
+      const int f = tid + 256 * i;
+      rw[i] = wq[f < NWP ? f : NWP - 1];           // (clamped, not conditional: the loads stay batched)
     }
-    if (gnow) {   // (last: the wait that protects the table registers then sits behind the issue of the big loads)
-      gsc = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 0) * p.C1 + c0 + 4 * (tid & 3));
-      gsh = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 1) * p.C1 + c0 + 4 * (tid & 3));
-    }
+    if (gnow) gn_quad(p, limg, c0, tid, gsc, gsh);   // (last: the wait that protects the table registers then sits behind the issue of the big loads)
   };
-  // The loaded pieces become the OPERAND values (GroupNorm + ReLU applied, out-of-image pixels zero) in place; returns this
-  // thread's largest |value|: the slab's scale exponent is the block-wide maximum's (exchanged through smax at a barrier the
-  // loop has anyway).
+  // The loaded pieces become the OPERAND values in place and this wave's largest |value| goes to smax: the slab's scale
+  // exponent is the block-wide maximum's (exchanged through smax at a barrier the loop has anyway).
   auto xform = [&]() __attribute__((always_inline)) {
     float m = 0.f;
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
-      const unsigned in = (rxok >> i) & 1u;
-      rx[i] = gnow ? gn_relu4(rx[i], gsc, gsh, in) : (in ? rx[i] : make_float4(0.f, 0.f, 0.f, 0.f));
-      if (tid + 256 * i < NPX * 4)
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(rx[i].x), fabsf(rx[i].y)), fmaxf(fabsf(rx[i].z), fabsf(rx[i].w))));
+      rx[i] = operand4(rx[i], gnow, gsc, gsh, (rxok >> i) & 1u);
+      if (tid + 256 * i < NPX * 4) m = fmaxf(m, absmax4(rx[i]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) smax[wave] = m;
+    wave_max_to(m, smax, lane, wave);
   };
-  auto exp_of = [](float mx) {      // mx 2^-e in [2^14, 2^15)  (fp16 overflows at 65504); an all-zero slab takes the floor
-    const int e = mx > 0.f ? __builtin_amdgcn_frexp_expf(mx) - 15 : -100;
-    return e < -100 ? -100 : (e > 100 ? 100 : e);
-  };
-  // x 2^-e = h0 + h1, two round-to-nearest fp16 terms (23 significand bits for every element within 2^-17 of the slab maximum)
+  // The staged slab -> LDS: x 2^-e = h0 + h1 (split2x4) of the values xform left, the weight pieces copied
   auto sstore = [&](int e) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < XP; ++i) {
       const int f = tid + 256 * i;
       if (f < NPX * 4) {
-        const float v[4] = {__builtin_amdgcn_ldexpf(rx[i].x, -e), __builtin_amdgcn_ldexpf(rx[i].y, -e),
-                            __builtin_amdgcn_ldexpf(rx[i].z, -e), __builtin_amdgcn_ldexpf(rx[i].w, -e)};
+        const int o = xs_piece_off<XROW>(f);
         f16x4 h0, h1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          h0[j] = (_Float16)v[j];
-          h1[j] = (_Float16)(v[j] - (float)h0[j]);
-        }
-        const int spx = f >> 2, siy = spx / IW;
-        const int o = siy * XROW + (spx - siy * IW) * 16 + 4 * (f & 3);
+        split2x4(rx[i], e, h0, h1);
         *reinterpret_cast<f16x4*>(xs + o) = h0;
         *reinterpret_cast<f16x4*>(xs + XPL + o) = h1;
       }
     }
 #pragma unroll
-    for (int i = 0; i < WQ; ++i) {
+    for (int i = 0; i < WP; ++i) {
       const int f = tid + 256 * i;
-      if (f < NWQ) reinterpret_cast<u32q*>(ws)[f] = rq[i];
+      if (f < NWP) reinterpret_cast<u32q*>(ws)[f] = rw[i];
     }
   };
 
@@ -756,37 +523,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #ifdef SVL_CONV_PHASE_TIMING
   unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = __builtin_amdgcn_s_memtime();
 #endif
-  // Scale bookkeeping (every thread holds the same values): e_st = exponent the STAGED slab was scaled with, e_acc = exponent of
-  // the accumulators.  A slab is staged with max(e_acc, its own exponent) -- never below what the tile has accumulated at, so
-  // the only rescale ever needed is acc *= 2^(e_acc - e_st) <= 1 (exact); a later slab of smaller magnitude keeps an ABSOLUTE
-  // error of 2^-39 of the running maximum, far below the fp32 accumulation noise.  The first slab of a tile starts afresh.
+  // Scale bookkeeping (every thread holds the same values): e_st = exponent the STAGED slab was scaled with, e_acc =
+  // exponent of the accumulators.  A slab is staged with max(e_acc, its own exponent) -- never below what the tile has accumulated
+  // at, so the only rescale ever needed is acc *= 2^(e_acc - e_st) <= 1 (exact); a later slab of smaller magnitude keeps an
+  // ABSOLUTE error of 2^-39 of the running maximum, far below the fp32 accumulation noise.  The first slab of a tile starts afresh.
   int e_st, e_acc = 0;
   bool fresh = true;                                  // the staged slab is the first of its tile
   gload(0);
   xform();
   __syncthreads();
-  e_st = exp_of(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
+  e_st = slab_exp_of(block_max4(smax));
   sstore(e_st);
   __syncthreads();
   SVL_PH(0)
   // The fragments of tap t + 1 are requested BEFORE the MFMAs of tap t and the two groups are fenced: left alone the
   // scheduler sinks every ds_read to just above its first use (register pressure), and the wave sits in s_waitcnt for
   // the LDS latency once per MFMA pair (round 4 counters: matrix pipe 52 % busy, a quarter of the wave cycles parked).
-  f16x8 a[2][2][PT], b[2][2][TN];
+  frag a[2][NP][PT], b[2][NP][TN];
   auto lfrag = [&](int tap, int fb) __attribute__((always_inline)) {
     const int dy = p.sign * (tap / 3 - 1), dx = p.sign * (tap % 3 - 1);
 #pragma unroll
     for (int u = 0; u < PT; ++u) {
       const int oa = (pr + 2 * u + 1 + dy) * XROW + (pc + 1 + dx) * 16 + 8 * hi;
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) a[fb][pl][u] = *reinterpret_cast<const f16x8*>(xs + pl * XPL + oa);
+      for (int pl = 0; pl < NP; ++pl) a[fb][pl][u] = *reinterpret_cast<const frag*>(xs + pl * XPL + oa);
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int rb = tap * N + 32 * j + l31;
       const int ob = rb * 16 + (((hi ^ (rb >> 3)) & 1) << 3);
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) b[fb][pl][j] = *reinterpret_cast<const f16x8*>(ws + pl * WPL + ob);
+      for (int pl = 0; pl < NP; ++pl) b[fb][pl][j] = *reinterpret_cast<const frag*>(ws + pl * WPL + ob);
     }
   };
   for (;;) {
@@ -794,7 +561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // the next piece of the pipeline: this tile's next slab, or slab 0 of the block's next tile
     const bool last = s + 1 == nslab;
     const bool more = !last || tile + (int)gridDim.x < ntiles;
-    if (last && more) decode(tile + (int)gridDim.x, limg, ly0, lx0);
+    if (last && more) tile_origin(tile + (int)gridDim.x, tiles_x, tiles_y, PHT, limg, ly0, lx0);
     if (more) gload(last ? 0 : s + 1);
     // the staged slab joins the accumulators at e_st
     if (fresh) e_acc = e_st;
@@ -829,7 +596,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();
     SVL_PH(2)
     if (more) {
-      const int e_own = exp_of(fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])));
+      const int e_own = slab_exp_of(block_max4(smax));
       fresh = last;                                  // slab 0 of the block's next tile
       e_st = fresh ? e_own : (e_own > e_acc ? e_own : e_acc);
       sstore(e_st);
@@ -840,101 +607,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       SVL_PH(4)
     }
   }
-  // epilogue of the tile (its stores drain under the next tile's first MFMA phase): the fp32 kernel's (column = output
-  // channel, row = pixel of the wave), with the pixel offsets formed once per pixel tile in 32 bits -- the epilogue's VALU
-  // instructions wait for gaps in the other block's MFMA stream like every VALU instruction of a staging phase
-  double gs[TN], gq[TN], ba[TN], bb[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) gs[j] = gq[j] = ba[j] = bb[j] = 0.0;
-  {
-    float* obase = p.out + (long)img * p.H * p.W * p.ldo + l31;
-    const float* xbase = p.gnb_x ? p.gnb_x + (long)img * p.H * p.W * p.ldo + l31 : nullptr;
-    const int ldo = (int)p.ldo;
-#pragma unroll
-    for (int u = 0; u < PT; ++u) {
-      int off[16];
-      unsigned okm = 0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const int y = y0 + wave * 2 * PT + 2 * u + (i >> 4), x = x0 + (i & 15);
-        okm |= (y < p.H && x < p.W) ? (1u << r) : 0u;
-        off[r] = (min(y, p.H - 1) * p.W + min(x, p.W - 1)) * ldo;
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const float bv = p.bias ? p.bias[l31 + 32 * j] : 0.f;
-        const int es = e_acc + wexp[l31 + 32 * j];     // undo the slab scale and this output channel's weight scale (exact)
-        float* ob = obase + 32 * j;
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          v[r] = __builtin_amdgcn_ldexpf(acc[u][j][r], es) + bv;
-          acc[u][j][r] = 0.f;
-        }
-        if (p.gn_part) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const double t = ((okm >> r) & 1u) ? (double)v[r] : 0.0;
-            gs[j] += t;
-            gq[j] += t * t;
-          }
-        }
-        if (p.act == SVL_ACT_GELU) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = gelu_erf(v[r]);
-        } else if (p.act == SVL_ACT_RELU) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.f);
-        }
-        if (p.accumulate) {
-          float prev[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) prev[r] = ob[off[r]];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] += prev[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if ((okm >> r) & 1u) ob[off[r]] = v[r];
-        if (p.gnb_part) {
-          // this lane's channel c = l31 + 32 j of the GroupNorm whose dy was just written: mask from the forward's own fma,
-          // sums in double from the first addition (norm.hip::groupnorm_bwd_sums_kernel's expressions)
-          const int c = l31 + 32 * j;
-          const float sc = p.gnb_table[((long)img * 2 + 0) * N + c], sh = p.gnb_table[((long)img * 2 + 1) * N + c];
-          const float mean = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2], rstd = p.gnb_stats[((long)img * (N / 16) + (c >> 4)) * 2 + 1];
-          const float* xb = xbase + 32 * j;
-          float xv[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) xv[r] = xb[off[r]];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const bool on = ((okm >> r) & 1u) && __builtin_fmaf(xv[r], sc, sh) > 0.f;
-            const float dm = on ? v[r] : 0.f;
-            ba[j] += (double)dm;
-            bb[j] += (double)dm * ((xv[r] - mean) * rstd);
-          }
-        }
-      }
-    }
-  }
-  if (p.gn_part) gn_tile_partials<TN>(p, gs, gq, gred, tid, tile);   // (one barrier inside; gred is not touched by the staging)
-  if (p.gnb_part) {       // lanes hi = 0 / 1 hold different pixel rows of the same channel; then the four waves, fixed order
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const double a2 = ba[j] + __shfl_xor(ba[j], 32, 64), b2 = bb[j] + __shfl_xor(bb[j], 32, 64);
-      if (hi == 0) {
-        gbred[wave][l31 + 32 * j][0] = a2;
-        gbred[wave][l31 + 32 * j][1] = b2;
-      }
-    }
-    __syncthreads();
-    if (tid < N) {
-      double* o = p.gnb_part + ((long)tile * N + tid) * 2;
-      o[0] = (gbred[0][tid][0] + gbred[1][tid][0]) + (gbred[2][tid][0] + gbred[3][tid][0]);
-      o[1] = (gbred[0][tid][1] + gbred[1][tid][1]) + (gbred[2][tid][1] + gbred[3][tid][1]);
-    }
-  }
+  tile_epilogue<TN, PT, true, true>(p, acc, img, y0, x0, e_acc, wexp, gred, gbred, tid, tile);   // (gred / gbred are not touched by the staging)
   SVL_PH(5)
   tile += (int)gridDim.x;
   if (tile >= ntiles) break;
@@ -950,19 +623,198 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #endif
 }
 
-// The weight planes image of conv3x3_tiled_h2_kernel: per output channel co one scale exponent e[co] (largest |w| of its 9 Ct
-// weights 2^-e in [2^14, 2^15)), and for slab s (16 input channels) the two fp16 planes [pl][tap * N + co][16 channels, halves
-// swapped by swz] of w 2^-e[co] exactly as the kernel lays a slab's weights out in LDS; the exponents follow the planes.
+// The bf16 x 3 form keeps a body of its OWN for the staging and store steps (pixel loads, operand value and xs offset written
+// out as below), on tile_origin, gn_relu4, split3x4, swz and tile_epilogue: through slab_source / load_pixel_piece / gn_quad the
+// N = 32 instantiation on 16 x 16 patches read twice as many scalars back from vector lanes, through operand4 / xs_piece_off the
+// compiler kept one copy fewer of the split-and-store code around the persistent loop, and that launch measured 2.2 - 3.6 %
+// slower than before in all of eight alternations (profiles/conv_tiled_refactor.md).  The loop is conv3x3_tiled_h2_kernel's.
+template <int TN, int PT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_tiled_bf16x_kernel(const ConvTiledP p, int tiles_x, int tiles_y) {
+  constexpr int N = 32 * TN;
+  constexpr int PHT = PH * PT, IHT = PHT + 2, NPX = IHT * IW;   // patch rows, halo rows, staged pixels
+  constexpr int XP = (NPX * 4 + 255) / 256;         // input float4 pieces per thread (3 / 6)
+  constexpr int WP = (9 * N * 4 + 255) / 256;       // weight float4 pieces per thread (5 / 9)
+  // (x tile in LDS, persistent blocks, fragment prefetch: the commentary is in conv3x3_tiled_h2_kernel, the same pipeline)
+  constexpr int XROW = IW * 16 + 8;                 // bf16 elements per staged patch row
+  constexpr int XPL = IHT * XROW, WPL = 9 * N * 16; // plane strides (bf16 elements)
+  __shared__ __attribute__((aligned(16))) __bf16 xs[3 * XPL];
+  __shared__ __attribute__((aligned(16))) __bf16 ws[3 * WPL];
+  __shared__ double gred[4 * TN * 2 * 2];           // GroupNorm partials of the four waves (ws holds the NEXT tile's weights by then)
+  __shared__ double gbred[4][N][2];                 // GroupNorm-backward channel sums of the four waves (gnb_part)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
+  const int ntiles = p.imgs * tiles_x * tiles_y;
+  int tile = blockIdx.x;                             // the tile being computed
+  int img, y0, x0;                                   // ... and its image / origin
+  int limg, ly0, lx0;                                // the same of the tile whose slab is being STAGED
+  tile_origin(tile, tiles_x, tiles_y, PHT, img, y0, x0);
+  limg = img; ly0 = y0; lx0 = x0;
+  const int Ct = p.C1 + p.C2, nslab = Ct / SLAB;
+  const int nwp = 9 * N * 4;
+
+  f32x16 acc[PT][TN];
+#pragma unroll
+  for (int u = 0; u < PT; ++u)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[u][j][r] = 0.f;
+
+  float4 rx[XP];
+  float4 rw[WP];
+  float4 gsc = make_float4(1.f, 1.f, 1.f, 1.f), gsh = make_float4(0.f, 0.f, 0.f, 0.f);   // gn_in: this thread's channel quad
+  unsigned rxok = 0;                                                                      // in-image flags of rx[]
+  bool gnow = false;                                                                      // the staged slab is normalised
+  auto gload = [&](int s) __attribute__((always_inline)) {
+    const int c0 = s * SLAB;
+    const bool first = c0 < p.C1;
+    const float* base = first ? p.src1 + ((long)limg * p.H) * p.W * p.ld1 + c0
+                              : p.src2 + ((long)(limg / p.rep) * p.H) * p.W * p.ld2 + (c0 - p.C1);
+    const long ld = first ? p.ld1 : p.ld2;
+    gnow = p.gn_in != nullptr && first;
+    rxok = 0;
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+      const int f = tid + 256 * i;
+      const int pix = min(f >> 2, NPX - 1), q = f & 3;
+      const int iy = pix / IW, ix = pix - iy * IW;
+      const int y = ly0 - 1 + iy, x = lx0 - 1 + ix;
+      const bool in = f < NPX * 4 && y >= 0 && y < p.H && x >= 0 && x < p.W;
+      rxok |= in ? (1u << i) : 0u;
+      const int yc = min(max(y, 0), p.H - 1), xc = min(max(x, 0), p.W - 1);   // (unconditional: see the fp32 kernel)
+      rx[i] = *reinterpret_cast<const float4*>(base + ((long)yc * p.W + xc) * ld + 4 * q);
+    }
+#pragma unroll
+    for (int i = 0; i < WP; ++i) {
+      const int f = min(tid + 256 * i, nwp - 1);   // quad fastest: 4 lanes cover the 64 contiguous bytes of one (co, tap)
+      const int q = f & 3, rest = f >> 2, co = rest % N, tap = rest / N;
+      rw[i] = *reinterpret_cast<const float4*>(p.w + (long)co * p.K + tap * Ct + c0 + 4 * q);
+    }
+    if (gnow) {   // (last: the wait that protects the table registers then sits behind the issue of the big loads)
+      gsc = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 0) * p.C1 + c0 + 4 * (tid & 3));
+      gsh = *reinterpret_cast<const float4*>(p.gn_in + ((long)limg * 2 + 1) * p.C1 + c0 + 4 * (tid & 3));
+    }
+  };
+  auto sstore = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < XP; ++i) {
+      const int f = tid + 256 * i;
+      if (f < NPX * 4) {
+        bf16x4 h0, h1, h2;
+        const unsigned in = (rxok >> i) & 1u;
+        split3x4(gnow ? gn_relu4(rx[i], gsc, gsh, in) : (in ? rx[i] : make_float4(0.f, 0.f, 0.f, 0.f)), h0, h1, h2);
+        const int spx = f >> 2, siy = spx / IW;
+        const int o = siy * XROW + (spx - siy * IW) * 16 + 4 * (f & 3);
+        *reinterpret_cast<bf16x4*>(xs + o) = h0;
+        *reinterpret_cast<bf16x4*>(xs + XPL + o) = h1;
+        *reinterpret_cast<bf16x4*>(xs + 2 * XPL + o) = h2;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < WP; ++i) {
+      const int f = tid + 256 * i;
+      if (f < nwp) {
+        const int q = f & 3, rest = f >> 2, co = rest % N, tap = rest / N;
+        bf16x4 h0, h1, h2;
+        split3x4(rw[i], h0, h1, h2);
+        const int o = swz(tap * N + co, q);        // (N is a multiple of 8: bit 3 of the row index is bit 3 of co)
+        *reinterpret_cast<bf16x4*>(ws + o) = h0;
+        *reinterpret_cast<bf16x4*>(ws + WPL + o) = h1;
+        *reinterpret_cast<bf16x4*>(ws + 2 * WPL + o) = h2;
+      }
+    }
+  };
+
+  const int pr = wave * 2 * PT + (l31 >> 4), pc = l31 & 15;   // this lane's A-operand pixel of its first tile
+#ifdef SVL_CONV_PHASE_TIMING
+  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = __builtin_amdgcn_s_memtime();
+#endif
+  gload(0);
+  sstore();
+  __syncthreads();
+  SVL_PH(0)
+  bf16x8 a[2][3][PT], b[2][3][TN];
+  auto lfrag = [&](int tap, int fb) __attribute__((always_inline)) {
+    const int dy = p.sign * (tap / 3 - 1), dx = p.sign * (tap % 3 - 1);
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+      const int oa = (pr + 2 * u + 1 + dy) * XROW + (pc + 1 + dx) * 16 + 8 * hi;
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) a[fb][pl][u] = *reinterpret_cast<const bf16x8*>(xs + pl * XPL + oa);
+    }
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int rb = tap * N + 32 * j + l31;
+      const int ob = rb * 16 + (((hi ^ (rb >> 3)) & 1) << 3);
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) b[fb][pl][j] = *reinterpret_cast<const bf16x8*>(ws + pl * WPL + ob);
+    }
+  };
+  for (;;) {
+  for (int s = 0; s < nslab; ++s) {
+    // the next piece of the pipeline: this tile's next slab, or slab 0 of the block's next tile
+    const bool last = s + 1 == nslab;
+    const bool more = !last || tile + (int)gridDim.x < ntiles;
+    if (last && more) tile_origin(tile + (int)gridDim.x, tiles_x, tiles_y, PHT, limg, ly0, lx0);
+    if (more) gload(last ? 0 : s + 1);
+    lfrag(0, 0);
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int fb = tap & 1;
+      if (tap + 1 < 9) lfrag(tap + 1, fb ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      // smallest cross terms first: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
+#define SVL_CT(PA, PB)                                                                     \
+  _Pragma("unroll") for (int u = 0; u < PT; ++u) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[u][j] = \
+      __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[fb][PA][u], b[fb][PB][j], acc[u][j], 0, 0, 0);
+      SVL_CT(2, 0)
+      SVL_CT(0, 2)
+      SVL_CT(1, 1)
+      SVL_CT(1, 0)
+      SVL_CT(0, 1)
+      SVL_CT(0, 0)
+#undef SVL_CT
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    SVL_PH(1)
+    __syncthreads();
+    SVL_PH(2)
+    if (more) sstore();
+    SVL_PH(3)
+    if (!last) {
+      __syncthreads();
+      SVL_PH(4)
+    }
+  }
+  // epilogue of the tile (its stores drain under the next tile's first MFMA phase): the fp32 kernel's (column = output
+  // channel, row = pixel of the wave), with the pixel offsets formed once per pixel tile in 32 bits -- the epilogue's VALU
+  // instructions wait for gaps in the other block's MFMA stream like every VALU instruction of a staging phase
+  tile_epilogue<TN, PT, false, true>(p, acc, img, y0, x0, 0, nullptr, gred, gbred, tid, tile);
+  SVL_PH(5)
+  tile += (int)gridDim.x;
+  if (tile >= ntiles) break;
+  img = limg; y0 = ly0; x0 = lx0;
+  __syncthreads();                                   // the staged slab 0 of the next tile is complete
+  }
+#ifdef SVL_CONV_PHASE_TIMING
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) atomicAdd(&g_conv_phase[i], ph[i]);
+    atomicAdd(&g_conv_phase[7], 1ull);
+  }
+#endif
+}
+
+// The weight planes image of conv3x3_tiled_h2_kernel: per output channel co one scale exponent e[co] (largest |w| of
+// its 9 Ct weights 2^-e in [2^14, 2^15); 0 for an all-zero channel), and for slab s (16 input channels) the two fp16 planes
+// [pl][tap * N + co][16 channels, halves swapped by swz] of w 2^-e[co] exactly as the kernel lays a slab's weights out in LDS;
+// the exponents follow the planes.
 __global__ __launch_bounds__(256) void conv_w_exps_kernel(const float* __restrict__ w, int N, int Ct, int* __restrict__ exps) {
   __shared__ float red[4];
   const int co = blockIdx.x;
   float m = 0.f;
   for (int i = threadIdx.x; i < 9 * Ct; i += 256) m = fmaxf(m, fabsf(w[(long)co * (9 * Ct) + i]));
   m = block_max_256(m, red);
-  if (threadIdx.x == 0) {
-    const int e = m > 0.f ? __builtin_amdgcn_frexp_expf(m) - 15 : 0;
-    exps[co] = e < -100 ? -100 : (e > 100 ? 100 : e);
-  }
+  if (threadIdx.x == 0) exps[co] = max_exp_of(m, 0);
 }
 __global__ __launch_bounds__(256) void conv_w_planes_kernel(const float* __restrict__ w, int N, int Ct, const int* __restrict__ exps,
                                                             _Float16* __restrict__ out) {
@@ -975,16 +827,8 @@ __global__ __launch_bounds__(256) void conv_w_planes_kernel(const float* __restr
   const int co = (int)(rest % N);
   rest /= N;
   const int tap = (int)(rest % 9), s = (int)(rest / 9);
-  const float4 v4 = *reinterpret_cast<const float4*>(w + (long)co * (9 * Ct) + tap * Ct + s * SLAB + 4 * q);
-  const int e = exps[co];
-  const float v[4] = {__builtin_amdgcn_ldexpf(v4.x, -e), __builtin_amdgcn_ldexpf(v4.y, -e), __builtin_amdgcn_ldexpf(v4.z, -e),
-                      __builtin_amdgcn_ldexpf(v4.w, -e)};
   f16x4 h0, h1;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h0[j] = (_Float16)v[j];
-    h1[j] = (_Float16)(v[j] - (float)h0[j]);
-  }
+  split2x4(*reinterpret_cast<const float4*>(w + (long)co * (9 * Ct) + tap * Ct + s * SLAB + 4 * q), exps[co], h0, h1);
   const int WPL = 9 * N * 16;
   _Float16* o = out + (long)s * 2 * WPL + swz(tap * N + co, q);
   *reinterpret_cast<f16x4*>(o) = h0;
@@ -1027,41 +871,45 @@ bool svl_conv3x3_tiled_eligible(const ConvTiledP& p) {
   if (p.ld1 % 4 || !a16(p.src1) || !a16(p.w)) return false;
   if (p.C2 > 0 && (!p.src2 || p.rep < 1 || p.ld2 % 4 || !a16(p.src2))) return false;
   if (p.act != SVL_ACT_NONE && p.act != SVL_ACT_GELU && p.act != SVL_ACT_RELU) return false;
+  if ((long)p.H * p.W * p.ldo >= (1L << 31)) return false;      // tile_epilogue forms an image's pixel offsets in 32 bits
   return (long)p.imgs * p.H * p.W >= 16384 && p.H >= PH && p.W >= PW;
 }
 
+namespace {
+// the three shapes of a split kernel: 16 x 16 patches (pt = 2, N = 32 only), else 8 x 16 patches at N = 32 / 64
+#define SVL_SPLIT_LAUNCH(KERNEL, N, pt, go)   \
+  do {                                        \
+    if ((pt) == 2) go(KERNEL<1, 2>);          \
+    else if ((N) == 32) go(KERNEL<1, 1>);     \
+    else go(KERNEL<2, 1>);                    \
+  } while (0)
+}  // namespace
+
 int svl_conv3x3_tiled_launch(const ConvTiledP& p, hipStream_t st, int* tiles_per_img) {
-  const int tx = (p.W + PW - 1) / PW, ty = (p.H + PH - 1) / PH;
-  if (tiles_per_img) *tiles_per_img = tx * ty;
-  const long blocks = (long)p.imgs * tx * ty;
-  SVL_CHECK_ARG(blocks < (1L << 31), "svl_conv3x3_tiled: grid too large");
-  if (svl_conv3x3_tiled_path() == SVL_PATH_BF16X) {   // the split emulation covers the narrow convolutions too
-    const bool wpre = p.w_planes != nullptr;     // planes given: the fp16 x 2 kernel; else the bf16 x 3 kernel splits the fp32 weights per block
+  const int tx = (p.W + PW - 1) / PW, ty1 = (p.H + PH - 1) / PH;
+  if (tiles_per_img) *tiles_per_img = tx * ty1;                    // (8-row tiles: what a refused call leaves)
+  SVL_CHECK_ARG((long)p.imgs * tx * ty1 < (1L << 31), "svl_conv3x3_tiled: grid too large");
+  // ONE choice of kernel: the pipe, then (split pipe) patch rows and operand format; the grid follows from it
+  const bool split = svl_conv3x3_tiled_path() == SVL_PATH_BF16X;   // the split emulation covers the narrow convolutions too
+  const int pt = split && p.N == 32 && p.H >= 2 * PH ? 2 : 1;      // 16 x 16 patches: two pixel tiles per wave
+  const int ty = pt == 2 ? (p.H + 2 * PH - 1) / (2 * PH) : ty1;
+  if (tiles_per_img && pt == 2) *tiles_per_img = tx * ty;
+  long blocks = (long)p.imgs * tx * ty;
+  if (split) {
     // persistent blocks: two per CU (the LDS image allows two), each walking tiles b, b + grid, ...
     static const long resident = [] {
       int dev = 0, cus = 256;
       if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
       return (long)(cus > 0 ? cus : 256) * 2;
     }();
-    if (p.N == 32 && p.H >= 2 * PH) {        // 16 x 16 patches: two pixel tiles per wave
-      const int ty2 = (p.H + 2 * PH - 1) / (2 * PH);
-      if (tiles_per_img) *tiles_per_img = tx * ty2;
-      const long nt2 = (long)p.imgs * tx * ty2;
-      const dim3 grid2((unsigned)(nt2 < resident ? nt2 : resident));
-      if (wpre) hipLaunchKernelGGL((conv3x3_tiled_h2_kernel<1, 2>), grid2, dim3(256), 0, st, p, tx, ty2);
-      else hipLaunchKernelGGL((conv3x3_tiled_bf16x_kernel<1, 2, false>), grid2, dim3(256), 0, st, p, tx, ty2);
-    } else {
-      const dim3 grid1((unsigned)(blocks < resident ? blocks : resident));
-      if (p.N == 32) {
-        if (wpre) hipLaunchKernelGGL((conv3x3_tiled_h2_kernel<1, 1>), grid1, dim3(256), 0, st, p, tx, ty);
-        else hipLaunchKernelGGL((conv3x3_tiled_bf16x_kernel<1, 1, false>), grid1, dim3(256), 0, st, p, tx, ty);
-      } else {
-        if (wpre) hipLaunchKernelGGL((conv3x3_tiled_h2_kernel<2, 1>), grid1, dim3(256), 0, st, p, tx, ty);
-        else hipLaunchKernelGGL((conv3x3_tiled_bf16x_kernel<2, 1, false>), grid1, dim3(256), 0, st, p, tx, ty);
-      }
-    }
-  } else if (p.N == 32) hipLaunchKernelGGL(conv3x3_tiled_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, p, tx, ty);
-  else hipLaunchKernelGGL(conv3x3_tiled_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, st, p, tx, ty);
+    if (blocks > resident) blocks = resident;
+  }
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, tx, ty); };
+  // planes given: the fp16 x 2 form; else the bf16 x 3 form splits the fp32 weights per block
+  if (split && p.w_planes) SVL_SPLIT_LAUNCH(conv3x3_tiled_h2_kernel, p.N, pt, go);
+  else if (split) SVL_SPLIT_LAUNCH(conv3x3_tiled_bf16x_kernel, p.N, pt, go);
+  else if (p.N == 32) go(conv3x3_tiled_kernel<1>);
+  else go(conv3x3_tiled_kernel<2>);
   SVL_LAUNCH_CHECK("svl_gemm_f32 (tiled 3x3 conv)");
   return SVL_OK;
 }
@@ -1079,11 +927,10 @@ extern "C" int svl_conv3x3_gn_f32(const float* src1, int64_t ld1, int C1, const 
                                   const float* w, int imgs, int H, int W, int N, float* out, int64_t ldo, float eps,
                                   double* ws, float* stats, const float* gn_in, const void* w_planes, svl_stream_t stream) {
   SVL_CHECK_ARG(src1 && w && out && ws && stats && imgs > 0 && N % 16 == 0, "svl_conv3x3_gn_f32: bad args");
-  ConvTiledP t;
+  ConvTiledP t = svl_conv3x3_tiled_params();
   t.src1 = src1; t.ld1 = ld1; t.C1 = C1; t.src2 = src2; t.ld2 = ld2; t.C2 = C2; t.rep = rep < 1 ? 1 : rep;
-  t.w = w; t.K = 9 * (C1 + C2); t.out = out; t.ldo = ldo; t.bias = nullptr; t.act = SVL_ACT_NONE; t.accumulate = 0;
-  t.imgs = imgs; t.H = H; t.W = W; t.N = N; t.sign = 1; t.gn_part = ws; t.gn_in = gn_in; t.w_planes = w_planes;
-  t.gnb_x = t.gnb_table = t.gnb_stats = nullptr; t.gnb_part = nullptr;
+  t.w = w; t.K = 9 * (C1 + C2); t.out = out; t.ldo = ldo;
+  t.imgs = imgs; t.H = H; t.W = W; t.N = N; t.gn_part = ws; t.gn_in = gn_in; t.w_planes = w_planes;
   if (!svl_conv3x3_tiled_eligible(t)) return SVL_ERR_UNSUPPORTED;
   SVL_CHECK_ARG(!gn_in || (((uintptr_t)gn_in & 15) == 0 && C1 % 4 == 0), "svl_conv3x3_gn_f32: gn_in must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
@@ -1134,10 +981,10 @@ extern "C" int svl_conv3x3_dgrad_gnb_f32(const float* dy, int64_t lddy, int C1, 
   SVL_CHECK_ARG(dy && w && out && gnb_x && gnb_table && gnb_stats && ws && chan_sums && imgs > 0 && N % 16 == 0,
                 "svl_conv3x3_dgrad_gnb_f32: bad args");
   if (svl_conv3x3_tiled_path() != SVL_PATH_BF16X) return SVL_ERR_UNSUPPORTED;      // (epilogue of the split kernel only)
-  ConvTiledP t;
-  t.src1 = dy; t.ld1 = lddy; t.C1 = C1; t.src2 = nullptr; t.ld2 = 0; t.C2 = 0; t.rep = 1;
-  t.w = w; t.K = 9 * C1; t.out = out; t.ldo = ldo; t.bias = nullptr; t.act = SVL_ACT_NONE; t.accumulate = accumulate;
-  t.imgs = imgs; t.H = H; t.W = W; t.N = N; t.sign = -1; t.gn_part = nullptr; t.gn_in = nullptr; t.w_planes = w_planes;
+  ConvTiledP t = svl_conv3x3_tiled_params();
+  t.src1 = dy; t.ld1 = lddy; t.C1 = C1;
+  t.w = w; t.K = 9 * C1; t.out = out; t.ldo = ldo; t.accumulate = accumulate;
+  t.imgs = imgs; t.H = H; t.W = W; t.N = N; t.sign = -1; t.w_planes = w_planes;
   t.gnb_x = gnb_x; t.gnb_table = gnb_table; t.gnb_stats = gnb_stats; t.gnb_part = ws;
   if (!svl_conv3x3_tiled_eligible(t)) return SVL_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
@@ -1205,11 +1052,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 1 ? 3
   const int gq = tid % (SL / 4);                      // this thread's channel quad of the slab (the same for all its pieces)
   const bool gn = p.gn_in != nullptr && c0 + 4 * gq < p.C1;
   auto gload = [&](int pi) {
-    int t = pi;
-    const int txi = t % tiles_x;
-    t /= tiles_x;
-    const int tyi = t % tiles_y, img = t / tiles_y;
-    const int y0 = tyi * PH, x0 = txi * PW;
+    int img, y0, x0;
+    tile_origin(pi, tiles_x, tiles_y, PH, img, y0, x0);
     rdok = 0;
 #pragma unroll
     for (int i = 0; i < DP; ++i) {
@@ -1252,7 +1096,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 1 ? 3
     for (int i = 0; i < XP; ++i) {
       const int f = tid + 256 * i;
       const unsigned in = (rxok >> i) & 1u;
-      if (f < NPIX * SL / 4) *reinterpret_cast<float4*>(xs + 4 * f) = gn ? gn_relu4(rx[i], gsc, gsh, in) : (in ? rx[i] : z4);
+      if (f < NPIX * SL / 4) *reinterpret_cast<float4*>(xs + 4 * f) = operand4(rx[i], gn, gsc, gsh, in);
     }
   };
 
@@ -1425,17 +1269,9 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   // gload = unconditional loads at clamped addresses, nothing else: the zeroing of out-of-image pixels happens in
   // sstore, on the far side of the compute phase and its barrier (a select next to the load makes the compiler sink the
   // load under the condition -- one exec-masked branch and one s_waitcnt per element).
-  auto coords = [&](int pi, int& img, int& y0, int& x0) {
-    int t = pi;
-    const int txi = t % tiles_x;
-    t /= tiles_x;
-    const int tyi = t % tiles_y;
-    img = t / tiles_y;
-    y0 = tyi * WPHT; x0 = txi * PW;
-  };
   auto gload = [&](int pi) {
     int img, y0, x0;
-    coords(pi, img, y0, x0);
+    tile_origin(pi, tiles_x, tiles_y, WPHT, img, y0, x0);
     const int spix = y0 * p.W + x0;
     const char* dimg = reinterpret_cast<const char*>(p.dy + cz) + (long)img * p.H * p.W * dld4;
 #pragma unroll
@@ -1464,7 +1300,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   // later, before anything is split.
   auto xform = [&](int pi, int par) {
     int img, y0, x0;
-    coords(pi, img, y0, x0);
+    tile_origin(pi, tiles_x, tiles_y, WPHT, img, y0, x0);
     const bool inner = y0 >= 1 && y0 + WPHT + 1 <= p.H && x0 >= 1 && x0 + PW + 1 <= p.W;
     float md = 0.f, mx = 0.f;
 #pragma unroll
@@ -1501,19 +1337,13 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(rx[z][j]));
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      md = fmaxf(md, __shfl_xor(md, o, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
+    md = wave_max(md);
+    mx = wave_max(mx);
     if (lane == 0) { smx[par][wave][0] = md; smx[par][wave][1] = mx; }
   };
-  auto exp_of = [](float m) {      // m 2^-e in [2^14, 2^15); an all-zero patch takes the floor
-    const int e = m > 0.f ? __builtin_amdgcn_frexp_expf(m) - 15 : -100;
-    return e < -100 ? -100 : (e > 100 ? 100 : e);
-  };
   // Running exponents (identical in every producer thread): a patch is staged with max(its own exponent, the largest one used
-  // so far) -- never below what the accumulators hold, so the consumers only ever scale them DOWN (conv3x3_tiled_h2_kernel).
+  // so far) -- never below what the accumulators hold, so the consumers only ever scale them DOWN (as in
+  // conv3x3_tiled_h2_kernel; an all-zero patch takes the floor).
   int e_rd = -100, e_rx = -100;
   auto sstore = [&](int buf) {
     _Float16* dsT = smw + buf * BUFE;
@@ -1521,7 +1351,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float md = smx[buf][0][0], mx = smx[buf][0][1];
 #pragma unroll
     for (int w = 1; w < 6; ++w) { md = fmaxf(md, smx[buf][w][0]); mx = fmaxf(mx, smx[buf][w][1]); }
-    const int ed = exp_of(md), ex = exp_of(mx);
+    const int ed = slab_exp_of(md), ex = slab_exp_of(mx);
     e_rd = ed > e_rd ? ed : e_rd;
     e_rx = ex > e_rx ? ex : e_rx;
     if (tid == 0) { sexp[buf][0] = e_rd; sexp[buf][1] = e_rx; }
@@ -1644,8 +1474,8 @@ extern "C" int svl_conv3x3_wgrad_tiled_groups(int imgs, int H, int W, int Ct, in
   const int nslab = Ct / 32;
   // measured: Co = 64 is best with one full round of its 2 resident blocks per CU, Co = 32 with 1.5x that
   long g = (Co > 32 ? 512 : 768) / (nslab < 1 ? 1 : nslab);
-  // the bf16 x 6 kernel: twelve-wave blocks with double-buffered LDS, ONE block per CU -> one round of 256 blocks (any
-  // value is valid for either kernel; the arithmetic switch is only read here to size the grid well)
+  // the fp16 x 2 kernel (conv3x3_wgrad_tiled_h2_kernel): twelve-wave blocks with double-buffered LDS, ONE block per CU -> one
+  // round of 256 blocks (any value is valid for either kernel; the arithmetic switch is only read here to size the grid well)
   if (svl_conv3x3_tiled_path() == SVL_PATH_BF16X) {
     if (Co == 32 && Ct % 64 == 0) g = 256 / (Ct / 64);
     if (Co == 32 && Ct == 32) g = 512;               // <1, 1, 2>: 256 blocks, each leaves two slabs
@@ -1663,7 +1493,7 @@ extern "C" int svl_conv3x3_wgrad_tiled(const float* dy, int64_t lddy, int Co, co
                                        float* slabs, int groups, const float* gn_in, svl_stream_t stream) {
   auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   const bool emu6 = svl_conv3x3_tiled_path() == SVL_PATH_BF16X;
-  // Co = 128 exists on the bf16 x 6 kernel only (two blocks of 64 output channels per patch group)
+  // Co = 128 exists on the fp16 x 2 kernel only (two blocks of 64 output channels per patch group)
   SVL_CHECK_ARG(dy && src1 && slabs && (Co == 32 || Co == 64 || (Co == 128 && emu6)) && C1 > 0 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 &&
                     (C1 + C2) % 32 == 0 &&
                     lddy % 4 == 0 && ld1 % 4 == 0 && a16(dy) && a16(src1) && imgs > 0 && H >= PH && W >= PW &&

@@ -10,6 +10,7 @@
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CH = 1024;        // bytes of one (k-group, row block, plane) chunk
@@ -40,6 +41,37 @@ __device__ __forceinline__ int scale_exp_of(float bound) {
   const int e = __builtin_amdgcn_frexp_expf(bound) - 15;      // bound = f 2^E, f in [0.5, 1)
   return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
+
+// The convolutions' operands (conv_tiled.hip, conv_dil.hip) take their scale from a block MAXIMUM found while the block stages
+// them: m 2^-e in [2^14, 2^15), clamped to +-100; an all-zero block takes `zero_e`.
+__device__ __forceinline__ int max_exp_of(float m, int zero_e) {
+  const int e = m > 0.f ? __builtin_amdgcn_frexp_expf(m) - 15 : zero_e;
+  return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+// ... of an activation slab: all zeros take the floor, so that any later slab of the same accumulators raises the exponent
+__device__ __forceinline__ int slab_exp_of(float m) { return max_exp_of(m, -100); }
+// x 2^-e = h0 + h1 for a quad: two round-to-nearest fp16 terms (23 significand bits for every element within 2^-17 of the maximum)
+__device__ __forceinline__ void split2x4(const float4 x, int e, f16x4& h0, f16x4& h1) {
+  const float v[4] = {__builtin_amdgcn_ldexpf(x.x, -e), __builtin_amdgcn_ldexpf(x.y, -e), __builtin_amdgcn_ldexpf(x.z, -e),
+                      __builtin_amdgcn_ldexpf(x.w, -e)};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h0[j] = (_Float16)v[j];
+    h1[j] = (_Float16)(v[j] - (float)h0[j]);
+  }
+}
+__device__ __forceinline__ float absmax4(const float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+// The maximum's way through a four-wave block: every wave leaves its own in smax[wave]; after a barrier block_max4 reads all four
+__device__ __forceinline__ float wave_max(float m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  return m;
+}
+__device__ __forceinline__ void wave_max_to(float m, float* smax, int lane, int wave) {
+  m = wave_max(m);
+  if (lane == 0) smax[wave] = m;
+}
+__device__ __forceinline__ float block_max4(const float* smax) { return fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3])); }
 
 // The 16 bytes of (k-group kg, row rr of the plane buffer, lane half h) in plane 0; plane pl is CH * pl further on.
 // p_ks = bytes between k-groups (rows_padded * 32 * NP).

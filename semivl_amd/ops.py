@@ -1342,8 +1342,8 @@ def cached_pack(W, tag, fn):
 
 
 def conv3x3_weight_planes(pack, N, Ct):
-    """bf16 x 3 planes of a narrow 3x3 convolution's packed weights [N, 9 Ct] in the tiled kernel's LDS image
-    (svl_conv3x3_weight_planes), or None when the tiled split kernel cannot use one."""
+    """fp16 x 2 planes (+ one exponent per output channel) of a narrow 3x3 convolution's packed weights [N, 9 Ct] in the
+    tiled kernel's LDS image (svl_conv3x3_weight_planes), or None when the tiled split kernel cannot use one."""
     if not (pack.is_cuda and N in (32, 64, 128) and Ct % 16 == 0):     # (128: the dilated ASPP convolutions, conv_dil.hip)
         return None
     lib = L.load()

@@ -1647,6 +1647,58 @@ def test_tiled_narrow_conv3x3_split_emulation(dev, emu_mode, b, N, H, W, C1, C2,
     assert torch.equal(y, y2), "deterministic"
 
 
+@pytest.mark.parametrize("N,H,W,C", [(64, 8, 16, 32), (32, 16, 16, 16), (32, 9, 17, 16)])
+def test_tiled_conv3x3_blocks_walk_several_tiles(dev, emu_mode, N, H, W, C):
+    """conv3x3_tiled_h2_kernel / conv3x3_tiled_bf16x_kernel (mode 6) when their persistent blocks walk from tile to tile: the
+    grid is min(tiles, 2 x CUs), and every other case of this file has fewer tiles than that.  Here tiles = 4 x CUs + 3 (four
+    per image on the ragged 9 x 17 map: the next multiple of four), so every block computes two or three tiles and the last
+    round is partial -- <2, 1> on 8 x 16 maps, <1, 2> on 16 x 16, <1, 1> on 9 x 17; with the planes image (NP = 2: the running exponent
+    starts afresh at each tile) and with a bare pack (NP = 3).  Small integers, image i scaled by 2^(3 ((5 i) mod 7) - 9) -- the
+    consecutive tiles of a block lie up to 2^18 apart, in both directions -- weights integers / 8, one all-zero image in the
+    middle (its tile takes the exponent floor): every product is exact in both split forms and every sum an integer multiple
+    of one power of two per image below 2^24, so the forward and the mirrored-tap input gradient EQUAL the float64 result
+    rounded to fp32.  On the first shape the launches with the GroupNorm epilogues leave the same bits as the plain ones."""
+    from semivl_amd import ops, lib as L
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    pht = 16 if (N == 32 and H >= 16) else 8                 # patch rows of the instantiation this shape reaches
+    per_img = -(-H // pht) * -(-W // 16)
+    n = -(-(4 * cus + 3) // per_img)
+    assert 2 * (2 * cus) < n * per_img < 3 * (2 * cus) and n * H * W >= 16384
+    g = torch.Generator().manual_seed(97)
+    scale = torch.tensor([2.0 ** (3 * ((5 * i) % 7) - 9) for i in range(n)]).view(n, 1, 1, 1)
+    x = torch.randint(-4, 5, (n, C, H, W), generator=g).float() * scale
+    x[n // 2] = 0.0
+    w = torch.randint(-4, 5, (N, C, 3, 3), generator=g).float() / 8        # forward: C -> N channels
+    wb = torch.randint(-4, 5, (C, N, 3, 3), generator=g).float() / 8       # input gradient of a convolution N -> C: N outputs
+    x, w, wb = x.to(dev), w.to(dev), wb.to(dev)
+    ref = F.conv2d(x.double(), w.double(), padding=1).float()
+    xz = torch.zeros(n, N, H, W, device=dev, dtype=torch.float64, requires_grad=True)
+    (gref,) = torch.autograd.grad(F.conv2d(xz, wb.double(), padding=1), xz, x.double())
+    gref = gref.float()
+    emu_mode(6)
+    wf, _ = ops.pack_conv_w(w)
+    _, wd = ops.pack_conv_w(wb)
+    assert ops.w_planes_of(wf) is not None and ops.w_planes_of(wd) is not None
+    xs = nhwc(x)
+    for name, pf, pd in (("planes", wf, wd), ("bare", wf.clone(), wd.clone())):
+        assert (ops.w_planes_of(pf) is None) == (name == "bare")
+        y = ops.conv_fwd(xs, C, n, H, W, C, pf, N, 3, 3, 1, 1)
+        assert L.load().svl_last_gemm_path() == 1, "the tiled split kernel took the launch"
+        assert torch.equal(nchw(y, n, H, W), ref), name
+        dx = ops.conv_dgrad(xs, C, n, H, W, C, pd, N, 3, 3, 1, 1)
+        assert L.load().svl_last_gemm_path() == 1
+        assert torch.equal(nchw(dx, n, H, W), gref), name
+        if (H, W) == (8, 16):
+            got = ops.conv3x3_gn(xs, C, n, H, W, C, pf, N, 1e-5)
+            assert got is not None and torch.equal(got[0], y), name
+            G = N // 16
+            gn_x = rnd(n * H * W, N, dev=dev, seed=98)
+            gamma, beta = rnd(N, dev=dev) + 1.0, rnd(N, dev=dev)
+            st = ops.groupnorm_fwd(gn_x, N, gamma, beta, 1e-5, n, H * W, N, G, True, ops.empty(n * H * W, N, device=dev), N)
+            got = ops.conv3x3_dgrad_gnb(xs, C, n, H, W, C, pd, N, gn_x, st, gamma, beta, G)
+            assert got is not None and torch.equal(got[0], dx), name
+
+
 @pytest.mark.parametrize("C,Co,H,W,n", [(32, 64, 32, 32, 16), (64, 32, 32, 32, 16), (32, 32, 32, 64, 8), (64, 128, 24, 40, 18)])
 def test_tiled_wgrad_running_exponents(dev, emu_mode, C, Co, H, W, n):
     """conv3x3_wgrad_tiled_h2_kernel (mode 6): both operands of the narrow 3x3 weight gradient are activations and take a
